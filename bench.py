@@ -17,12 +17,21 @@ Workloads (--workload):
   finetune  configs[2]/[3]: one LoRA fine-tune step = log-mel + encoder fwd/bwd + decoder/CE + gradient exchange + AdamW
   noop      launcher / rendezvous / timing / JSON rehearsal without touching the GPU (CPU test of the N > 1 plumbing)
 
-The JSON line carries, besides the driver's contract fields:
+A plain encode run (no --full) sets up, warms up, times exactly --steps steps, writes --dump-outputs if given and prints the
+JSON line: the driver's contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) and
+  ranks         per-rank clips/s, the collective backend and the world size an all-reduce of ones actually returned
+With --full the encode workload also measures and checks what the headline does not need:
   roofline      the dominant kernel class (the MFMA GEMMs), timed live with HIP events on the launch stream;
                 achieved = algorithmic FLOP (2 M N K per launch) / event time, peak = dense bf16 MFMA peak
+  time_share_ms_per_step, power, the other kind of weights, other_precisions, outlier_profile, configs (the other 1-GPU configurations)
   cpu_baseline  oracle/ (CPU restatement of the reference) timed on this host's cores on a bounded sample (rank 0, N=1)
   parity        HIP outputs vs that oracle on the same sample
-  ranks         per-rank clips/s, the collective backend and the world size an all-reduce of ones actually returned
+The --no-* options switch single blocks of --full off.  The finetune and sweep workloads report their own blocks as before.
+
+--dump-outputs DIR writes, after the timed steps, what rank 0's timed path returned in its last step as DIR/<name>.npy (float32 /
+float64, under 64 MB in all): encode -> last_hidden_state (whole, or a fixed seeded sample of its (clip, position) rows listed in
+last_hidden_state_rows.npy), finetune -> loss, sweep -> hidden_checksum.  The inputs are seeded, so runs with the same arguments
+(and two builds of the project) can be compared output for output.
 """
 from __future__ import annotations
 
@@ -86,6 +95,11 @@ def parse():
                          "everywhere (the library's own default); bf16: gradient contractions in single bf16 products (~0.5 %% gradient error)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, the real multi-GPU path) or gloo (rehearsal of the N > 1 code path on one GPU: every rank on cuda:0)")
+    ap.add_argument("--full", action="store_true",
+                    help="encode workload: besides the headline, the GEMM roofline and time shares, package power, the other kind of weights, the other "
+                         "precisions, the CPU baseline and parity, the outlier profile and the other 1-GPU configurations (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step (rank 0) as DIR/<name>.npy, float32 / float64, < 64 MB")
     return ap.parse_args()
 
 
@@ -326,7 +340,7 @@ def finetune_cpu_baseline(a, torch, cfg, labels_all):
                       "1 warm-up + 2 timed passes, median %.2f s per pass" % (n, a.lora_r, m), "threads_note": note}
 
 
-def finetune_measure(a, R, bwd, with_cpu_baseline):
+def finetune_measure(a, R, bwd, with_cpu_baseline, dump=None):
     """One measured fine-tune configuration on this rank's GPU (see finetune_main): warm-up, EXACTLY a.steps timed steps, class shares.
     bwd: None = the library default (every GEMM of the step in the forward's split-bf16 format), "f16f8" = the MLP's four GEMMs per layer in f16f8."""
     torch, dev, rank, world = R.torch, R.dev, R.rank, R.world
@@ -358,6 +372,8 @@ def finetune_measure(a, R, bwd, with_cpu_baseline):
         _lib.prof_collect(k)
     dt, mine, _ = R.timed(step, a.steps)
     gemm_ms, gemm_n, gemm_flop = _lib.prof_collect("gemm")
+    if dump and rank == 0:
+        dump_outputs(dump, {"loss": [state["loss"]]})      # the last timed step's loss, before the extra step below replaces it
     _lib.prof_enable(True, [k for k in _lib.PROF_CLASSES if k != "gemm"])
     tr.exchange_report()                                   # starts (and clears) the bucket timing of libawt's communicator: the extra step below is the one reported
     step()
@@ -438,9 +454,9 @@ def finetune_main(a):
     R = Ranks(a)
     if a.backward_precision is not None:
         bwd = None if a.backward_precision == "bf16x3" else a.backward_precision
-        result = finetune_measure(a, R, bwd, not a.no_cpu_baseline)
+        result = finetune_measure(a, R, bwd, not a.no_cpu_baseline, a.dump_outputs)
     else:
-        result = finetune_measure(a, R, None, not a.no_cpu_baseline)
+        result = finetune_measure(a, R, None, not a.no_cpu_baseline, a.dump_outputs)
         if a.precision == "bf16x3":
             for key, bwd in (("f16f8_mlp", "f16f8"), ("bf16_backward", "bf16")):
                 fast = finetune_measure(a, R, bwd, False)
@@ -457,7 +473,7 @@ def finetune_main(a):
     R.finish()
 
 
-def sweep_measure(a, R, shard, t_synth, with_cpu_baseline):
+def sweep_measure(a, R, shard, t_synth, with_cpu_baseline, dump=None):
     """The whole seeded clip set, end to end, once, on this rank's pre-staged shard (host int16 [n_local, 64000])."""
     from mlx8_ws_audio_transformer_amd import _lib, sweep, weights as wts
     from mlx8_ws_audio_transformer_amd.encoder import NativeWhisperEncoder
@@ -478,6 +494,8 @@ def sweep_measure(a, R, shard, t_synth, with_cpu_baseline):
     dt, mine, n_local = R.timed(lambda: sweep.encode_sweep(enc, pcm, a.batch, sink), 1)
     gemm_ms, gemm_n, gemm_flop = _lib.prof_collect("gemm")
     _lib.prof_enable(False)
+    if dump and R.rank == 0:
+        dump_outputs(dump, {"hidden_checksum": [float(check.item())]})
     rates = R.gather(n_local / mine)
     checks = R.gather(float(check.item()))
     nb = -(-pcm.shape[0] // a.batch)
@@ -531,7 +549,7 @@ def sweep_main(a):
     shard, first = sweep.stage_shard(a.clips, rank, world, seed=1234)     # host synthesis (forks a pool): before the GPU is touched
     t_synth = time.perf_counter() - t0
     R = Ranks(a)
-    result = sweep_measure(a, R, shard, t_synth, not a.no_cpu_baseline)
+    result = sweep_measure(a, R, shard, t_synth, not a.no_cpu_baseline, a.dump_outputs)
     if R.rank == 0:
         result["wall_s"] = round(time.time() - T_START, 1)
         print(json.dumps(result))
@@ -656,6 +674,33 @@ def load_bench_weights(torch, enc, W):
     return enc
 
 
+DUMP_MAX_BYTES = 60 * 2 ** 20      # --dump-outputs: all files of one run together stay under 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: array} -> path/<name>.npy; float32 / float64 as they are, anything else as float64."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        if v.dtype not in (np.float32, np.float64):
+            v = v.astype(np.float64)
+        np.save(os.path.join(path, name + ".npy"), v)
+
+
+def hidden_dump(torch, hidden):
+    """last_hidden_state [B, S, d] (fp32, on the device) as dump arrays: whole when it fits DUMP_MAX_BYTES, else a fixed sample of its rows
+    (seed 0, drawn from the flat row index b * S + s, ascending), the row indices dumped beside it."""
+    import numpy as np
+    B, S, d = hidden.shape
+    n = DUMP_MAX_BYTES // (4 * d + 8)
+    if B * S * d * 4 <= DUMP_MAX_BYTES:
+        return {"last_hidden_state": hidden.cpu().numpy()}
+    idx = np.sort(np.random.default_rng(0).choice(B * S, size=n, replace=False))
+    rows = hidden.reshape(B * S, d)[torch.from_numpy(idx).to(hidden.device)]
+    return {"last_hidden_state": rows.cpu().numpy(), "last_hidden_state_rows": idx.astype(np.float64)}
+
+
 def cpu_budget():
     """(threads to use, note): the cores this process may actually RUN on = min(affinity mask, cgroup CPU quota).  On the GPU box the mask
     shows all 256 logical CPUs of the host while the container's share is one GPU's worth of it: the oracle on 256 threads ran 8x SLOWER
@@ -751,28 +796,20 @@ def gemm_algorithmic_bytes_per_step(exact_frac: float) -> float:
     return exact_frac * GEMM_ALGO_BYTES_PER_STEP_EXACT + (1.0 - exact_frac) * GEMM_ALGO_BYTES_PER_STEP
 
 
-def measure_encode(a, R, _lib, enc, pcm, kind):
-    """Warm-up, then EXACTLY a.steps timed passes of the hot path (barrier + synchronize on both sides, max over ranks) with the GEMM class
-    event-timed live on the launch stream, then one extra untimed pass for the other classes' shares.  Returns the block both weight cases
-    share: value, ms_per_step, roofline (with what the LIBRARY says about the weights, not what the command line asked for), time shares."""
+def measure_encode(a, R, _lib, enc, pcm, kind, profile=True):
+    """Warm-up, then EXACTLY a.steps timed passes of the hot path (barrier + synchronize on both sides, max over ranks).  profile (--full):
+    the GEMM class event-timed live on the launch stream, then one extra untimed pass for the other classes' shares.  Returns the block both
+    weight cases share: value, ms_per_step (with profile: roofline, with what the LIBRARY says about the weights, not what the command line
+    asked for, and time shares), the seconds of the timed region and the last step's output."""
     B, world = pcm.shape[0], R.world
     for _ in range(max(1, a.warmup)):
         enc.encode_pcm(pcm)
     R.sync()
-    _lib.prof_enable(True, ["gemm"])
-    for k in _lib.PROF_CLASSES:
-        _lib.prof_collect(k)
+    if profile:
+        _lib.prof_enable(True, ["gemm"])
+        for k in _lib.PROF_CLASSES:
+            _lib.prof_collect(k)
     dt, mine, out = R.timed(lambda: enc.encode_pcm(pcm), a.steps)
-    prof = {"gemm": _lib.prof_collect("gemm")}
-    _lib.prof_enable(True, [k for k in _lib.PROF_CLASSES if k != "gemm"])
-    enc.encode_pcm(pcm)
-    for k in _lib.PROF_CLASSES:
-        if k != "gemm":
-            ms, n, fl = _lib.prof_collect(k)
-            prof[k] = (ms * a.steps, n, fl)      # scaled so the per-step division below applies to every class
-    _lib.prof_enable(False)
-    gemm_ms, gemm_n, gemm_flop = prof["gemm"]
-    achieved = gemm_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
     n_exact, n_mat = enc.exact16_matrices()
     exact_frac = n_exact / max(1, n_mat)
     terms = float(_lib.MFMA_PER_PAIR[enc.precision])
@@ -786,29 +823,40 @@ def measure_encode(a, R, _lib, enc, pcm, kind):
                     else "the same initialisation rounded to fp16-representable values (a frozen base released in half precision)"),
         "fp16_exact_projection_matrices": "%d of %d (found by the library at upload)" % (n_exact, n_mat),
         "mfma_products_per_fragment_pair": round(terms, 3),
-        "roofline": {"bound": "mfma", "kernel": "gemm_f8s_kernel / gemm_pp_kernel / gemm_f8_kernel / gemm_kernel<%s> (all encoder GEMMs: conv stem, QKV, out, fc1, fc2)" % enc.precision,
-                     "achieved": round(achieved, 2), "peak": PEAK_BF16_DENSE_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(achieved / PEAK_BF16_DENSE_TFLOPS, 4), "traffic": None,
-                     "launches": gemm_n, "avg_launch_ms": round(gemm_ms / max(gemm_n, 1), 4),
-                     "mfma_issue_frac": round(terms * achieved / PEAK_BF16_DENSE_TFLOPS, 4)},
-        "time_share_ms_per_step": {k: round(v[0] / a.steps, 3) for k, v in prof.items()},
     }
-    # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc passes (tools/profile_round.sh); a committed summary is
-    # attached only when it was measured on THIS build (source hash), this precision and this kind of weights
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath) and a.model == "small" and not a.trimmed and B == 64:
-        try:
-            tj = json.load(open(tpath))
-            entries = tj.get("entries", [tj])
-            hit = [e for e in entries if e.get("build") == source_hash() and e.get("precision") == enc.precision and e.get("weights", "fp16") == kind]
-            if hit:
-                block["roofline"]["traffic"] = round(hit[-1]["per_kernel"]["gemm_kernel"]["hbm_bytes_per_launch"])
-                block["roofline"]["traffic_note"] = "bytes per GEMM launch, FETCH_SIZE x2 (gfx950) + WRITE_SIZE, rocprofv3 --pmc passes on this build (profiles/traffic.json)"
-                block["roofline"]["algorithmic_bytes_per_launch"] = round(gemm_algorithmic_bytes_per_step(exact_frac) / 50)
-            else:
-                block["roofline"]["traffic_note"] = "profiles/traffic.json has no entry for build %s / %s / %s weights: not attached" % (source_hash(), enc.precision, kind)
-        except Exception:
-            pass
+    if profile:
+        prof = {"gemm": _lib.prof_collect("gemm")}
+        _lib.prof_enable(True, [k for k in _lib.PROF_CLASSES if k != "gemm"])
+        enc.encode_pcm(pcm)
+        for k in _lib.PROF_CLASSES:
+            if k != "gemm":
+                ms, n, fl = _lib.prof_collect(k)
+                prof[k] = (ms * a.steps, n, fl)      # scaled so the per-step division below applies to every class
+        _lib.prof_enable(False)
+        gemm_ms, gemm_n, gemm_flop = prof["gemm"]
+        achieved = gemm_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+        block["roofline"] = {"bound": "mfma", "kernel": "gemm_f8s_kernel / gemm_pp_kernel / gemm_f8_kernel / gemm_kernel<%s> (all encoder GEMMs: conv stem, QKV, out, fc1, fc2)" % enc.precision,
+                             "achieved": round(achieved, 2), "peak": PEAK_BF16_DENSE_TFLOPS, "unit": "TFLOP/s",
+                             "frac": round(achieved / PEAK_BF16_DENSE_TFLOPS, 4), "traffic": None,
+                             "launches": gemm_n, "avg_launch_ms": round(gemm_ms / max(gemm_n, 1), 4),
+                             "mfma_issue_frac": round(terms * achieved / PEAK_BF16_DENSE_TFLOPS, 4)}
+        block["time_share_ms_per_step"] = {k: round(v[0] / a.steps, 3) for k, v in prof.items()}
+        # HBM traffic of the dominant kernel comes from separate rocprofv3 --pmc passes (tools/profile_round.sh); a committed summary is
+        # attached only when it was measured on THIS build (source hash), this precision and this kind of weights
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tpath) and a.model == "small" and not a.trimmed and B == 64:
+            try:
+                tj = json.load(open(tpath))
+                entries = tj.get("entries", [tj])
+                hit = [e for e in entries if e.get("build") == source_hash() and e.get("precision") == enc.precision and e.get("weights", "fp16") == kind]
+                if hit:
+                    block["roofline"]["traffic"] = round(hit[-1]["per_kernel"]["gemm_kernel"]["hbm_bytes_per_launch"])
+                    block["roofline"]["traffic_note"] = "bytes per GEMM launch, FETCH_SIZE x2 (gfx950) + WRITE_SIZE, rocprofv3 --pmc passes on this build (profiles/traffic.json)"
+                    block["roofline"]["algorithmic_bytes_per_launch"] = round(gemm_algorithmic_bytes_per_step(exact_frac) / 50)
+                else:
+                    block["roofline"]["traffic_note"] = "profiles/traffic.json has no entry for build %s / %s / %s weights: not attached" % (source_hash(), enc.precision, kind)
+            except Exception:
+                pass
     gf = ENCODER_GFLOP_PER_CLIP.get((a.model, a.trimmed))
     if gf:
         block["end_to_end_algorithmic_tflops"] = round(block["value"] * gf / 1e3, 2)
@@ -862,9 +910,9 @@ def other_configs(a, R, torch, dev, _lib, staged):
 
 
 def encode_main(a):
-    sampler = PowerSampler() if (int(os.environ.get("RANK", "0")) == 0 and a.gpus == 1 and not a.no_power) else None   # a sysfs-reading thread; never under a profiler
+    sampler = PowerSampler() if (a.full and int(os.environ.get("RANK", "0")) == 0 and a.gpus == 1 and not a.no_power) else None   # a sysfs-reading thread; never under a profiler
     staged = None
-    if a.gpus == 1 and "WORLD_SIZE" not in os.environ and not a.no_configs and a.model == "small" and not a.trimmed:
+    if a.full and a.gpus == 1 and "WORLD_SIZE" not in os.environ and not a.no_configs and a.model == "small" and not a.trimmed:
         from mlx8_ws_audio_transformer_amd import sweep as _sweep
         t0 = time.perf_counter()
         shard, _ = _sweep.stage_shard(a.clips, 0, 1, seed=1234)        # the sweep block's clip set: host synthesis forks a pool, so before the GPU is touched
@@ -887,7 +935,9 @@ def encode_main(a):
                                   bench_weights(cfg, kind))
 
     enc = build(a.weights)
-    head, dt, mine, out = measure_encode(a, R, _lib, enc, pcm, a.weights)
+    head, dt, mine, out = measure_encode(a, R, _lib, enc, pcm, a.weights, profile=a.full)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, hidden_dump(torch, out))
     rates = R.gather(B * a.steps / mine)
     result = {
         "metric": "4s@16kHz clips/sec through mel+Whisper-%s encoder" % a.model,
@@ -901,7 +951,7 @@ def encode_main(a):
                    "mfma_products_per_fragment_pair": head["mfma_products_per_fragment_pair"], "weights": head["weights"],
                    "fp16_exact_projection_matrices": head["fp16_exact_projection_matrices"],
                    "parallelism": "dp%d (clip shards, no data-path collective)" % world},
-        "roofline": head["roofline"], "time_share_ms_per_step": head["time_share_ms_per_step"],
+        **{k: head[k] for k in ("roofline", "time_share_ms_per_step") if k in head},
         "ranks": R.describe(rates), "build": source_hash(),
     }
     for k in ("end_to_end_algorithmic_tflops", "end_to_end_frac_of_mfma_peak"):
@@ -909,7 +959,7 @@ def encode_main(a):
             result[k] = head[k]
 
     side_out = {}
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         # ---- package power and shader clock while the headline workload runs (sysfs samples on a thread of this process, outside the timed
         #      region): the encoder sits at the package power limit, which is what caps roofline.frac
         result["power"] = sampler.window(torch, lambda: enc.encode_pcm(pcm), dev) if sampler else None

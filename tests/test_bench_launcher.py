@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -122,3 +124,55 @@ def test_power_is_read_from_sysfs_without_any_child_process(tmp_path):
             os.environ.pop("ROCP_TOOL_LIBRARIES")
         else:
             os.environ["ROCP_TOOL_LIBRARIES"] = old
+
+
+def test_hidden_dump_is_a_fixed_sample_under_64_mb(tmp_path):
+    """--dump-outputs: the B = 64 Whisper-small output (295 MB) is dumped as the same seeded sample of (clip, position) rows every time, its
+    row indices beside it, all float32 / float64 and under 64 MB together; an output that fits is dumped whole."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    h = torch.randn(64, 1500, 768, generator=torch.Generator().manual_seed(0))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), bench.hidden_dump(torch, h))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["last_hidden_state.npy", "last_hidden_state_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) < 64e6
+    x, rows = (np.load(tmp_path / "a" / n) for n in names)
+    assert x.dtype == np.float32 and rows.dtype == np.float64 and x.shape == (rows.size, 768) and rows.size > 16000
+    assert np.array_equal(x, h.reshape(-1, 768).numpy()[rows.astype(np.int64)])
+    assert all(np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)) for n in names)
+    small = torch.randn(2, 200, 384)
+    assert np.array_equal(bench.hidden_dump(torch, small)["last_hidden_state"], small.numpy())
+
+
+def test_full_and_dump_outputs_options_are_accepted(tmp_path):
+    r = _run("--workload", "noop", "--steps", "2", "--warmup", "0", "--full", "--dump-outputs", str(tmp_path / "out"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert j["steps"] == 2 and j["ms_per_step"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run prints the headline alone (no side blocks: those are --full's), with `ms_per_step` of exactly --steps timed steps, and
+    --dump-outputs writes the last timed step's hidden states; the inputs are seeded, so a second run dumps the same arrays."""
+    import numpy as np
+    args = ("--model", "tiny", "--trimmed", "--batch", "4", "--steps", "3", "--warmup", "1")
+    out = []
+    for d in ("a", "b"):
+        r = _run(*args, "--dump-outputs", str(tmp_path / d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        out.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0]))
+    j = out[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j, k
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0 and j["unit"] == "clips/s" and j["dtype"] == "fp16"
+    assert abs(j["value"] - 4 * 1e3 / j["ms_per_step"]) <= 0.01 * j["value"]
+    for k in ("roofline", "time_share_ms_per_step", "power", "other_precisions", "cpu_baseline", "parity", "outlier_profile", "configs"):
+        assert k not in j, k
+    assert os.listdir(tmp_path / "a") == ["last_hidden_state.npy"]
+    a, b = (np.load(tmp_path / d / "last_hidden_state.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (4, 200, 384) and np.isfinite(a).all() and np.abs(a).max() > 0
+    assert np.array_equal(a, b)
