@@ -26,10 +26,7 @@ constexpr int kThreads = 256;
 // QT (template parameter) = 32-query tiles per wave: K / V fragments, LDS tiles and the barrier are amortised over QT x 48
 // MFMAs.  QT = 2 for full launches; QT = 1 (twice the workgroups, half the time per K/V tile) when the grid would not
 // fill the chip's 512 workgroup slots (one or two clips).
-#ifndef AWT_ATTN_KB
-#define AWT_ATTN_KB 64
-#endif
-constexpr int KB = AWT_ATTN_KB;   // keys per tile (32 or 64)
+constexpr int KB = 64;           // keys per tile
 constexpr int NSUB = KB / 32;     // 32-key sub-tiles per tile
 constexpr int PLANE = KB * 64 * 2;  // 8 KiB: [64 keys][64 dims] bf16
 
@@ -131,15 +128,6 @@ __global__ __launch_bounds__(kThreads, 2) void attention_kernel(AttnArgs a) {
   const int voffx = voff ^ 64;
 
   const int ntiles = (a.S + KB - 1) / KB;
-#ifdef AWT_ATTN_STAGGER
-  // the two waves of a SIMD (one from each of the CU's two workgroups) alternate between an MFMA phase and a VALU phase of
-  // equal length; started together they stay in step and never overlap.  Delay the odd wave slot of the first round.
-  {
-    unsigned hwid;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-    if ((int)blockIdx.x < AWT_ATTN_STAGGER_BLOCKS && (hwid & 1)) __builtin_amdgcn_s_sleep(AWT_ATTN_STAGGER);
-  }
-#endif
   stage_kv<TERMS>(a, head_off, 0, smem, wave, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -294,11 +282,7 @@ template <int TERMS, int QT, bool F16 = false>
 int launch_t(const AttnArgs& a, hipStream_t s) {
   constexpr int lds = 2 * (TERMS == 3 ? 4 : 2) * PLANE;
   constexpr int QB = 4 * 32 * QT;
-  AWT_ONCE_PER_DEVICE(AWT_HIP_CHECK(hipFuncSetAttribute((const void*)attention_kernel<TERMS, QT, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-  dim3 grid(((a.S + QB - 1) / QB) * a.B * a.H);
-  hipLaunchKernelGGL((attention_kernel<TERMS, QT, F16>), grid, dim3(kThreads), lds, s, a);
-  AWT_HIP_CHECK(hipGetLastError());
-  return AWT_OK;
+  return launch_kernel<attention_kernel<TERMS, QT, F16>>(dim3(((a.S + QB - 1) / QB) * a.B * a.H), dim3(kThreads), lds, s, a);
 }
 
 }  // namespace

@@ -274,11 +274,7 @@ __global__ __launch_bounds__(kThreads, 2) void attention_bwd_kernel(BwdArgs a) {
 template <int TERMS, int MODE, int GT>
 int launch_mode(const BwdArgs& a, hipStream_t s) {
   constexpr int lds = 2 * ((TERMS == 3 ? 4 : 2) * PLANE + 512);
-  AWT_ONCE_PER_DEVICE(AWT_HIP_CHECK(hipFuncSetAttribute((const void*)attention_bwd_kernel<TERMS, MODE, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-  dim3 grid(((a.S + LB - 1) / LB) * a.B * a.H);
-  hipLaunchKernelGGL((attention_bwd_kernel<TERMS, MODE, GT>), grid, dim3(kThreads), lds, s, a);
-  AWT_HIP_CHECK(hipGetLastError());
-  return AWT_OK;
+  return launch_kernel<attention_bwd_kernel<TERMS, MODE, GT>>(dim3(((a.S + LB - 1) / LB) * a.B * a.H), dim3(kThreads), lds, s, a);
 }
 
 }  // namespace

@@ -427,10 +427,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f16f8_pipe_kernel(Attn8A
   //   slots 20..23  O^T += V8^T Pl8^T + Vl8^T P8^T  (et x 2)
   //                 (PV8 only; without it P V is the single fp16 product: P in [0, 1] rounds to 11 significant bits and the
   //                  normaliser is the sum of the unrounded P -- DESIGN.md "Numerics" for what that costs)
-#ifndef AWT_ATTN_DEPTH
-#define AWT_ATTN_DEPTH 2
-#endif
-  constexpr int NSLOT = PV8 ? 24 : 20, DEPTH = AWT_ATTN_DEPTH, RING = DEPTH + 1;   // fragments are read DEPTH slots ahead of their MFMA
+  constexpr int NSLOT = PV8 ? 24 : 20, DEPTH = 2, RING = DEPTH + 1;   // fragments are read DEPTH slots ahead of their MFMA
   // LDS: PV8 -- two 32 KB stages shared by K and V (K staged two tiles ahead, V one).  !PV8 -- three-deep rings (K three tiles ahead,
   // V two): a tile's LDS-DMA then has two iterations (~4 us) to land instead of one, and the wait at the end of an iteration only covers
   // the loads of the iteration before (counted vmcnt).  With one iteration of slack the timing-only build without the wait ran 18 % faster.
@@ -676,22 +673,14 @@ template <int NW, bool PV8>
 int launch_pipe(const Attn8Args& a, hipStream_t s) {
   constexpr int lds = PV8 ? 2 * STAGE : RING3_BYTES;
   constexpr int QB = 32 * NW;
-  AWT_ONCE_PER_DEVICE(AWT_HIP_CHECK(hipFuncSetAttribute((const void*)attention_f16f8_pipe_kernel<NW, PV8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-  dim3 grid(((a.S + QB - 1) / QB) * a.B * a.H);
-  hipLaunchKernelGGL((attention_f16f8_pipe_kernel<NW, PV8>), grid, dim3(64 * NW), lds, s, a);
-  AWT_HIP_CHECK(hipGetLastError());
-  return AWT_OK;
+  return launch_kernel<attention_f16f8_pipe_kernel<NW, PV8>>(dim3(((a.S + QB - 1) / QB) * a.B * a.H), dim3(64 * NW), lds, s, a);
 }
 
 template <int QT, int NW>
 int launch_t(const Attn8Args& a, hipStream_t s) {
   constexpr int lds = 2 * STAGE;
   constexpr int QB = NW * 32 * QT;
-  AWT_ONCE_PER_DEVICE(AWT_HIP_CHECK(hipFuncSetAttribute((const void*)attention_f16f8_kernel<QT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-  dim3 grid(((a.S + QB - 1) / QB) * a.B * a.H);
-  hipLaunchKernelGGL((attention_f16f8_kernel<QT, NW>), grid, dim3(64 * NW), lds, s, a);
-  AWT_HIP_CHECK(hipGetLastError());
-  return AWT_OK;
+  return launch_kernel<attention_f16f8_kernel<QT, NW>>(dim3(((a.S + QB - 1) / QB) * a.B * a.H), dim3(64 * NW), lds, s, a);
 }
 
 }  // namespace

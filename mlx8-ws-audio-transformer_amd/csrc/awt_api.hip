@@ -52,7 +52,7 @@ extern "C" int awt_tuning_set(const char* key, int value) {
     return AWT_OK;
   }
   if (!strcmp(key, "gemm_pp")) {
-    AWT_REQUIRE(value >= 0 && value <= 2, AWT_ERR_INVALID, "tuning_set: gemm_pp must be 0 (off, default), 1 (automatic) or 2 (wherever supported)");
+    AWT_REQUIRE(value >= 0 && value <= 2, AWT_ERR_INVALID, "tuning_set: gemm_pp must be 0 (off), 1 (automatic, default) or 2 (wherever supported)");
     awt_gemm_set_pp_mode(value);
     return AWT_OK;
   }
@@ -587,7 +587,7 @@ extern "C" int awt_encoder_create(awt_ctx* c, const awt_encoder_cfg* cfg, awt_en
   AWT_REQUIRE(cfg->ffn_dim > 0 && cfg->ffn_dim % 128 == 0, AWT_ERR_INVALID, "encoder_create: ffn_dim must be a multiple of 128");
   AWT_REQUIRE(cfg->n_mels > 0 && cfg->n_mels % 8 == 0 && cfg->n_mels <= 128, AWT_ERR_INVALID, "encoder_create: n_mels must be a multiple of 8, <= 128");
   AWT_REQUIRE(cfg->n_layers > 0 && cfg->n_ctx > 0, AWT_ERR_INVALID, "encoder_create: n_layers and n_ctx must be positive");
-  AWT_REQUIRE(cfg->mfma_terms == PREC_BF16 || cfg->mfma_terms == PREC_F16 || cfg->mfma_terms == PREC_BF16X3 || cfg->mfma_terms == PREC_F16X3 || cfg->mfma_terms == PREC_F16F8, AWT_ERR_INVALID,
+  AWT_REQUIRE(prec_known(cfg->mfma_terms), AWT_ERR_INVALID,
               "encoder_create: mfma_terms must be 1 (bf16), 2 (fp16), 3 (bf16x3), 4 (fp16x3) or 5 (f16f8)");
   AWT_REQUIRE(!cfg->training || cfg->mfma_terms == PREC_BF16 || cfg->mfma_terms == PREC_BF16X3, AWT_ERR_INVALID,
               "encoder_create: training keeps its activations as bf16 planes: mfma_terms must be 1 or 3 (gradients do not fit fp16's range unscaled)");
@@ -822,6 +822,7 @@ extern "C" size_t awt_op_linear_workspace_bytes(int M, int N, int K) {
 }
 extern "C" int awt_op_linear(awt_ctx* c, const float* x, const float* w, const float* bias, float* y, int M, int N, int K,
                              int terms, void* workspace, size_t ws_bytes, void* stream) {
+  AWT_REQUIRE(prec_known(terms), AWT_ERR_INVALID, "op_linear: terms must be 1 (bf16), 2 (fp16), 3 (bf16x3), 4 (fp16x3) or 5 (f16f8)");
   AWT_REQUIRE(c && x && w && y && workspace, AWT_ERR_INVALID, "op_linear: null argument");
   AWT_REQUIRE(M > 0 && N > 0 && N % 128 == 0 && K > 0 && K % 64 == 0, AWT_ERR_INVALID, "op_linear: N % 128 == 0 and K % 64 == 0 required");
   AWT_REQUIRE(ws_bytes >= awt_op_linear_workspace_bytes(M, N, K), AWT_ERR_WORKSPACE, "op_linear: workspace too small");
@@ -831,21 +832,6 @@ extern "C" int awt_op_linear(awt_ctx* c, const float* x, const float* w, const f
   bf16_t* xl = (bf16_t*)base;                 base += align_up((size_t)M * K * 2);
   bf16_t* wh = (bf16_t*)base;                 base += align_up((size_t)N * K * 2);
   bf16_t* wl = (bf16_t*)base;
-  if (terms == PREC_F16F6) {   // experimental: fp16 plane + two e3m2 planes (the second 2-byte plane's space holds both, 0.75 B per element each)
-#ifndef AWT_EXPERIMENTAL_F6
-    return awt_fail(AWT_ERR_INVALID, "op_linear (f16f6): the FP6 cross-term experiment is not part of this build (compile with -DAWT_EXPERIMENTAL_F6)");
-#else
-    AWT_REQUIRE(N % 256 == 0, AWT_ERR_INVALID, "op_linear (f16f6): N % 256 == 0 required");
-    Act ax6; ax6.p16 = xh; ax6.hi8 = (uint8_t*)xl; ax6.lo8 = (uint8_t*)xl + (size_t)M * K / 4 * 3;
-    uint8_t* w6 = (uint8_t*)wl; uint8_t* wl6 = w6 + (size_t)N * K / 4 * 3;
-    int rc6 = launch_split_planes_f6(c, x, M, K, xh, ax6.hi8, ax6.lo8, s); if (rc6) return rc6;
-    rc6 = launch_pack_weight_f6(c, w, N, K, wh, w6, wl6, s); if (rc6) return rc6;
-    Planes pw6; pw6.hi = wh; pw6.lo = (bf16_t*)w6; pw6.x8 = wl6; pw6.rows = N; pw6.ld = K;
-    GemmSeg sg6 = seg_plain(ax6, K, pw6, 0, K, M);
-    GemmOut o6{}; o6.f32 = y; o6.ldo = N; o6.bias = bias; o6.n_valid = N;
-    return launch_gemm(c, M, N, &sg6, 1, terms, EPI_F32, o6, s);
-#endif
-  }
   if (terms == PREC_F16F8 && awt_gemm_pp_mode() == 2 && gemm_pp_supported(M, N, K, EPI_F32)) {
     // the persistent ping-pong kernel (tuning knob "gemm_pp" = 2): x as split lines over the two x planes' space (its 256-row panel reads beyond M
     // stay inside the workspace: the packed weight image of N >= 256 rows follows), the weight in the packed region image over the two w planes' space
@@ -892,6 +878,7 @@ extern "C" int awt_op_layernorm(awt_ctx* c, const float* x, const float* gamma, 
 extern "C" size_t awt_op_attention_workspace_bytes(int B, int H, int S) { return 6 * align_up((size_t)B * H * S * 64 * 2); }
 extern "C" int awt_op_attention(awt_ctx* c, const float* q, const float* k, const float* v, float* o, int B, int H, int S,
                                 int terms, void* workspace, size_t ws_bytes, void* stream) {
+  AWT_REQUIRE(prec_known(terms), AWT_ERR_INVALID, "op_attention: terms must be 1 (bf16), 2 (fp16), 3 (bf16x3), 4 (fp16x3) or 5 (f16f8)");
   AWT_REQUIRE(c && q && k && v && o && workspace, AWT_ERR_INVALID, "op_attention: null argument");
   AWT_REQUIRE(ws_bytes >= awt_op_attention_workspace_bytes(B, H, S), AWT_ERR_WORKSPACE, "op_attention: workspace too small");
   hipStream_t s = (hipStream_t)stream;

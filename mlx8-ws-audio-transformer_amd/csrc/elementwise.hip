@@ -2,11 +2,14 @@
 #include "common.h"
 #include "gemm_pp.h"
 
-#ifndef AWT_LN_NT_LOAD
-#define AWT_LN_NT_LOAD 1   // -0.3 .. -0.4 ms per encoder step, most of it in the GEMM that follows (profiles/r03_gemm_experiments.txt)
-#endif
-
 namespace {
+
+// a 16-byte load of data the kernel reads exactly once: streaming, so that what the kernel writes stays cache-resident.  LayerNorm: -0.3 .. -0.4 ms per
+// encoder step, most of it in the GEMM that follows; LayerNorm backward: 8.94 -> 8.45 ms per fine-tune step (profiles/r03_gemm_experiments.txt)
+__device__ __forceinline__ float4 ldg_once(const float4* p) {
+  const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
+  return make_float4(t[0], t[1], t[2], t[3]);
+}
 
 // ------------------------------------------------------------------------------------------------ LayerNorm
 // One wave per row, the row lives in registers (d <= 1280): two-pass mean / variance in fp32 exactly like
@@ -28,12 +31,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 #pragma unroll
   for (int i = 0; i < kLnMaxChunks; ++i) {
     const int c = lane + 64 * i;
-#if AWT_LN_NT_LOAD   // the residual stream is read once here: a streaming load keeps the planes this kernel writes (the next GEMM's operand) cache-resident
-    if (c < nchunk) { const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xr + c)); v[i] = make_float4(t[0], t[1], t[2], t[3]); }
+    if (c < nchunk) v[i] = ldg_once(xr + c);      // the residual stream: the planes written here are the next GEMM's operand
     else v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-#else
-    v[i] = c < nchunk ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
     sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
   }
 #pragma unroll
@@ -199,18 +198,6 @@ __global__ __launch_bounds__(256) void im2col_conv1_kernel(const float* __restri
 // ------------------------------------------------------------------------------------------------ LayerNorm backward
 // dx = dres + rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * gamma,  xhat = (x - mean) * rstd.
 // Statistics are recomputed from the saved LayerNorm input (fp32), one wave per row, row in registers.
-#ifndef AWT_LNB_NT_LOAD
-#define AWT_LNB_NT_LOAD 1   // LayerNorm class of the fine-tune step 8.94 -> 8.45 ms (profiles/r03_gemm_experiments.txt)
-#endif
-// a 16-byte load of data this kernel reads exactly once (streaming when AWT_LNB_NT_LOAD)
-__device__ __forceinline__ float4 ldg_once(const float4* p) {
-#if AWT_LNB_NT_LOAD
-  const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-  return make_float4(t[0], t[1], t[2], t[3]);
-#else
-  return *p;
-#endif
-}
 // gscale multiplies dy (the power-of-two gradient scale enters at the final LayerNorm); out8: dx also as f16f8 operand planes (the next consumer is
 // an f16f8 GEMM: awt_encoder_cfg.backward_terms = 5)
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
@@ -410,48 +397,6 @@ __global__ __launch_bounds__(256) void outer_reduce_final_kernel(const float* __
   }
 }
 
-
-#ifdef AWT_EXPERIMENTAL_F6
-// ------------------------------------------------------------------------------------------------ PREC_F16F6 operand images (experimental)
-// One thread per (row, group of 32 consecutive k): fp16 plane + the two e3m2 planes.  WEIGHT: fragment-major images, exponent kF6Wgt.
-template <bool WEIGHT>
-__global__ __launch_bounds__(256) void planes_f6_kernel(const float* __restrict__ x, int M, int K, bf16_t* p16, uint8_t* hi6, uint8_t* lo6) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int groups = K >> 5;
-  if (idx >= (int64_t)M * groups) return;
-  const int m = (int)(idx / groups), g = (int)(idx - (int64_t)m * groups);
-  const float* src = x + (int64_t)m * K + 32 * g;
-  float v[32], lo[32];
-  bf16_t h[32];
-#pragma unroll
-  for (int i = 0; i < 32; i += 4) { const float4 t = *reinterpret_cast<const float4*>(src + i); v[i] = t.x; v[i + 1] = t.y; v[i + 2] = t.z; v[i + 3] = t.w; }
-#pragma unroll
-  for (int i = 0; i < 32; ++i) { h[i] = f32_to_f16(v[i]); lo[i] = v[i] - f16_to_f32(h[i]); }
-  constexpr int S = WEIGHT ? kF6Wgt : kF6Act;
-  const u32x6 qh = bf6x32<S>(v), ql = bf6x32<S + kF8Lo>(lo);
-  uint8_t *dh, *dl;
-  if (WEIGHT) {
-    const int64_t o = w6_byte_index(m, 32 * g, K >> 6);
-    dh = hi6 + o; dl = lo6 + o;
-#pragma unroll
-    for (int c8 = 0; c8 < 4; ++c8)
-      *reinterpret_cast<uint4*>(p16 + w16f8_index(m, 32 * g + 8 * c8, K >> 4)) =
-          make_uint4(pack2(h[8 * c8], h[8 * c8 + 1]), pack2(h[8 * c8 + 2], h[8 * c8 + 3]), pack2(h[8 * c8 + 4], h[8 * c8 + 5]), pack2(h[8 * c8 + 6], h[8 * c8 + 7]));
-  } else {
-    const int64_t o = (int64_t)m * (K / 4 * 3) + 24 * g;
-    dh = hi6 + o; dl = lo6 + o;
-#pragma unroll
-    for (int c8 = 0; c8 < 4; ++c8)
-      *reinterpret_cast<uint4*>(p16 + (int64_t)m * K + 32 * g + 8 * c8) =
-          make_uint4(pack2(h[8 * c8], h[8 * c8 + 1]), pack2(h[8 * c8 + 2], h[8 * c8 + 3]), pack2(h[8 * c8 + 4], h[8 * c8 + 5]), pack2(h[8 * c8 + 6], h[8 * c8 + 7]));
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    *reinterpret_cast<uint2*>(dh + 8 * i) = make_uint2(qh[2 * i], qh[2 * i + 1]);
-    *reinterpret_cast<uint2*>(dl + 8 * i) = make_uint2(ql[2 * i], ql[2 * i + 1]);
-  }
-}
-#endif  // AWT_EXPERIMENTAL_F6
 }  // namespace
 
 int launch_layernorm(awt_ctx* c, const float* x, const float* gamma, const float* beta, int M, int d, float eps,
@@ -482,7 +427,7 @@ int launch_split_f32(awt_ctx* c, const float* x, int64_t n, float scale, bf16_t*
 int launch_split_planes(awt_ctx* c, const float* x, int64_t n, float scale, int prec, int f8_exp, bf16_t* p16, bf16_t* lo16, uint8_t* hi8,
                         uint8_t* lo8, hipStream_t s, char* ilv) {
   AWT_REQUIRE(x && (p16 || ilv) && n > 0 && n % 4 == 0, AWT_ERR_INVALID, "split: n must be a positive multiple of 4");
-  AWT_REQUIRE(prec == PREC_BF16 || prec == PREC_F16 || prec == PREC_BF16X3 || prec == PREC_F16X3 || prec == PREC_F16F8, AWT_ERR_INVALID, "split: unknown precision");
+  AWT_REQUIRE(prec_known(prec), AWT_ERR_INVALID, "split: unknown precision");
   AWT_REQUIRE(prec != PREC_F16F8 || (hi8 && lo8) || ilv, AWT_ERR_INVALID, "split: f16f8 needs both e4m3 planes");
   AWT_REQUIRE(!ilv || (prec == PREC_F16F8 && n % 64 == 0), AWT_ERR_INVALID, "split: split lines are an f16f8 format of whole 64-element line pairs");
   AWT_REQUIRE(f8_exp >= -20 && f8_exp <= 20, AWT_ERR_INVALID, "split: bad e4m3 exponent");
@@ -599,20 +544,3 @@ int launch_outer_reduce(awt_ctx* c, const bf16_t* x_hi, const bf16_t* x_lo, int6
   }
   return AWT_OK;
 }
-
-#ifdef AWT_EXPERIMENTAL_F6
-int launch_split_planes_f6(awt_ctx* c, const float* x, int M, int K, bf16_t* p16, uint8_t* hi6, uint8_t* lo6, hipStream_t s) {
-  AWT_REQUIRE(x && p16 && hi6 && lo6 && M > 0 && K > 0 && K % 64 == 0, AWT_ERR_INVALID, "split_planes_f6: K must be a multiple of 64");
-  const int64_t n = (int64_t)M * (K / 32);
-  hipLaunchKernelGGL(planes_f6_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, M, K, p16, hi6, lo6);
-  AWT_HIP_CHECK(hipGetLastError());
-  return AWT_OK;
-}
-int launch_pack_weight_f6(awt_ctx* c, const float* w, int N, int K, bf16_t* w16, uint8_t* hi6, uint8_t* lo6, hipStream_t s) {
-  AWT_REQUIRE(w && w16 && hi6 && lo6 && N > 0 && N % 32 == 0 && K > 0 && K % 64 == 0, AWT_ERR_INVALID, "pack_weight_f6: N % 32 == 0 and K % 64 == 0 required");
-  const int64_t n = (int64_t)N * (K / 32);
-  hipLaunchKernelGGL(planes_f6_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, N, K, w16, hi6, lo6);
-  AWT_HIP_CHECK(hipGetLastError());
-  return AWT_OK;
-}
-#endif  // AWT_EXPERIMENTAL_F6

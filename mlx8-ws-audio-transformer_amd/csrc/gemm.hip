@@ -34,12 +34,6 @@
 
 namespace {
 
-#ifndef AWT_GEMM_NT_STORE
-#define AWT_GEMM_NT_STORE 1   // f16f8 kernel: operand-plane outputs leave as streaming (non-temporal) stores: whole 256-byte row segments per instruction, read next by
-#endif                        // another kernel; -0.3 ms per step.  (NOT for the 4 / 8-byte stores of attention / LayerNorm: those need L2 write combining, +60 % there.)
-#ifndef AWT_GEMM_WDEC
-#define AWT_GEMM_WDEC 1   // f16f8 kernel: the K-tile barrier waits for the LDS-DMA only; W fragment loads are waited for at their consumers
-#endif
 int g_gm = AWT_GEMM_GM;   // row panels per tile group (awt_tuning_set "gemm_gm")
 constexpr int kMaxSeg = 3;
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
@@ -306,17 +300,12 @@ __device__ __forceinline__ void store_out8_f8(const GemmOut& o, int m, int n, fl
     __builtin_nontemporal_store((i32x2){(int)fp8x4_rt(l[0], l[1], l[2], l[3], liml8, invl8), (int)fp8x4_rt(l[4], l[5], l[6], l[7], liml8, invl8)}, reinterpret_cast<i32x2*>(line + 192 + e));
     return;
   }
-#if AWT_GEMM_NT_STORE   // the planes are read next by another kernel, not by this one -> streaming stores (profiles/r03_gemm_experiments.txt)
+  // the planes are read next by another kernel, not by this one -> streaming stores: whole 256-byte row segments per instruction, -0.3 ms per step
+  // (profiles/r03_gemm_experiments.txt).  NOT for the 4 / 8-byte stores of attention / LayerNorm: those need L2 write combining, +60 % there.
   __builtin_nontemporal_store((i32x4_t){(int)pack2(h[0], h[1]), (int)pack2(h[2], h[3]), (int)pack2(h[4], h[5]), (int)pack2(h[6], h[7])}, reinterpret_cast<i32x4_t*>(o.hi + off));
-  if (EPI == EPI_QKV && o.skip_v8 && n >= 2 * o.H * 64) return;
+  if (EPI == EPI_QKV && o.skip_v8 && n >= 2 * o.H * 64) return;      // v: fp16 plane only
   if (o.hi8) __builtin_nontemporal_store((i32x2){(int)fp8x4_rt(v[0], v[1], v[2], v[3], lim8, inv8), (int)fp8x4_rt(v[4], v[5], v[6], v[7], lim8, inv8)}, reinterpret_cast<i32x2*>(o.hi8 + off));
   __builtin_nontemporal_store((i32x2){(int)fp8x4_rt(l[0], l[1], l[2], l[3], liml8, invl8), (int)fp8x4_rt(l[4], l[5], l[6], l[7], liml8, invl8)}, reinterpret_cast<i32x2*>(o.lo8 + off));
-#else
-  *reinterpret_cast<uint4*>(o.hi + off) = make_uint4(pack2(h[0], h[1]), pack2(h[2], h[3]), pack2(h[4], h[5]), pack2(h[6], h[7]));
-  if (EPI == EPI_QKV && o.skip_v8 && n >= 2 * o.H * 64) return;      // v: fp16 plane only
-  if (o.hi8) *reinterpret_cast<uint2*>(o.hi8 + off) = make_uint2(fp8x4_rt(v[0], v[1], v[2], v[3], lim8, inv8), fp8x4_rt(v[4], v[5], v[6], v[7], lim8, inv8));   // null: see store_act4
-  *reinterpret_cast<uint2*>(o.lo8 + off) = make_uint2(fp8x4_rt(l[0], l[1], l[2], l[3], liml8, invl8), fp8x4_rt(l[4], l[5], l[6], l[7], liml8, invl8));
-#endif
 }
 
 template <int TERMS, int BK, int EPI, class CFG, bool F16, bool WX = false, bool BATCH = false>
@@ -557,11 +546,10 @@ struct F8IssueOrder {
   template <bool PF> static constexpr int w16_wait(int ks) { return younger(last_w16(ks), PF ? issued_at_step(ks) : 0); }
   // e4m3 W planes, the previous K-tile's last operations
   template <bool PF> static constexpr int w8_wait() { return younger(last_w8, PF ? issued_at_f8 : 0); }
-  // at the K-tile barrier, after this K-tile's last operation was issued: only its DMA pieces must have landed (AWT_GEMM_WDEC) / also its fp16 fragments
+  // at the K-tile barrier, after this K-tile's last operation was issued: only its DMA pieces must have landed (its W fragments are waited for where they are consumed)
   static constexpr int dma_wait_at_barrier() { return N - 1 - last_dma; }
-  static constexpr int w16_wait_at_barrier() { return N - 1 - last_w16(KS - 1); }
   static_assert(w16_wait<true>(0) == (KS - 1) * TN + NW8 + DMA_PER_STEP && w16_wait<true>(KS - 1) == (KS - 1) * TN + NW8 + NDMA && w16_wait<false>(1) == (KS - 2) * TN + NW8, "w16 waits");
-  static_assert(w8_wait<true>() == NDMA + NW16 && w8_wait<false>() == 0 && dma_wait_at_barrier() == NW16 + NW8 && w16_wait_at_barrier() == NW8, "w8 / barrier waits");
+  static_assert(w8_wait<true>() == NDMA + NW16 && w8_wait<false>() == 0 && dma_wait_at_barrier() == NW16 + NW8, "w8 / barrier waits");
   static_assert(w16_wait<true>(KS - 1) <= 63, "vmcnt is a 6-bit count");
 };
 
@@ -765,12 +753,10 @@ __global__ __launch_bounds__(CFG::WM * CFG::WN * 64, CFG::WM * CFG::WN == 4 ? 2 
         // LDS operations younger than this step's fragment: the (up to) three fragments read ahead, plus the first e4m3 reads
         constexpr int AHEAD = (4 * TM - 1 - S < AD ? 4 * TM - 1 - S : AD) + (EARLY8 && !WX && S >= 4 * TM - 2 ? 2 : 0) + (EARLY8 && S >= 4 * TM - 1 ? 2 : 0);
         lgkm_wait<AHEAD>(af[S % (AD + 1)]);
-#if AWT_GEMM_WDEC
         // the fp16 W fragments of k-step ks were loaded a whole K-tile ago (ring); vmcnt retires in issue order, so the wait counts what was
         // issued since: the later k-steps' fragments of this K-tile (3 - ks) TN, its e4m3 planes NW8, and -- when prefetching -- the DMA
         // pieces (all of them from k-step 1 on, this step's share in k-step 0) and the ks TN fragments already reloaded for K-tile kt + 1
         if constexpr (i == 0) wait_vm<ORD::template w16_wait<PF>(ks)>(w16[ks][0], w16[ks][1]);
-#endif
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = mfma32<true>(af[S % (AD + 1)], w16[ks][j], acc[i][j]);
@@ -816,14 +802,9 @@ __global__ __launch_bounds__(CFG::WM * CFG::WN * 64, CFG::WM * CFG::WN == 4 ? 2 
     }(std::make_integer_sequence<int, TM>{});
     if constexpr (PF) {
       load_w8();
-#if AWT_GEMM_WDEC
       // only the DMA pieces of K-tile kt + 1 must have landed before the barrier; its W fragments (NW16 + NW8 younger loads) stay in flight
       // across it and are waited for where they are consumed, a K-tile after their issue
       wait_vm<ORD::dma_wait_at_barrier()>();
-#else
-      // the DMA pieces and the fp16 W fragments of K-tile kt + 1 are older than the NW8 e4m3 loads just issued
-      wait_vm<ORD::w16_wait_at_barrier()>();
-#endif
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -1073,9 +1054,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f8s_kernel(GemmArgs g) {
         }
         constexpr int AHEAD = (KS * TM - 1 - S < AD ? KS * TM - 1 - S : AD) + (EARLY8 && S >= KS * TM - 1 ? 2 : 0);
         lgkm_wait<AHEAD>(af[S % (AD + 1)]);
-#if AWT_GEMM_WDEC
         if constexpr (i == 0) wait_vm<ORD::template w16_wait<PF>(ks)>(w16[ks][0], w16[ks][1], w16[ks][2], w16[ks][3]);
-#endif
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = mfma16<true>(af[S % (AD + 1)], w16[ks][j], acc[i][j]);
@@ -1101,11 +1080,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f8s_kernel(GemmArgs g) {
     }(std::make_integer_sequence<int, TM>{});
     if constexpr (PF) {
       load_w8();
-#if AWT_GEMM_WDEC
       wait_vm<ORD::dma_wait_at_barrier()>();
-#else
-      wait_vm<ORD::w16_wait_at_barrier()>();
-#endif
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -1168,41 +1143,31 @@ __global__ __launch_bounds__(256, 2) void gemm_f8s_kernel(GemmArgs g) {
   if (m0 + BM <= g.M && n0 + BN <= g.out.n_valid) strips(std::true_type{}); else strips(std::false_type{});
 }
 
+// Every launch of a GemmArgs kernel: the tile counts of its bm x bn block tiling and the tile order, one workgroup per tile (and per matrix of a
+// batched launch: blockIdx.y), then launch_kernel (common.h).  N % bn != 0: the last column tile is partly empty (its stores are masked by n_valid).
+template <auto Kernel>
+int launch_tiles(GemmArgs a, int bm, int bn, int threads, int lds, hipStream_t s, int group_n = 0, int batch = 1) {
+  a.tiles_m = (a.M + bm - 1) / bm;
+  a.tiles_n = (a.N + bn - 1) / bn;
+  a.group_n = group_n; a.gm = g_gm;
+  return launch_kernel<Kernel>(dim3(a.tiles_m * a.tiles_n, batch), dim3(threads), lds, s, a);
+}
+
 int g_mfma16 = 1;   // tuning knob "gemm_mfma16": 1 = the 16 x 16 form wherever its weight copies exist (default), 0 = the 32 x 32 kernels only
+// 128 x 256 tiles; with N % 256 != 0 the last column tile's weight rows exist (zero or unread garbage) and are multiplied, its stores are masked
 template <int EPI>
 int launch_f8s(GemmArgs a, hipStream_t s) {
-  constexpr int lds = 2 * (128 * 64 * 2 + 2 * 128 * 64);
-  a.tiles_m = (a.M + 127) / 128;
-  a.tiles_n = (a.N + 255) / 256;      // N % 256 != 0: the last column tile is partly empty (its weight rows exist, zero or unread garbage; its stores are masked by n_valid)
-  a.group_n = 0; a.gm = g_gm;
-  AWT_ONCE_PER_DEVICE(AWT_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_f8s_kernel<EPI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-  hipLaunchKernelGGL((gemm_f8s_kernel<EPI, false>), dim3(a.tiles_m * a.tiles_n), dim3(256), lds, s, a);
-  AWT_HIP_CHECK(hipGetLastError());
-  return AWT_OK;
+  return launch_tiles<gemm_f8s_kernel<EPI, false>>(a, 128, 256, 256, 2 * (128 * 64 * 2 + 2 * 128 * 64), s);
 }
 
 template <int EPI, class CFG>
 int launch_f8(GemmArgs a, hipStream_t s) {
-  constexpr int BM = CFG::WM * CFG::TM * 32, BN = CFG::WN * CFG::TN * 32;
+  constexpr int BM = CFG::WM * CFG::TM * 32, BN = CFG::WN * CFG::TN * 32, NT = CFG::WM * CFG::WN * 64;
   constexpr int lds = 2 * (BM * 64 * 2 + 2 * BM * 64);     // two stages of A16 | A8 | Al8 = 64 KB (>= the epilogue patches)
-  a.tiles_m = (a.M + BM - 1) / BM;
-  a.tiles_n = (a.N + BN - 1) / BN;
-  a.group_n = 0; a.gm = g_gm;
-  if (a.nseg == 1 && a.seg[0].w_exact16) {
-    AWT_ONCE_PER_DEVICE(AWT_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_f8_kernel<EPI, CFG, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-    hipLaunchKernelGGL((gemm_f8_kernel<EPI, CFG, false, true>), dim3(a.tiles_m * a.tiles_n), dim3(CFG::WM * CFG::WN * 64), lds, s, a);
-  } else if (a.nseg == 1) {
-    AWT_ONCE_PER_DEVICE(AWT_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_f8_kernel<EPI, CFG, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-    hipLaunchKernelGGL((gemm_f8_kernel<EPI, CFG, false>), dim3(a.tiles_m * a.tiles_n), dim3(CFG::WM * CFG::WN * 64), lds, s, a);
-  } else {
-    AWT_ONCE_PER_DEVICE(AWT_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_f8_kernel<EPI, CFG, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-    hipLaunchKernelGGL((gemm_f8_kernel<EPI, CFG, true>), dim3(a.tiles_m * a.tiles_n), dim3(CFG::WM * CFG::WN * 64), lds, s, a);
-  }
-  AWT_HIP_CHECK(hipGetLastError());
-  return AWT_OK;
+  if (a.nseg == 1 && a.seg[0].w_exact16) return launch_tiles<gemm_f8_kernel<EPI, CFG, false, true>>(a, BM, BN, NT, lds, s);
+  if (a.nseg == 1) return launch_tiles<gemm_f8_kernel<EPI, CFG, false>>(a, BM, BN, NT, lds, s);
+  return launch_tiles<gemm_f8_kernel<EPI, CFG, true>>(a, BM, BN, NT, lds, s);
 }
-
-
 
 // ================================================================================================ persistent ping-pong kernel (gemm_pp.h)
 // 256 x 256 tiles, 8 waves, one workgroup per CU walking its tiles with one continuous K-tile stream; PREC_F16F8, one plain K segment.
@@ -1271,257 +1236,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(pp::Args g, GemmOut out
 
 template <int EPI, bool ILV>
 int launch_pp(const pp::Args& a, const GemmOut& o, int grid, hipStream_t s) {
-  AWT_ONCE_PER_DEVICE(AWT_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_pp_kernel<EPI, ILV>, hipFuncAttributeMaxDynamicSharedMemorySize, pp::LDS_BYTES)));
-  hipLaunchKernelGGL((gemm_pp_kernel<EPI, ILV>), dim3(grid), dim3(pp::NT), pp::LDS_BYTES, s, a, o);
-  AWT_HIP_CHECK(hipGetLastError());
-  return AWT_OK;
+  return launch_kernel<gemm_pp_kernel<EPI, ILV>>(dim3(grid), dim3(pp::NT), pp::LDS_BYTES, s, a, o);
 }
-
-#ifdef AWT_EXPERIMENTAL_F6   // round-2 experiment: not compiled into the shipped library
-// ================================================================================================ PREC_F16F6 (experimental)
-// The f16f8 kernel with the two correction planes in FP6 e3m2: per fragment pair the fp16 product (4 x 32 pipe cycles per 64-deep K-tile and
-// 32 x 32 tile) plus two block-scaled FP6 products of 32 cycles each = 1.5 bf16-MFMA-equivalents instead of 2, and 3.5 instead of 4 operand
-// bytes per element.  128 x 256 on four waves, single K segment, fp32 output (the single-operator path `awt_op_linear`, precision 6); the encoder
-// does not use it yet: its producers (LayerNorm, GELU epilogue, attention output) would have to emit 32-consecutive-k groups.
-// LDS stage: A16 (16 KB) | A_hi6 (6 KB: 128 rows x 48 B) | A_lo6 (6 KB).  A lane (row r, half h) reads its 24 bytes as three ds_read_b64.
-template <int OFF>
-__device__ __forceinline__ i32x2 lds_read8a(unsigned addr) {
-  i32x2 v;
-  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-  return v;
-}
-template <int OFF>
-__device__ __forceinline__ i32x2 gload8(unsigned voff, const void* sbase) {
-  i32x2 v;
-  asm volatile("global_load_dwordx2 %0, %1, %2 offset:%3" : "=v"(v) : "v"(voff), "s"(sbase), "n"(OFF));
-  return v;
-}
-template <int EPI>
-__global__ __launch_bounds__(256, 2) void gemm_f6_kernel(GemmArgs g) {
-  constexpr int TM = 4, TN = 2, BM = 128, BN = 256, BK = 64, NT = 256;
-  constexpr int PL16 = BM * BK * 2, PL6 = BM * 48, STAGE = PL16 + 2 * PL6;     // 16 + 6 + 6 KB
-  constexpr int IT16 = PL16 / 16 / NT, IT6 = 2 * PL6 / 16 / NT;                 // 4 + 3 LDS-DMA pieces per thread
-  constexpr int NDMA = IT16 + IT6;
-  constexpr int NW16 = 4 * TN, NW6 = 2 * TN * 2;                                // W loads per lane per K-tile: fp16, e3m2 (2 planes x TN x (16 B + 8 B))
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int tid = wave * 64 + lane;
-  const int nwg = g.tiles_m * g.tiles_n;
-  const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  const int qn = nwg >> 3, rn = nwg & 7;
-  const int tile = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx;
-  const int GM = g.gm;
-  int tm, tn;
-  {
-    const int grp = tile / (GM * g.tiles_n);
-    const int gm = min(GM, g.tiles_m - grp * GM);
-    const int within = tile - grp * GM * g.tiles_n;
-    tn = within / gm; tm = grp * GM + (within - tn * gm);
-  }
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int wc = wave;                       // 1 x 4 waves: wave w owns columns 64 w .. 64 w + 63 of the tile
-  const int r32 = lane & 31, half = lane >> 5;
-  const GemmSeg& sg = g.seg[0];
-  const int ktiles = sg.K / BK;
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = (f32x16){};
-
-  // ---- A streams: per-thread byte offsets of the DMA pieces (fixed), bases advanced per K-tile
-  unsigned a16o[IT16], a6o[IT6];
-#pragma unroll
-  for (int it = 0; it < IT16; ++it) {
-    const int p = it * NT + tid, row = p >> 3, c = (p & 7) ^ ((row >> 1) & 7);
-    int m = m0 + row; m = m < g.M ? m : g.M - 1;
-    a16o[it] = (unsigned)(((int64_t)m * sg.lda + c * 8) * 2);
-  }
-  const int64_t pitch6 = sg.lda / 4 * 3;                          // bytes per row of an e3m2 plane
-  const int64_t plane6 = (const char*)sg.al8 - (const char*)sg.a8;   // the lo6 plane follows the hi6 plane (checked on the host: < 4 GB)
-#pragma unroll
-  for (int it = 0; it < IT6; ++it) {
-    const int q = it * NT + tid, pl = q >= 384, within = q - pl * 384, row = within / 3, c = within - row * 3;
-    int m = m0 + row; m = m < g.M ? m : g.M - 1;
-    a6o[it] = (unsigned)(pl * plane6 + (int64_t)m * pitch6 + c * 16);
-  }
-  const char* a16b = (const char*)sg.a_hi;
-  const char* a6b = (const char*)sg.a8;
-  const int nt0 = (n0 >> 5) + wc * TN;
-  const int64_t w16_ts = (int64_t)sg.w_ksteps * 2 * 1024;           // bytes per 32-row n-tile of the fp16 plane
-  const int64_t w6_ts = (int64_t)(sg.w_ksteps / 2) * 1536;           // bytes per n-tile of an e3m2 plane: (K / 64) blocks of 64 x 24 B
-  const char *w16b[TN], *w6b[TN], *wl6b[TN];
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    w16b[j] = (const char*)sg.w_hi + (nt0 + j) * w16_ts;
-    w6b[j] = (const char*)sg.w8 + (nt0 + j) * w6_ts;
-    wl6b[j] = (const char*)sg.wl8 + (nt0 + j) * w6_ts;
-  }
-  const unsigned wl16 = lane * 16, wl24 = lane * 24;
-  int kk = 0;
-  auto advance = [&]() {
-    if (kk + 1 < ktiles) {
-      ++kk;
-      a16b += BK * 2; a6b += 48;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) { w16b[j] += 4 * 1024; w6b[j] += 1536; wl6b[j] += 1536; }
-    }
-  };
-  auto dma = [&](auto op_t, char* stage) {
-    constexpr int OP = decltype(op_t)::value;
-    if constexpr (OP < IT16) glds16(a16b + a16o[OP], stage + (OP * NT + wave * 64) * 16);
-    else glds16(a6b + a6o[OP - IT16], stage + PL16 + ((OP - IT16) * NT + wave * 64) * 16);
-  };
-  bf16x8 w16[4][TN];
-  bf16x8 w6a[TN], wl6a[TN];          // first 16 bytes of the lane's 24
-  i32x2 w6c[TN], wl6c[TN];           // last 8
-  auto load_w16 = [&](auto ks_t) {
-    constexpr int ks = decltype(ks_t)::value;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) w16[ks][j] = gload16<ks * 1024>(wl16, w16b[j]);
-  };
-  auto load_w6 = [&]() {
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      w6a[j] = gload16<0>(wl24, w6b[j]); w6c[j] = gload8<16>(wl24, w6b[j]);
-      wl6a[j] = gload16<0>(wl24, wl6b[j]); wl6c[j] = gload8<16>(wl24, wl6b[j]);
-    }
-  };
-  auto cat6 = [](bf16x8 lo, i32x2 hi) -> i32x8 {
-    const i32x4_t l = __builtin_bit_cast(i32x4_t, lo);
-    return (i32x8){l[0], l[1], l[2], l[3], hi[0], hi[1], 0, 0};
-  };
-
-  [&]<int... O>(std::integer_sequence<int, O...>) { (dma(std::integral_constant<int, O>{}, smem), ...); }(std::make_integer_sequence<int, NDMA>{});
-  [&]<int... S>(std::integer_sequence<int, S...>) { (load_w16(std::integral_constant<int, S>{}), ...); }(std::make_integer_sequence<int, 4>{});
-  load_w6();
-  wait_vm<0>();
-  __builtin_amdgcn_s_barrier();
-
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)(smem);
-  unsigned a16a[4];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) a16a[ks] = lds0 + r32 * 128 + (((2 * ks + half) ^ ((r32 >> 1) & 7)) << 4);
-  unsigned a6a = lds0 + PL16 + r32 * 48 + 24 * half;
-
-  constexpr int DMA_PER_STEP = (NDMA + TM - 1) / TM;
-  auto ktile = [&](auto pf_t, int kt) {
-    constexpr bool PF = decltype(pf_t)::value;
-    char* nxt = smem + ((kt + 1) & 1) * STAGE;
-    if constexpr (PF) advance();
-    constexpr int AD = 3;
-    bf16x8 af[AD + 1];
-    auto read_a16 = [&](auto s_t) {
-      constexpr int S2 = decltype(s_t)::value;
-      af[S2 % (AD + 1)] = lds_read16<(S2 % TM) * 32 * 128>(a16a[S2 / TM]);
-    };
-    [&]<int... S>(std::integer_sequence<int, S...>) { (read_a16(std::integral_constant<int, S>{}), ...); }(std::make_integer_sequence<int, AD>{});
-    [&]<int... S>(std::integer_sequence<int, S...>) {
-      ([&] {
-        constexpr int ks = S / TM, i = S % TM;
-        if constexpr (S + AD < 4 * TM) read_a16(std::integral_constant<int, S + AD>{});
-        if constexpr (PF && ks == 0) {
-          [&]<int... O>(std::integer_sequence<int, O...>) {
-            ([&] { constexpr int op = i * DMA_PER_STEP + O; if constexpr (op < NDMA) dma(std::integral_constant<int, op>{}, nxt); }(), ...);
-          }(std::make_integer_sequence<int, DMA_PER_STEP>{});
-        }
-        constexpr int AHEAD = (4 * TM - 1 - S < AD ? 4 * TM - 1 - S : AD);
-        lgkm_wait<AHEAD>(af[S % (AD + 1)]);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = mfma32<true>(af[S % (AD + 1)], w16[ks][j], acc[i][j]);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (PF && i == TM - 1) load_w16(std::integral_constant<int, ks>{});
-      }(), ...);
-    }(std::make_integer_sequence<int, 4 * TM>{});
-    // ---- e3m2 part: the six 8-byte reads of row tile i + 1 are issued before the four MFMAs of row tile i (two register sets), waits hand-counted
-    if constexpr (PF) wait_vm<NDMA + NW16>(); else wait_vm<0>();
-    i32x2 xy[2][6];
-    auto read_xy = [&](auto i_t, i32x2 (&d)[6]) {
-      constexpr int O = decltype(i_t)::value * 32 * 48;
-      d[0] = lds_read8a<O>(a6a); d[1] = lds_read8a<O + 8>(a6a); d[2] = lds_read8a<O + 16>(a6a);
-      d[3] = lds_read8a<O + PL6>(a6a); d[4] = lds_read8a<O + PL6 + 8>(a6a); d[5] = lds_read8a<O + PL6 + 16>(a6a);
-    };
-    read_xy(std::integral_constant<int, 0>{}, xy[0]);
-    [&]<int... I>(std::integer_sequence<int, I...>) {
-      ([&] {
-        i32x2 (&cur)[6] = xy[I & 1];
-        if constexpr (I + 1 < TM) read_xy(std::integral_constant<int, I + 1>{}, xy[(I + 1) & 1]);
-        asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(cur[0]), "+v"(cur[1]), "+v"(cur[2]), "+v"(cur[3]), "+v"(cur[4]), "+v"(cur[5]) : "n"(I + 1 < TM ? 6 : 0));
-        __builtin_amdgcn_sched_barrier(0);
-        const i32x8 ax = {cur[0][0], cur[0][1], cur[1][0], cur[1][1], cur[2][0], cur[2][1], 0, 0};
-        const i32x8 ay = {cur[3][0], cur[3][1], cur[4][0], cur[4][1], cur[5][0], cur[5][1], 0, 0};
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[I][j] = mfma32_f6<e8m0(-kF6Act), e8m0(-kF6Wgt - kF8Lo)>(ax, cat6(wl6a[j], wl6c[j]), acc[I][j]);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[I][j] = mfma32_f6<e8m0(-kF6Act - kF8Lo), e8m0(-kF6Wgt)>(ay, cat6(w6a[j], w6c[j]), acc[I][j]);
-        __builtin_amdgcn_sched_barrier(0);
-      }(), ...);
-    }(std::make_integer_sequence<int, TM>{});
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (PF) {
-      load_w6();
-      wait_vm<NW6>();
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if constexpr (PF) {
-      const int flip = (kt & 1) ? -STAGE : STAGE;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) a16a[ks] += flip;
-      a6a += flip;
-    }
-  };
-  for (int kt = 0; kt + 1 < ktiles; ++kt) ktile(std::true_type{}, kt);
-  ktile(std::false_type{}, ktiles - 1);
-
-  // ---- epilogue: as gemm_f8_kernel (predicated form)
-  constexpr int PITCH = 72;
-  float* patch = reinterpret_cast<float*>(smem) + wave * (32 * PITCH);
-  const int c8 = (lane & 7) * 8, r8 = lane >> 3;
-  const int em0 = m0, en = n0 + wc * 64 + c8;
-  float4 b0 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = b0;
-  if (g.out.bias && en < g.out.n_valid) { b0 = *reinterpret_cast<const float4*>(g.out.bias + en); b1 = *reinterpret_cast<const float4*>(g.out.bias + en + 4); }
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int rr = 0; rr < 16; ++rr) patch[((rr & 3) + 8 * (rr >> 2) + 4 * half) * PITCH + j * 32 + r32] = acc[i][j][rr];
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    float4 side[4][2];
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      side[it][0] = load_side4<EPI>(g.out, em0 + i * 32 + r8 + 8 * it, en, g.M);
-      side[it][1] = load_side4<EPI>(g.out, em0 + i * 32 + r8 + 8 * it, en + 4, g.M);
-    }
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int rl = r8 + 8 * it;
-      const float4 v0 = *reinterpret_cast<const float4*>(patch + rl * PITCH + c8), v1 = *reinterpret_cast<const float4*>(patch + rl * PITCH + c8 + 4);
-      store_out8_f8<EPI, false>(g.out, em0 + i * 32 + rl, en, v0, v1, side[it][0], side[it][1], b0, b1, g.M);
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  }
-}
-
-template <int EPI>
-int launch_f6(GemmArgs a, hipStream_t s) {
-  constexpr int lds = 2 * (128 * 64 * 2 + 2 * 128 * 48);     // 56 KB (>= the 36 KB of epilogue patches)
-  a.tiles_m = (a.M + 127) / 128;
-  a.tiles_n = a.N / 256;
-  a.group_n = 0; a.gm = g_gm;
-  AWT_ONCE_PER_DEVICE(AWT_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_f6_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)));
-  hipLaunchKernelGGL((gemm_f6_kernel<EPI>), dim3(a.tiles_m * a.tiles_n), dim3(256), lds, s, a);
-  AWT_HIP_CHECK(hipGetLastError());
-  return AWT_OK;
-}
-
-#endif  // AWT_EXPERIMENTAL_F6
 
 int g_force_tile = 0;  // 0 = auto, 64 / 128 / 256 = forced (tuning and tests)
 // Tile order (see the kernel).  Measured on the encoder's shapes (tools/gemm_traffic_shapes.sh, profiles/r01_gemm_tile_order.txt):
@@ -1529,76 +1245,52 @@ int g_force_tile = 0;  // 0 = auto, 64 / 128 / 256 = forced (tuning and tests)
 // panels, so row-panel groups are the default; AWT_GEMM_GROUP_N=n selects column groups for experiments.
 int g_group_n = 0;
 
+template <int TERMS, int BK, int EPI, class CFG, bool F16 = false, bool WX = false>
+int launch_one(GemmArgs a, hipStream_t s) {
+  using T = Tile<TERMS, BK, CFG, WX>;
+  return launch_tiles<gemm_kernel<TERMS, BK, EPI, CFG, F16, WX>>(a, T::BM, T::BN, T::THREADS, T::LDS_BYTES, s, g_group_n);
+}
 // batched launch (launch_gemm_batched): `batch` independent matrices of one shape, blockIdx.y = matrix
 template <int TERMS, int BK, int EPI, class CFG>
 int launch_batched_one(GemmArgs a, int batch, hipStream_t s) {
   using T = Tile<TERMS, BK, CFG, false>;
-  AWT_ONCE_PER_DEVICE(AWT_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_kernel<TERMS, BK, EPI, CFG, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES)));
-  a.tiles_m = (a.M + T::BM - 1) / T::BM;
-  a.tiles_n = (a.N + T::BN - 1) / T::BN;
-  a.group_n = 0; a.gm = g_gm;
-  hipLaunchKernelGGL((gemm_kernel<TERMS, BK, EPI, CFG, false, false, true>), dim3(a.tiles_m * a.tiles_n, batch), dim3(T::THREADS), T::LDS_BYTES, s, a);
-  AWT_HIP_CHECK(hipGetLastError());
-  return AWT_OK;
+  return launch_tiles<gemm_kernel<TERMS, BK, EPI, CFG, false, false, true>>(a, T::BM, T::BN, T::THREADS, T::LDS_BYTES, s, 0, batch);
 }
-
-template <int TERMS, int BK, int EPI, class CFG, bool F16 = false, bool WX = false>
-int launch_one(GemmArgs a, hipStream_t s) {
-  using T = Tile<TERMS, BK, CFG, WX>;
-  AWT_ONCE_PER_DEVICE(AWT_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_kernel<TERMS, BK, EPI, CFG, F16, WX>, hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES)));
-  a.tiles_m = (a.M + T::BM - 1) / T::BM;
-  a.tiles_n = (a.N + T::BN - 1) / T::BN;
-  a.group_n = g_group_n; a.gm = g_gm;
-  hipLaunchKernelGGL((gemm_kernel<TERMS, BK, EPI, CFG, F16, WX>), dim3(a.tiles_m * a.tiles_n), dim3(T::THREADS), T::LDS_BYTES, s, a);
-  AWT_HIP_CHECK(hipGetLastError());
-  return AWT_OK;
-}
-
 
 // Tile choice by tile count: a launch should put at least one tile on each of the 512 workgroup slots (256 CUs x 2) --
 // with fewer, its duration is one tile's K loop however small M is, so smaller tiles (shorter K-tile steps) win.
 //   128 x 256 (4 waves of 128 x 64): the encoder's shapes from ~3 clips up;  128 x 128: N not a multiple of 256 (LoRA
 //   projections, N = 384 models) and mid-sized M;  64 x 128: one or two clips (M = 1500 .. 3000) and tiny test shapes.
 constexpr int kSlots = 512;
+// the bf16 / fp16 kernels' tile: 256 when the 128 x 256 tiles (of `batch` matrices) fill the slots, else 128 when the 128 x 128 tiles do, else 64.
+// A forced tile (g_force_tile) is taken as given, except that 256 falls back to 128 when N % 256 != 0.
+int pick_tile(int M, int N, int batch = 1) {
+  const int64_t panels = (int64_t)((M + 127) / 128) * batch;
+  int tile = g_force_tile;
+  if (!tile) tile = (N % 256 == 0 && panels * (N / 256) >= kSlots) ? 256 : (panels * (N / 128) >= kSlots ? 128 : 64);
+  return (tile == 256 && N % 256 != 0) ? 128 : tile;
+}
+
 template <int EPI>
 int launch_epi(GemmArgs a, int prec, hipStream_t s) {
-  if (prec == PREC_F16F6) {
-#ifndef AWT_EXPERIMENTAL_F6
-    return awt_fail(AWT_ERR_INVALID, "gemm (f16f6): the FP6 cross-term experiment is not part of this build (compile with -DAWT_EXPERIMENTAL_F6)");
-#else
-    if constexpr (EPI == EPI_F32 || EPI == EPI_F32_RESID) {
-      if (a.nseg != 1 || a.N % 256 != 0 || a.seg[0].rows_out != a.M || a.seg[0].rows_in != a.M || a.seg[0].row_mul != 1 || a.seg[0].row_add != 0)
-        return awt_fail(AWT_ERR_INVALID, "gemm (f16f6): one plain K segment and N % 256 == 0 only");
-      const int64_t gap = (const char*)a.seg[0].al8 - (const char*)a.seg[0].a8;
-      if (gap <= 0 || gap >= (1ll << 31)) return awt_fail(AWT_ERR_INVALID, "gemm (f16f6): the lo6 plane must follow the hi6 plane within 2 GB");
-      return launch_f6<EPI>(a, s);
-    } else return awt_fail(AWT_ERR_INVALID, "gemm (f16f6): fp32 outputs only (experimental single-operator path)");
-#endif
-  }
   if (prec == PREC_F16F8) {
-    {
-      // the 16 x 16 MFMA form: one segment that carries its 16-row weight copies and takes no fp16-exact shortcut (multi-segment K loops keep the 32 x 32
-      // kernel: their per-segment address state does not fit beside the 16 x 16 form's fragment rings).  It also takes N % 256 != 0 (Whisper-tiny: 384, 1152)
-      // when the copies are allocated for whole column tiles and at most a quarter of the last tile's work is padding: measured on M = 48000 (tools/tiny_shapes_probe.py)
-      // 136 -> 126 us at N = 1152, 186 -> 170 us at N = 384 / K = 1536 against the 128 x 128 tiles these shapes fell to
-      const int n256 = (a.N + 255) / 256 * 256;
-      const bool f8s_ok = g_mfma16 && a.nseg == 1 && a.seg[0].ws16 && a.seg[0].ws8 && a.seg[0].a8 && !a.seg[0].w_exact16 &&
-                          (a.N % 256 == 0 || (a.seg[0].ws_rows >= n256 && (int64_t)n256 * 3 <= (int64_t)a.N * 4));
-      const int64_t t256f = (int64_t)((a.M + 127) / 128) * (f8s_ok ? n256 / 256 : a.N / 256);
-      int tile = g_force_tile;
-      if (!tile) tile = ((a.N % 256 == 0 || f8s_ok) && t256f >= kSlots) ? 256 : 128;
-      if (tile == 512 && a.N % 256 == 0 && a.nseg == 1) return launch_f8<EPI, CfgF8Big>(a, s);
-      if (tile == 256 && f8s_ok) return launch_f8s<EPI>(a, s);
-      if (tile >= 256 && a.N % 256 == 0) return launch_f8<EPI, CfgF8W4>(a, s);
-      return launch_f8<EPI, CfgF8Sq>(a, s);
-    }
-  }
-  const int terms = prec_products(prec);
-  if (prec == PREC_F16X3) {      // fp16 hi / lo planes on the same kernels
-    const int64_t t256h = (int64_t)((a.M + 127) / 128) * (a.N / 256), t128h = (int64_t)((a.M + 127) / 128) * (a.N / 128);
+    // the 16 x 16 MFMA form: one segment that carries its 16-row weight copies and takes no fp16-exact shortcut (multi-segment K loops keep the 32 x 32
+    // kernel: their per-segment address state does not fit beside the 16 x 16 form's fragment rings).  It also takes N % 256 != 0 (Whisper-tiny: 384, 1152)
+    // when the copies are allocated for whole column tiles and at most a quarter of the last tile's work is padding: measured on M = 48000 (tools/tiny_shapes_probe.py)
+    // 136 -> 126 us at N = 1152, 186 -> 170 us at N = 384 / K = 1536 against the 128 x 128 tiles these shapes fell to
+    const int n256 = (a.N + 255) / 256 * 256;
+    const bool f8s_ok = g_mfma16 && a.nseg == 1 && a.seg[0].ws16 && a.seg[0].ws8 && a.seg[0].a8 && !a.seg[0].w_exact16 &&
+                        (a.N % 256 == 0 || (a.seg[0].ws_rows >= n256 && (int64_t)n256 * 3 <= (int64_t)a.N * 4));
+    const int64_t t256f = (int64_t)((a.M + 127) / 128) * (f8s_ok ? n256 / 256 : a.N / 256);
     int tile = g_force_tile;
-    if (!tile) tile = (a.N % 256 == 0 && t256h >= kSlots) ? 256 : (t128h >= kSlots ? 128 : 64);
-    if (tile == 256 && a.N % 256 != 0) tile = 128;
+    if (!tile) tile = ((a.N % 256 == 0 || f8s_ok) && t256f >= kSlots) ? 256 : 128;
+    if (tile == 512 && a.N % 256 == 0 && a.nseg == 1) return launch_f8<EPI, CfgF8Big>(a, s);
+    if (tile == 256 && f8s_ok) return launch_f8s<EPI>(a, s);
+    if (tile >= 256 && a.N % 256 == 0) return launch_f8<EPI, CfgF8W4>(a, s);
+    return launch_f8<EPI, CfgF8Sq>(a, s);
+  }
+  const int tile = pick_tile(a.M, a.N);
+  if (prec == PREC_F16X3) {      // fp16 hi / lo planes on the same kernels
     if (a.nseg == 1 && a.seg[0].w_exact16) {     // fp16-exact weights: two products per fragment pair
       if (tile == 256) return launch_one<3, 32, EPI, CfgW4, true, true>(a, s);
       if (tile == 128) return launch_one<3, 32, EPI, Cfg128, true, true>(a, s);
@@ -1608,15 +1300,12 @@ int launch_epi(GemmArgs a, int prec, hipStream_t s) {
     if (tile == 128) return launch_one<3, 32, EPI, Cfg128, true>(a, s);
     return launch_one<3, 64, EPI, Cfg64, true>(a, s);
   }
-  const int64_t t256 = (int64_t)((a.M + 127) / 128) * (a.N / 256), t128 = (int64_t)((a.M + 127) / 128) * (a.N / 128);
-  int tile = g_force_tile;
-  if (!tile) tile = (a.N % 256 == 0 && t256 >= kSlots) ? 256 : (t128 >= kSlots ? 128 : 64);
-  if (tile == 256 && a.N % 256 != 0) tile = 128;
   if (prec == PREC_F16) {        // one fp16 product (measurement mode): the single-product kernels on fp16 planes
     if (tile == 256) return launch_one<1, 64, EPI, CfgW4, true>(a, s);
     if (tile == 128) return launch_one<1, 64, EPI, Cfg128, true>(a, s);
     return launch_one<1, 64, EPI, Cfg64, true>(a, s);
   }
+  const int terms = prec_products(prec);
   if (tile == 256) return terms == 3 ? launch_one<3, 32, EPI, CfgW4>(a, s) : launch_one<1, 64, EPI, CfgW4>(a, s);
   if (tile == 128) return terms == 3 ? launch_one<3, 32, EPI, Cfg128>(a, s) : launch_one<1, 64, EPI, Cfg128>(a, s);
   // few tiles per CU: the K loop is latency-bound (one barrier + one global round trip per K-tile), so the deeper 64-wide
@@ -1627,12 +1316,9 @@ int launch_epi(GemmArgs a, int prec, hipStream_t s) {
 
 template <int EPI>
 int launch_batched_epi(GemmArgs a, int batch, hipStream_t s) {
-  // tile by the rows a matrix wastes: 64-row tiles when the last 128-row tile would be at most half full or the launch is small
-  const int64_t t256 = (int64_t)((a.M + 127) / 128) * (a.N / 256) * batch, t128 = (int64_t)((a.M + 127) / 128) * (a.N / 128) * batch;
+  // tile by the rows a matrix wastes: 64-row tiles when the last 128-row tile would be at most half full, else by tile count
   const int tail = a.M % 128;
-  int tile = g_force_tile;
-  if (!tile) tile = (tail > 0 && tail <= 64 && a.M < 1024) ? 64 : (a.N % 256 == 0 && t256 >= kSlots) ? 256 : (t128 >= kSlots ? 128 : 64);
-  if (tile == 256 && a.N % 256 != 0) tile = 128;
+  const int tile = (!g_force_tile && tail > 0 && tail <= 64 && a.M < 1024) ? 64 : pick_tile(a.M, a.N, batch);
   if (tile == 256) return launch_batched_one<3, 32, EPI, CfgW4>(a, batch, s);
   if (tile == 128) return launch_batched_one<3, 32, EPI, Cfg128>(a, batch, s);
   return launch_batched_one<3, 64, EPI, Cfg64>(a, batch, s);
@@ -1710,7 +1396,7 @@ int launch_gemm(awt_ctx* c, int M, int N, const GemmSeg* segs, int nseg, int pre
                 hipStream_t s) {
   AWT_REQUIRE(M > 0 && N > 0 && N % 128 == 0, AWT_ERR_INVALID, "gemm: N must be a positive multiple of 128");
   AWT_REQUIRE(nseg >= 1 && nseg <= kMaxSeg, AWT_ERR_INVALID, "gemm: 1..3 K-segments");
-  AWT_REQUIRE(prec == PREC_BF16 || prec == PREC_F16 || prec == PREC_BF16X3 || prec == PREC_F16X3 || prec == PREC_F16F8 || prec == PREC_F16F6, AWT_ERR_INVALID, "gemm: unknown operand precision");
+  AWT_REQUIRE(prec_known(prec), AWT_ERR_INVALID, "gemm: unknown operand precision");
   const int terms = prec_products(prec);
   AWT_REQUIRE(c && c->zeros, AWT_ERR_INVALID, "gemm: context without a zero page");
   static const bool env_read = [] { if (const char* e = getenv("AWT_GEMM_GROUP_N")) g_group_n = std::max(0, atoi(e)); return true; }();   // tile-order experiments (tools/)
@@ -1721,7 +1407,7 @@ int launch_gemm(awt_ctx* c, int M, int N, const GemmSeg* segs, int nseg, int pre
   for (int i = 0; i < nseg; ++i) {
     a.seg[i] = segs[i];
     AWT_REQUIRE(segs[i].K > 0 && segs[i].K % 64 == 0, AWT_ERR_INVALID, "gemm: every K-segment must be a positive multiple of 64");
-    if (prec == PREC_F16F8 || prec == PREC_F16F6) AWT_REQUIRE(segs[i].a_hi && segs[i].w_hi && (segs[i].a8 || (segs[i].w_exact16 && nseg == 1 && prec == PREC_F16F8)) && segs[i].al8 && segs[i].w8 && segs[i].wl8 && segs[i].w_ksteps % 2 == 0 && segs[i].w_k0 % 2 == 0,
+    if (prec == PREC_F16F8) AWT_REQUIRE(segs[i].a_hi && segs[i].w_hi && (segs[i].a8 || (segs[i].w_exact16 && nseg == 1)) && segs[i].al8 && segs[i].w8 && segs[i].wl8 && segs[i].w_ksteps % 2 == 0 && segs[i].w_k0 % 2 == 0,
                                         AWT_ERR_INVALID, "gemm (f16f8): null operand plane or a K-segment that is not 64-aligned in its weight matrix");
     else AWT_REQUIRE(segs[i].a_hi && segs[i].w_hi && (terms == 1 || (segs[i].a_lo && segs[i].w_lo)), AWT_ERR_INVALID, "gemm: null operand plane");
     AWT_REQUIRE(segs[i].lda % 8 == 0 && segs[i].w_ksteps > 0 && segs[i].w_k0 >= 0 && segs[i].w_k0 + segs[i].K / 32 <= segs[i].w_ksteps, AWT_ERR_INVALID,

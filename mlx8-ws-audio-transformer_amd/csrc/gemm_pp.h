@@ -124,9 +124,8 @@ __device__ __forceinline__ void mfma_y(ACC& c, bf16x8 a0, bf16x8 a1, bf16x8 b0, 
 // in flight (they are older than every DMA the loop waits for afterwards: vmcnt retires in order, so the loop's counted waits then
 // wait for them as well -- the price of a store burst is paid at the next tile's first waits, not before its first MFMAs).
 // Requirements: nk even and >= 4; A readable for tiles_m * 256 rows (rows >= M feed accumulators that are never stored).
-template <int FMT, int DMA_WAVES = 8, class EPI>
+template <int FMT, class EPI>
 __device__ __forceinline__ void kloop(const Args& g, char* smem, EPI&& epi) {
-  static_assert(DMA_WAVES == 8 || DMA_WAVES == 2, "staging by all eight waves or by waves 6 and 7");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wr = wave >> 2, wc = wave & 3;
@@ -156,20 +155,18 @@ __device__ __forceinline__ void kloop(const Args& g, char* smem, EPI&& epi) {
   // ---- operand streams.  Every region type walks the same sequence of (tile, K-tile) pairs at its own phase; inside a tile a stream
   // advances by one K-tile per staging (A: 128 bytes along the row, W: 2 regions), and all four streams move on to the next tile within
   // the tile's last K-tile pair, at fixed points of the schedule (pair<true> below), to bases computed once per tile.
-  // DMA_WAVES = 8: every wave stages two 1 KB pieces of each region.  DMA_WAVES = 2: waves 6 and 7 stage eight pieces each and are the only waves that ever wait
-  // on vmcnt in the loop -- the other six waves' epilogue stores then drain behind the next tile's K loop instead of in front of its first DMA waits (vmcnt
-  // retires in order, so a wave that stores AND stages has to see its stores acknowledged before the DMA it is waiting for).
-  constexpr int PIECES = 16 / DMA_WAVES;                  // 1 KB pieces of a 16 KB region per staging wave
-  const bool dma_wave = wave >= 8 - DMA_WAVES;
-  const int dw = wave - (8 - DMA_WAVES);                 // index among the staging waves
+  // Every wave stages two 1 KB pieces of each region (a form with waves 6 and 7 staging for the workgroup was 25 % slower in the K loop: DESIGN.md section 4.2c).
+  // The `wave >= 0` guard of the two staging lambdas is always true and costs no instruction; it stays because the range it gives `wave` shapes the
+  // address arithmetic hipcc emits and with it the kernel's register allocation (without it: 60 instead of 44 bytes of spill scratch).
+  constexpr int PIECES = 2;                              // 1 KB pieces of a 16 KB region per wave
   const char* ab[2];                                     // wave-uniform: A + (tile row + s * 64) * row bytes + K-tile * 128
   const char* wb[2];                                     // wave-uniform: W region (tile column, K-tile, s)
-  // per lane: piece p = dw * PIECES + i covers region rows rho = 8 p + (lane >> 3) = source rows (rho >> 6) * 128 + (rho & 63), chunk (lane & 7) ^ ((rho >> 1) & 7).
-  // Consecutive pieces are 8 rows apart (a wave-uniform address step; PIECES <= 8 keeps a wave inside one 64-row half) and flip bit 2 of the swizzle: two offsets.
+  // per lane: piece p = wave * PIECES + i covers region rows rho = 8 p + (lane >> 3) = source rows (rho >> 6) * 128 + (rho & 63), chunk (lane & 7) ^ ((rho >> 1) & 7).
+  // Consecutive pieces are 8 rows apart (a wave-uniform address step inside one 64-row half) and flip bit 2 of the swizzle: two offsets.
   unsigned aoff[2];
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
-    const int rho = (dw * PIECES + e) * 8 + (lane >> 3), c = (lane & 7) ^ ((rho >> 1) & 7);
+    const int rho = (wave * PIECES + e) * 8 + (lane >> 3), c = (lane & 7) ^ ((rho >> 1) & 7);
     aoff[e] = (unsigned)(((rho >> 6) * 128 + (rho & 63) - 8 * e) * g.a_row_bytes + c * 16);     // piece i: + 8 i rows on the scalar base
   }
   const unsigned wvoff = lane * 16;
@@ -177,24 +174,24 @@ __device__ __forceinline__ void kloop(const Args& g, char* smem, EPI&& epi) {
   auto w_base = [&](int tn, int s) { return g.W + w_region_offset(tn, 0, s, nk); };
   auto stage_a = [&](auto s_t, auto buf_t) {
     constexpr int s = decltype(s_t)::value, buf = decltype(buf_t)::value;
-    if (dma_wave) {
-      const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + buf * BUF + (s ? OFF_A1 : OFF_A0) + dw * PIECES * 1024);
+    if (wave >= 0) {
+      const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + buf * BUF + (s ? OFF_A1 : OFF_A0) + wave * PIECES * 1024);
 #pragma unroll
-      for (int i = 0; i < PIECES; ++i) dma_s(ab[s] + (int64_t)(8 * i) * g.a_row_bytes, aoff[i & 1], dst + i * 1024);
+      for (int i = 0; i < PIECES; ++i) dma_s(ab[s] + (int64_t)(8 * i) * g.a_row_bytes, aoff[i], dst + i * 1024);
     }
     ab[s] += 128;
   };
   auto stage_b = [&](auto s_t, auto buf_t) {
     constexpr int s = decltype(s_t)::value, buf = decltype(buf_t)::value;
-    if (dma_wave) {
-      const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + buf * BUF + (s ? OFF_B1 : OFF_B0) + dw * PIECES * 1024);
+    if (wave >= 0) {
+      const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + buf * BUF + (s ? OFF_B1 : OFF_B0) + wave * PIECES * 1024);
 #pragma unroll
-      for (int i = 0; i < PIECES; ++i) dma_s(wb[s] + (dw * PIECES + i) * 1024, wvoff, dst + i * 1024);
+      for (int i = 0; i < PIECES; ++i) dma_s(wb[s] + (wave * PIECES + i) * 1024, wvoff, dst + i * 1024);
     }
     wb[s] += 2 * REGION;
   };
-  // counted waits of the staging waves: N regions still in flight = N * PIECES pieces (the other waves have nothing of the loop's to wait for)
-  auto vmw = [&](auto n_t) { if (dma_wave) vmwait<decltype(n_t)::value * PIECES>(); };
+  // counted waits: N regions still in flight = N * PIECES pieces
+  auto vmw = [&](auto n_t) { vmwait<decltype(n_t)::value * PIECES>(); };
   using R5 = std::integral_constant<int, 5>; using R4 = std::integral_constant<int, 4>;
   using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
 

@@ -8,11 +8,18 @@ import torch
 
 from . import _lib
 
-_TERMS = {"bf16": 1, "fp16": 2, "bf16x3": 3, "fp16x3": 4, "f16f8": 5, "f16f6": 6}   # common.h PREC_* (f16f6: experimental, `linear` only)
+_TERMS = {"bf16": 1, "fp16": 2, "bf16x3": 3, "fp16x3": 4, "f16f8": 5}   # common.h PREC_*
+
+
+def _terms(precision: str) -> int:
+    if precision not in _TERMS:
+        raise ValueError(f"unknown precision {precision!r}: one of {', '.join(_TERMS)}")
+    return _TERMS[precision]
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, precision: str = "bf16x3") -> torch.Tensor:
     """y = x w^T + bias on the MFMA GEMM kernel; x [M, K], w [N, K] fp32 device tensors, N % 128 == 0, K % 64 == 0."""
+    terms = _terms(precision)
     x, w = x.float().contiguous(), w.float().contiguous()
     M, K = x.shape
     N = w.shape[0]
@@ -22,7 +29,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     b = bias.float().contiguous() if bias is not None else None
     with torch.cuda.device(x.device):
         _lib.check(L.awt_op_linear(_lib.ctx(x.device), _lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y), M, N, K,
-                                   _TERMS[precision], _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
+                                   terms, _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
     return y
 
 
@@ -38,6 +45,7 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, precision: str = "bf16x3") -> torch.Tensor:
     """softmax(q k^T) v for q (pre-scaled), k, v: [B, H, S, 64] fp32 -> [B, S, H * 64] fp32."""
+    terms = _terms(precision)
     q, k, v = (t.float().contiguous() for t in (q, k, v))
     B, H, S, hd = q.shape
     if hd != 64:
@@ -47,5 +55,5 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, precision: str 
     ws = _lib.workspace(L.awt_op_attention_workspace_bytes(B, H, S), q.device)
     with torch.cuda.device(q.device):
         _lib.check(L.awt_op_attention(_lib.ctx(q.device), _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), B, H, S,
-                                      _TERMS[precision], _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
+                                      terms, _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
     return o

@@ -7,7 +7,7 @@ import torch
 from mlx8_ws_audio_transformer_amd import weights as wts
 from oracle import encoder as oracle_enc
 from oracle import logmel as oracle_mel
-from tests.util import piano_clips_f32
+from tests.util import piano_clips_f32, tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -88,7 +88,6 @@ def test_backward_is_reproducible_and_rejects_untrainable_configurations():
 def test_backward_is_bit_identical_under_every_gemm_tiling():
     """Forward-for-training and backward (transposed frozen weights, GELU' epilogue, LoRA segments) under each forced block
     tiling: same adapter gradients bit for bit."""
-    from mlx8_ws_audio_transformer_amd import _lib
     from mlx8_ws_audio_transformer_amd.encoder import NativeWhisperEncoder
     cfg = wts.config("tiny", True)
     spec = wts.LoraSpec(r=8, alpha=16.0, targets=("q_proj", "v_proj"))
@@ -98,15 +97,12 @@ def test_backward_is_bit_identical_under_every_gemm_tiling():
     mel = torch.from_numpy(oracle_mel.whisper_logmel(piano_clips_f32(3), n_samples=cfg.n_frames * 160)).cuda()
     grads = []
     for tile in (0, 64, 128, 256):
-        _lib.tuning_set("gemm_tile", tile)
-        try:
+        with tuning(gemm_tile=tile):
             for p in enc.parameters():
                 p.grad = None
             out = enc(mel).last_hidden_state
             (out * out).sum().backward()
             grads.append(torch.cat([p.grad.flatten() for n, p in enc.named_parameters() if "lora_" in n]).clone())
-        finally:
-            _lib.tuning_set("gemm_tile", 0)
     assert float(grads[0].abs().max()) > 0
     for g in grads[1:]:
         assert torch.equal(g, grads[0])

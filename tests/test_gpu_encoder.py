@@ -6,7 +6,7 @@ import torch
 from mlx8_ws_audio_transformer_amd import weights as wts
 from oracle import encoder as oracle_enc
 from oracle import logmel as oracle_mel
-from tests.util import golden, piano_clips_f32
+from tests.util import golden, piano_clips_f32, tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -98,21 +98,15 @@ def test_encoder_other_parity_modes_vs_oracle(precision, name, trimmed, batch):
 # automatic choice keeps the 128-row tiles): split-line activations from LayerNorm / the attention epilogue / fc1's GELU epilogue
 @pytest.mark.parametrize("name,trimmed,batch", [("small", True, 2), ("small", False, 2), ("base", False, 1), ("tiny", True, 2), ("medium", True, 1)])
 def test_encoder_f16f8_on_the_ping_pong_gemm(name, trimmed, batch):
-    from mlx8_ws_audio_transformer_amd import _lib
     cfg = wts.config(name, trimmed)
     W = wts.init_encoder_weights(cfg, 0, "test")
     mel = _mel(cfg, batch)
     enc = _native(cfg, "f16f8")
     x = torch.from_numpy(mel).cuda()
-    _lib.tuning_set("gemm_pp", 0)
-    base = enc(x).last_hidden_state.cpu().numpy()
-    _lib.tuning_set("gemm_pp", 2)
-    _lib.tuning_set("gemm_pp_mask", 15)
-    try:
+    with tuning(gemm_pp=0):
+        base = enc(x).last_hidden_state.cpu().numpy()
+    with tuning(gemm_pp=2, gemm_pp_mask=15):
         out = enc(x).last_hidden_state.cpu().numpy()
-    finally:
-        _lib.tuning_set("gemm_pp", 1)
-        _lib.tuning_set("gemm_pp_mask", 12)
     ref = oracle_enc.encoder_forward(W, mel, cfg.heads).numpy()
     e = oracle_enc.error_norms(out, ref)
     print(name, trimmed, e, "vs the shipped tiling", float(np.abs(out - base).max()))
@@ -250,7 +244,6 @@ def test_every_gemm_tiling_gives_the_same_bits(precision):
     """The three block tilings (64 x 128, 128 x 128, 128 x 256) accumulate every output element over k in the same order,
     so the whole encoder -- conv-stem segments with row maps, LoRA segments, every fused epilogue -- must agree bit for
     bit whichever tiling is forced."""
-    from mlx8_ws_audio_transformer_amd import _lib
     cfg = wts.config("tiny", True)          # d = 384: qkv N = 1152 and out / fc2 N = 384 fall back from 256 to 128 on their own
     lora = wts.LoraSpec(r=8, alpha=16.0, targets=("q_proj", "v_proj"))
     enc = _native(cfg, precision, lora=lora)
@@ -261,11 +254,8 @@ def test_every_gemm_tiling_gives_the_same_bits(precision):
     mel = torch.from_numpy(_mel(cfg, 3)).cuda()
     outs = []
     for tile in (0, 64, 128, 256):
-        _lib.tuning_set("gemm_tile", tile)
-        try:
+        with tuning(gemm_tile=tile):
             outs.append(enc(mel).last_hidden_state.clone())
-        finally:
-            _lib.tuning_set("gemm_tile", 0)
     for o in outs[1:]:
         assert torch.equal(o, outs[0])
     cfg2 = wts.config("mini", False)        # d = 128, S = 1500
@@ -273,11 +263,8 @@ def test_every_gemm_tiling_gives_the_same_bits(precision):
     mel2 = torch.from_numpy(_mel(cfg2, 1)).cuda()
     ref = enc2(mel2).last_hidden_state.clone()
     for tile in (64, 128):
-        _lib.tuning_set("gemm_tile", tile)
-        try:
+        with tuning(gemm_tile=tile):
             assert torch.equal(enc2(mel2).last_hidden_state, ref)
-        finally:
-            _lib.tuning_set("gemm_tile", 0)
 
 
 # measured envelope per operand precision on the outlier profile (weights.with_outlier_channels: 30x LayerNorm gains, 10x fc2 /
@@ -446,16 +433,12 @@ def test_fp16_exact_checkpoint_takes_the_one_cross_term_gemm_and_keeps_parity(na
 def test_encoder_with_forced_attention_forms(shape):
     """The QKV epilogue only writes v's e4m3 images when the attention form that will run reads them (the default single-product P V form does
     not): forcing a cross-term form through the whole encoder must therefore still see valid planes."""
-    from mlx8_ws_audio_transformer_amd import _lib
     cfg = wts.config("tiny", True)
     W = wts.init_encoder_weights(cfg, 0, "test")
     mel = _mel(cfg, 2)
     ref = oracle_enc.encoder_forward(W, mel, cfg.heads, dtype=torch.float64).numpy()
-    _lib.tuning_set("attn_shape", shape)
-    try:
+    with tuning(attn_shape=shape):
         out = _native(cfg, "f16f8")(torch.from_numpy(mel).cuda()).last_hidden_state.cpu().numpy()
-    finally:
-        _lib.tuning_set("attn_shape", 0)
     e = oracle_enc.error_norms(out, ref)
     print(shape, e)
     assert e["max_abs"] < 3e-4, e

@@ -7,6 +7,7 @@ import torch
 from mlx8_ws_audio_transformer_amd import synth, weights as wts
 from oracle import encoder as oracle_enc
 from oracle import logmel as oracle_mel
+from tests.util import tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -47,16 +48,10 @@ def test_ping_pong_mlp_route_is_bit_identical_to_the_128_row_tiles(full):
     cfg, pcm, enc, hidden, feats = full
     if enc.precision != "f16f8":
         pytest.skip("the ping-pong GEMM is an f16f8 kernel")
-    from mlx8_ws_audio_transformer_amd import _lib
-    try:
-        _lib.tuning_set("gemm_pp", 0)
+    with tuning(gemm_pp=0):
         off = enc.encode_pcm(pcm)
-        _lib.tuning_set("gemm_pp", 2)
-        _lib.tuning_set("gemm_pp_mask", 15)
+    with tuning(gemm_pp=2, gemm_pp_mask=15):
         every = enc.encode_pcm(pcm)
-    finally:
-        _lib.tuning_set("gemm_pp", 1)
-        _lib.tuning_set("gemm_pp_mask", 12)
     assert torch.equal(off, hidden) and torch.equal(every, hidden)
 
 

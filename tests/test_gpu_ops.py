@@ -3,6 +3,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.util import tuning
+
 pytestmark = pytest.mark.gpu
 
 
@@ -20,13 +22,10 @@ TOL = {"bf16x3": 2e-5, "bf16": 1.5e-2, "fp16": 2e-3, "fp16x3": 2e-6, "f16f8": 6e
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (300, 256, 192), (1500, 384, 768), (77, 128, 3072),
                                    (2500, 768, 768), (4096, 256, 128), (3000, 2304, 768)])
 def test_linear(precision, M, N, K, tile):
-    from mlx8_ws_audio_transformer_amd import _lib, ops
+    from mlx8_ws_audio_transformer_amd import ops
     x, w, b = _rand((M, K), 1), _rand((N, K), 2, K ** -0.5), _rand((N,), 3)
-    _lib.tuning_set("gemm_tile", tile)
-    try:
+    with tuning(gemm_tile=tile):
         y = ops.linear(x, w, b, precision)
-    finally:
-        _lib.tuning_set("gemm_tile", 0)
     ref = torch.nn.functional.linear(x.double(), w.double(), b.double())
     err = (y.double() - ref).abs().max().item()
     print(precision, (M, N, K), tile, "max-abs", err, "ref max", ref.abs().max().item())
@@ -39,16 +38,13 @@ def test_linear(precision, M, N, K, tile):
 @pytest.mark.parametrize("M,N,K", [(256, 256, 128), (300, 256, 192), (1000, 512, 768), (2500, 768, 768), (3000, 2304, 768), (777, 768, 3072), (70000, 512, 256),
                                    (700, 1280, 1280), (520, 1280, 5120), (300, 5120, 1280)])     # ... and large-v3's widths (nk = 40, 160)
 def test_linear_ping_pong(M, N, K):
-    from mlx8_ws_audio_transformer_amd import _lib, ops
+    from mlx8_ws_audio_transformer_amd import ops
     x, w, b = _rand((M, K), 1), _rand((N, K), 2, K ** -0.5), _rand((N,), 3)
     ref = torch.nn.functional.linear(x.double(), w.double(), b.double())
     y_ship = ops.linear(x, w, b, "f16f8")
-    _lib.tuning_set("gemm_pp", 2)
-    try:
+    with tuning(gemm_pp=2):
         y = ops.linear(x, w, b, "f16f8")
         y2 = ops.linear(x, w, b, "f16f8")
-    finally:
-        _lib.tuning_set("gemm_pp", 1)
     err = (y.double() - ref).abs().max().item()
     print((M, N, K), "ping-pong max-abs", err, "shipped kernel", (y_ship.double() - ref).abs().max().item())
     assert err < TOL["f16f8"] * max(1.0, ref.abs().max().item()), err
@@ -61,18 +57,14 @@ def test_linear_ping_pong(M, N, K):
 @pytest.mark.parametrize("M,N,K", [(3000, 768, 768), (2999, 2304, 768), (4100, 768, 3072), (6000, 1536, 384), (3000, 1280, 5120), (36000, 3072, 768),
                                    (3000, 1152, 384), (2999, 384, 1536), (5000, 384, 384), (48000, 1152, 384)])    # ... and Whisper-tiny's widths: a partly empty last column tile
 def test_linear_f16f8_on_16x16_mfma(M, N, K):
-    from mlx8_ws_audio_transformer_amd import _lib, ops
+    from mlx8_ws_audio_transformer_amd import ops
     x, w, b = _rand((M, K), 1), _rand((N, K), 2, K ** -0.5), _rand((N,), 3)
     ref = torch.nn.functional.linear(x.double(), w.double(), b.double())
-    _lib.tuning_set("gemm_tile", 256)
-    try:
+    with tuning(gemm_tile=256):
         y = ops.linear(x, w, b, "f16f8")
         y2 = ops.linear(x, w, b, "f16f8")
-        _lib.tuning_set("gemm_mfma16", 0)
+    with tuning(gemm_tile=256, gemm_mfma16=0):
         y32 = ops.linear(x, w, b, "f16f8")
-    finally:
-        _lib.tuning_set("gemm_mfma16", 1)
-        _lib.tuning_set("gemm_tile", 0)
     err, err32 = (y.double() - ref).abs().max().item(), (y32.double() - ref).abs().max().item()
     print((M, N, K), "16x16 max-abs", err, "32x32", err32, "between", (y - y32).abs().max().item())
     assert err < TOL["f16f8"] * max(1.0, ref.abs().max().item()), err
@@ -82,16 +74,13 @@ def test_linear_f16f8_on_16x16_mfma(M, N, K):
 
 def test_linear_f16f8_on_16x16_mfma_places_every_element():
     # x = rows of a permutation-like matrix, W with a distinct value per (n, k): a swapped fragment lane, K block or C register shows up as a wrong element
-    from mlx8_ws_audio_transformer_amd import _lib, ops
+    from mlx8_ws_audio_transformer_amd import ops
     M, N, K = 4096, 512, 256
     x = torch.zeros(M, K)
     x[torch.arange(M), (torch.arange(M) * 7) % K] = 1.0
     w = ((torch.arange(N * K, dtype=torch.float32).reshape(N, K) * 37) % 1021 - 510) / 1024 + 1e-4     # not fp16-exact: keeps the general kernel
-    _lib.tuning_set("gemm_tile", 256)
-    try:
+    with tuning(gemm_tile=256):
         y = ops.linear(x.cuda(), w.cuda(), None, "f16f8").cpu()
-    finally:
-        _lib.tuning_set("gemm_tile", 0)
     ref = w.t()[(torch.arange(M) * 7) % K]
     assert (y - ref).abs().max().item() < 1e-6
 
@@ -101,7 +90,7 @@ def test_linear_f16f8_seeded_random_shapes_on_every_route():
     # through the three f16f8 GEMM routes -- automatic, the 128 x 256 16 x 16-MFMA tiles forced, the ping-pong kernel wherever it applies -- against fp64:
     # partial row panels, partial column tiles and the persistent kernel's panel over-read all in one place
     import random
-    from mlx8_ws_audio_transformer_amd import _lib, ops
+    from mlx8_ws_audio_transformer_amd import ops
     rnd = random.Random(20260401)
     shapes = [(rnd.choice([1, 7, 127, 128, 129, 255, 257, 1000, 1501, 3000, 4099]), 128 * rnd.randint(1, 12), 64 * rnd.randint(1, 24)) for _ in range(36)]
     worst = 0.0
@@ -109,16 +98,9 @@ def test_linear_f16f8_seeded_random_shapes_on_every_route():
         x, w, b = _rand((M, K), 100 + i), _rand((N, K), 200 + i, K ** -0.5), _rand((N,), 300 + i)
         ref = torch.nn.functional.linear(x.double(), w.double(), b.double())
         bound = TOL["f16f8"] * max(1.0, ref.abs().max().item())
-        for route in ("auto", "tile256", "ping-pong"):
-            try:
-                if route == "tile256":
-                    _lib.tuning_set("gemm_tile", 256)
-                if route == "ping-pong":
-                    _lib.tuning_set("gemm_pp", 2)
+        for route, knobs in (("auto", {}), ("tile256", {"gemm_tile": 256}), ("ping-pong", {"gemm_pp": 2})):
+            with tuning(**knobs):
                 y = ops.linear(x, w, b, "f16f8")
-            finally:
-                _lib.tuning_set("gemm_tile", 0)
-                _lib.tuning_set("gemm_pp", 1)
             err = (y.double() - ref).abs().max().item()
             worst = max(worst, err / bound)
             assert torch.isfinite(y).all() and err < bound, (M, N, K, route, err)
@@ -176,15 +158,12 @@ def test_attention(precision, B, H, S):
 @pytest.mark.parametrize("shape", [1, 2, 3, 4, 5, 6, 7])
 def test_attention_f16f8_workgroup_shapes(shape):
     """Every workgroup shape of the f16f8 attention kernel (4 x 32, 4 x 64, 6 x 32 queries) on a sequence with a tail tile."""
-    from mlx8_ws_audio_transformer_amd import _lib, ops
+    from mlx8_ws_audio_transformer_amd import ops
     for S in (333, 64, 100, 128, 200, 1500):          # 6 / 1 / 2 / 2 / 4 / 24 key tiles, with and without a tail tile
         B, H = 2, 2
         q, k, v = _rand((B, H, S, 64), 17, 0.35), _rand((B, H, S, 64), 18), _rand((B, H, S, 64), 19)
-        _lib.tuning_set("attn_shape", shape)
-        try:
+        with tuning(attn_shape=shape):
             o = ops.attention(q, k, v, "f16f8")
-        finally:
-            _lib.tuning_set("attn_shape", 0)
         p = torch.softmax(q.double() @ k.double().transpose(2, 3), dim=-1)
         ref = (p @ v.double()).transpose(1, 2).reshape(B, S, H * 64)
         assert (o.double() - ref).abs().max().item() < (ATT_TOL_F16F8_CROSS if shape <= 5 else ATT_TOL["f16f8"]), S
@@ -193,19 +172,19 @@ def test_attention_f16f8_workgroup_shapes(shape):
 @pytest.mark.parametrize("precision", ["bf16x3", "fp16x3", "f16f8", "f16f8-pipe"])
 def test_attention_online_softmax_rescale_branch(precision):
     # one key per late tile dominates one query's row: forces the running maximum to jump tile after tile
-    from mlx8_ws_audio_transformer_amd import _lib, ops
+    from mlx8_ws_audio_transformer_amd import ops
+    knobs = {}
     if precision == "f16f8-pipe":
-        _lib.tuning_set("attn_shape", 4)
-        precision = "f16f8"
+        knobs, precision = {"attn_shape": 4}, "f16f8"
     B, H, S = 1, 1, 448
     q, k, v = _rand((B, H, S, 64), 10, 0.2), _rand((B, H, S, 64), 11), _rand((B, H, S, 64), 12)
     for t, key in enumerate([70, 150, 260, 390]):
         k[0, 0, key] = q[0, 0, 5] * (20.0 + 15 * t)
-    o = ops.attention(q, k, v, precision)
+    with tuning(**knobs):
+        o = ops.attention(q, k, v, precision)
     p = torch.softmax(q.double() @ k.double().transpose(2, 3), dim=-1)
     ref = (p @ v.double()).transpose(1, 2).reshape(B, S, 64)
     # logits reach ~170: fp32 ulp of the exp2 argument is ~1.5e-5; f16f8 carries the logits to 2^-16 relative: 170 * 2^-16 = 2.6e-3 in the exponent
-    _lib.tuning_set("attn_shape", 0)
     assert (o.double() - ref).abs().max().item() < (3e-4 if precision != "f16f8" else 1.5e-2)
 
 
@@ -220,13 +199,23 @@ def test_linear_output_larger_than_2g_elements():
     assert (y[rows].double() - ref).abs().max().item() < TOL["bf16x3"] * max(1.0, ref.abs().max().item())
 
 
-def test_fp6_experiment_is_not_in_the_shipped_library():
-    """The round-2 FP6 (e3m2) cross-term experiment is compiled only with -DAWT_EXPERIMENTAL_F6: the shipped library refuses the mode
-    loudly instead of carrying an unreachable kernel."""
+def test_fp6_precision_is_refused():
+    """The round-2 FP6 (e3m2) cross-term experiment (precision code 6) is not part of the library: the Python layer
+    refuses the name, and the C ABI refuses the code as its first check, before anything is written or launched."""
     from mlx8_ws_audio_transformer_amd import _lib, ops
     x, w = _rand((128, 64), 31), _rand((256, 64), 32, 0.125)
-    with pytest.raises(_lib.AwtError, match="AWT_EXPERIMENTAL_F6"):
+    with pytest.raises(ValueError, match="f16f6"):
         ops.linear(x, w, None, "f16f6")
+    M, K = x.shape
+    N = w.shape[0]
+    L = _lib.lib()
+    y = torch.full((M, N), 7.0, device="cuda")
+    ws = _lib.workspace(L.awt_op_linear_workspace_bytes(M, N, K), x.device)
+    with pytest.raises(_lib.AwtError, match="terms"):
+        _lib.check(L.awt_op_linear(_lib.ctx(x.device), _lib.ptr(x), _lib.ptr(w), None, _lib.ptr(y), M, N, K, 6, _lib.ptr(ws), ws.numel(),
+                                   _lib.stream_handle()))
+    torch.cuda.synchronize()
+    assert bool((y == 7.0).all())
 
 
 @pytest.mark.parametrize("M,N,K", [(1000, 256, 64), (1500, 768, 768), (3000, 768, 3072), (700, 384, 1536), (96, 2304, 768)])
@@ -250,15 +239,12 @@ def test_linear_f16f8_with_fp16_exact_weights(M, N, K):
 
 def test_exact_weight_gemm_is_bit_identical_across_block_tiles():
     """The one-cross-term (fp16-exact weights) GEMM on every block-tile configuration: 128 x 128, 128 x 256, 256 x 256 -- same bits."""
-    from mlx8_ws_audio_transformer_amd import _lib, ops
+    from mlx8_ws_audio_transformer_amd import ops
     x, w, b = _rand((2000, 768), 51), _rand((768, 768), 52, 768 ** -0.5).half().float(), _rand((768,), 53)
     outs = {}
-    try:
-        for tile in (256, 128, 512):
-            _lib.tuning_set("gemm_tile", tile)
+    for tile in (256, 128, 512):
+        with tuning(gemm_tile=tile):
             outs[tile] = ops.linear(x, w, b, "f16f8")
-    finally:
-        _lib.tuning_set("gemm_tile", 0)
     assert torch.equal(outs[256], outs[128]) and torch.equal(outs[256], outs[512])
     ref = x.double() @ w.double().t() + b.double()
     assert (outs[256].double() - ref).abs().max().item() < 1e-4
@@ -268,17 +254,14 @@ def test_exact_weight_gemm_is_bit_identical_across_block_tiles():
 def test_linear_fp16x3_with_fp16_exact_weights(M, N, K):
     """Split-fp16 mode on weights that are exactly fp16: the a_hi w_lo product is zero and is not issued (two products per fragment pair).
     The result stays at the mode's accuracy, for every block tile."""
-    from mlx8_ws_audio_transformer_amd import _lib, ops
+    from mlx8_ws_audio_transformer_amd import ops
     x, w, b = _rand((M, K), 61), _rand((N, K), 62, K ** -0.5).half().float(), _rand((N,), 63)
     ref = x.double() @ w.double().t() + b.double()
-    try:
-        for tile in (0, 64, 128, 256):
-            _lib.tuning_set("gemm_tile", tile)
+    for tile in (0, 64, 128, 256):
+        with tuning(gemm_tile=tile):
             y = ops.linear(x, w, b, "fp16x3")
-            err = (y.double() - ref).abs().max().item()
-            assert err < 1e-5 * max(1.0, (K / 768) ** 0.5), (tile, err)     # fp32 accumulation noise of O(1) outputs (bias included)
-    finally:
-        _lib.tuning_set("gemm_tile", 0)
+        err = (y.double() - ref).abs().max().item()
+        assert err < 1e-5 * max(1.0, (K / 768) ** 0.5), (tile, err)     # fp32 accumulation noise of O(1) outputs (bias included)
 
 
 def test_linear_f16f8_activation_planes_larger_than_4_gib():

@@ -1,4 +1,5 @@
-"""Shared seeded inputs for the parity tests (regenerates exactly what tools/make_golden.py fed the reference)."""
+"""Shared seeded inputs for the parity tests (regenerates exactly what tools/make_golden.py fed the reference), and the tuning-knob context."""
+import contextlib
 import os
 
 import numpy as np
@@ -6,6 +7,27 @@ import numpy as np
 from mlx8_ws_audio_transformer_amd import synth, weights as wts
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+# the library's defaults of the tuning knobs the tests change (include/awt.h, awt_tuning_set)
+TUNING_DEFAULTS = {"gemm_tile": 0, "gemm_pp": 1, "gemm_pp_mask": 12, "gemm_mfma16": 1, "attn_shape": 0}
+
+
+@contextlib.contextmanager
+def tuning(**knobs):
+    """Sets the given tuning knobs for the block; on exit every knob of TUNING_DEFAULTS is back at its library default."""
+    from mlx8_ws_audio_transformer_amd import _lib
+
+    unknown = set(knobs) - set(TUNING_DEFAULTS)
+    if unknown:
+        raise KeyError(f"tuning: no default recorded for {sorted(unknown)}")
+    try:
+        for key, value in knobs.items():
+            _lib.tuning_set(key, value)
+        yield
+    finally:
+        for key, value in TUNING_DEFAULTS.items():
+            _lib.tuning_set(key, value)
 
 
 def golden(name):
