@@ -326,6 +326,27 @@ int awt_op_attention_small_backward_dropout(awt_ctx* c, const float* q, int ldq,
                                             const float* dout, int ldo, const float* lse, float* delta, float* dq, float* dk, float* dv, int B,
                                             int H, int Lq, int Sk, int causal, int causal_off, float drop_p, uint64_t seed, void* stream);
 
+/* Causal attention of Lq new query rows per batch over a preallocated decode cache: keys / values of batch b, position j at
+ * k + b kv_batch_stride + j ldkv + 64 h (likewise v), T live positions (T >= Lq; query i sees keys j <= T - Lq + i).  q / o as in
+ * awt_op_attention_small.  The cache is [rows, Tmax, 2 d] per layer, so kv_batch_stride = Tmax ldkv (csrc/decoder_ops.hip). */
+int awt_op_attention_cached(awt_ctx* c, const float* q, int ldq, const float* k, const float* v, int ldkv, int64_t kv_batch_stride, float* o,
+                            int ldo, int B, int H, int Lq, int T, void* stream);
+/* Next-token selection of generate (csrc/decode_select.hip), two launches, bit-reproducible.  rows = clips x beams rows of logits
+ * (pitch ld >= vocab, ld % 4 == 0, 16-byte aligned; columns >= vocab are never read as candidates).  Per row: log-softmax over all
+ * vocab columns when log_softmax != 0, then columns whose bit is set in `banned` ((vocab + 31) / 32 words, or NULL) become -inf, then
+ * beam_scores[row] is added (NULL: 0).  Per clip: the k best of its beams x vocab candidates, best first (NaN first, ties to the lower
+ * beam x vocab index): top_scores / top_tokens / top_parent [clips, k] (top_parent = beam within the clip; may be NULL).  beams <= 8,
+ * k <= 16.  beams = 1, k = 1, log_softmax = 0 is torch.argmax after banning.  workspace: awt_select_tokens_workspace_bytes. */
+size_t awt_select_tokens_workspace_bytes(int rows, int vocab, int k);
+int awt_op_select_tokens(awt_ctx* c, const float* logits, int ld, int rows, int vocab, int beams, const uint32_t* banned, const float* beam_scores,
+                         int log_softmax, int k, float* top_scores, int64_t* top_tokens, int32_t* top_parent, void* workspace, size_t ws_bytes,
+                         void* stream);
+/* dst[l, r, t, :] = src[l, parent[r], t, :] for l < layers, r < dst_rows, t < T of caches laid out [layers, rows, Tmax, width]
+ * (src with src_rows rows, dst with dst_rows; width % 4 == 0; src != dst).  One launch.  A parent outside [0, src_rows) leaves its
+ * destination row as it was.  Beam reorder (parent = surviving beams' parents) and the B -> B x beams expansion (parent = r / beams). */
+int awt_op_kv_gather(awt_ctx* c, const float* src, float* dst, const int32_t* parent, int layers, int src_rows, int dst_rows, int T, int Tmax,
+                     int width, void* stream);
+
 /* Process-wide tuning / test hooks.  key "gemm_tile": 0 = choose the GEMM block tile from the shape (default), 64 / 128 / 256 =
  * force the 64 x 128, 128 x 128 or 128 x 256 tile (256 falls back to 128 when N is not a multiple of 256) so that tests can
  * drive every tiling on small shapes; 512 = the 256 x 256 eight-wave tile of the f16f8 GEMM (same results, slower).

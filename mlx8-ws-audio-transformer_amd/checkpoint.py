@@ -157,3 +157,11 @@ def save_pretrained_dir(path: str, cfg: dict, encoder_sd: Dict[str, torch.Tensor
     else:
         raise ValueError("fmt must be 'safetensors' or 'bin'")
     return path
+
+
+def load_generation_config(path: str):
+    """`generation_config.json` of a checkpoint directory as a generation.GenerationConfig, or None when the directory has none (HF
+    `GenerationConfig.from_pretrained`; `trainer.save_model()` writes it next to config.json, AB/fineTune.py:200)."""
+    from .generation import GenerationConfig
+    gpath = os.path.join(os.fspath(path), "generation_config.json")
+    return GenerationConfig.from_json_file(gpath) if os.path.exists(gpath) else None

@@ -209,6 +209,9 @@ struct SmallAttn {
   // index, top 24 bits against p -- so the forward and both backward kernels regenerate it instead of storing B H Lq Sk bytes, and a host-side
   // restatement of the same function gives tests the identical mask.  drop_p = 0: no dropout (inv_keep = 1).
   float drop_p, inv_keep; unsigned long long seed;
+  // elements between consecutive batches of k / v in the forward kernel; 0 = Sk ldk / Sk ldv (packed).  A preallocated decode cache
+  // [rows, Tmax, 2 d] holds T <= Tmax live positions per row: batch stride Tmax ldk (awt_op_attention_cached).
+  int64_t kbs, vbs;
 };
 __device__ __forceinline__ float drop_keep(const SmallAttn& a, int bh, int i, int j) {
   if (a.drop_p <= 0.f) return 1.0f;
@@ -309,8 +312,8 @@ __global__ __launch_bounds__(256) void small_attn_fwd_kernel(SmallAttn a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int bh = blockIdx.x, h = bh % a.H, b = bh / a.H;
   const int i0 = blockIdx.y * QB, nq = min(QB, a.Lq - i0);
-  const float* kp = a.k + (int64_t)b * a.Sk * a.ldk + 64 * h;
-  const float* vp = a.v + (int64_t)b * a.Sk * a.ldv + 64 * h;
+  const float* kp = a.k + (int64_t)b * (a.kbs ? a.kbs : (int64_t)a.Sk * a.ldk) + 64 * h;
+  const float* vp = a.v + (int64_t)b * (a.vbs ? a.vbs : (int64_t)a.Sk * a.ldv) + 64 * h;
   for (int t = threadIdx.x; t < QB * 64; t += 256) {
     const int i = t >> 6, e = t & 63;
     qs[i][e] = i < nq ? a.q[((int64_t)b * a.Lq + i0 + i) * a.ldq + 64 * h + e] * 0.125f : 0.f;
@@ -592,6 +595,18 @@ extern "C" int awt_op_attention_small_dropout(awt_ctx* c, const float* q, int ld
   AWT_REQUIRE(c && q && k && v && o, AWT_ERR_INVALID, "op_attention_small: null argument");
   SmallAttn a{q, k, v, o, lse, nullptr, nullptr, nullptr, nullptr, nullptr, B, H, Lq, Sk, ldq, ldk, ldv, ldo, causal, causal_off, drop_p, drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f, seed};
   int rc = check_small(a, "op_attention_small"); if (rc) return rc;
+  hipLaunchKernelGGL(small_attn_fwd_kernel, dim3(B * H, (Lq + QB - 1) / QB), dim3(256), 0, (hipStream_t)stream, a);
+  AWT_HIP_CHECK(hipGetLastError());
+  return AWT_OK;
+}
+extern "C" int awt_op_attention_cached(awt_ctx* c, const float* q, int ldq, const float* k, const float* v, int ldkv, int64_t kv_batch_stride, float* o,
+                                       int ldo, int B, int H, int Lq, int T, void* stream) {
+  AWT_REQUIRE(c && q && k && v && o, AWT_ERR_INVALID, "op_attention_cached: null argument");
+  AWT_REQUIRE(T >= Lq && kv_batch_stride >= (int64_t)T * ldkv && kv_batch_stride % 4 == 0, AWT_ERR_INVALID,
+              "op_attention_cached: need T >= Lq and a batch stride that is a multiple of 4 covering T rows of ldkv");
+  SmallAttn a{q, k, v, o, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, H, Lq, T, ldq, ldkv, ldkv, ldo, 1, T - Lq, 0.0f, 1.0f, 0,
+              kv_batch_stride, kv_batch_stride};
+  int rc = check_small(a, "op_attention_cached"); if (rc) return rc;
   hipLaunchKernelGGL(small_attn_fwd_kernel, dim3(B * H, (Lq + QB - 1) / QB), dim3(256), 0, (hipStream_t)stream, a);
   AWT_HIP_CHECK(hipGetLastError());
   return AWT_OK;

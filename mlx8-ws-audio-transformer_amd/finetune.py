@@ -24,6 +24,7 @@ loss and greedy decoding are pinned to `WhisperForConditionalGeneration` by test
 """
 from __future__ import annotations
 
+import copy
 import math
 import os
 from dataclasses import dataclass, field
@@ -190,6 +191,10 @@ class WhisperLoRAModel(nn.Module):
         for n, p in self.decoder.named_parameters():
             p.requires_grad = "lora_" in n      # frozen base model: only the adapters train
         self.config = SimpleNamespace(decoder_start_token_id=DECODER_START, pad_token_id=PAD_ID, eos_token_id=EOS_ID, d_model=cfg.d_model)
+        self.max_target_positions = max_target_positions
+        # what generate reads (HF `model.generation_config`); a constructed model has no Whisper prompt fields and decodes as it always did
+        from .generation import GenerationConfig
+        self.generation_config = GenerationConfig(decoder_start_token_id=DECODER_START, pad_token_id=PAD_ID, eos_token_id=EOS_ID, max_length=225)
 
     def lora_parameters(self) -> List[nn.Parameter]:
         """Every trainable parameter: the encoder's adapters, then the decoder's (if any)."""
@@ -222,6 +227,11 @@ class WhisperLoRAModel(nn.Module):
         for key, attr in (("decoder_start_token_id", "decoder_start_token_id"), ("pad_token_id", "pad_token_id"), ("eos_token_id", "eos_token_id")):
             if hf.get(key) is not None:
                 setattr(model.config, attr, int(hf[key]))
+                setattr(model.generation_config, attr, int(hf[key]))
+        from .checkpoint import load_generation_config
+        gc = load_generation_config(path)
+        if gc is not None:
+            model.generation_config = gc
         model.name_or_path = os.fspath(path)
         return model
 
@@ -252,7 +262,11 @@ class WhisperLoRAModel(nn.Module):
                "max_target_positions": d.embed_positions.weight.shape[0], "decoder_start_token_id": self.config.decoder_start_token_id,
                "pad_token_id": self.config.pad_token_id, "eos_token_id": self.config.eos_token_id, "activation_function": "gelu",
                "scale_embedding": False, "torch_dtype": "float32"}
-        return save_pretrained_dir(os.fspath(path), cfg, enc, dec, fmt=fmt)
+        out = save_pretrained_dir(os.fspath(path), cfg, enc, dec, fmt=fmt)
+        gc = getattr(self, "generation_config", None)
+        if gc is not None and gc.whisper_prompt:                    # a Whisper generation config travels with the weights
+            gc.save(out)
+        return out
 
     def forward(self, input_features: torch.Tensor, labels: Optional[torch.Tensor] = None, decoder_input_ids: Optional[torch.Tensor] = None):
         if decoder_input_ids is None:
@@ -274,18 +288,99 @@ class WhisperLoRAModel(nn.Module):
         return SimpleNamespace(loss=loss, logits=logits, encoder_last_hidden_state=hidden)
 
     @torch.no_grad()
-    def generate(self, input_features: torch.Tensor, max_length: int = 225, eos_token_id: Optional[int] = None,
-                 decoder_input_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Greedy decoding as `model.generate(input_features)` is used at AB/wavToWhisper.py:59 / fineTuneMidiTester.py:34 and by
-        `predict_with_generate` (fineTune.py:172): encoder once, cross-attention keys / values once (the fused native
-        projection), then one token per step with a self-attention cache.  Returns [B, <= max_length] token ids, starting
-        with decoder_start_token_id; rows that have emitted `eos_token_id` are padded with pad_token_id."""
+    def generate(self, input_features: torch.Tensor, max_length: Optional[int] = None, eos_token_id: Optional[int] = None,
+                 decoder_input_ids: Optional[torch.Tensor] = None, num_beams: Optional[int] = None, length_penalty: Optional[float] = None,
+                 early_stopping=None, language=None, task: Optional[str] = None, is_multilingual: Optional[bool] = None,
+                 return_timestamps: Optional[bool] = None, do_sample: Optional[bool] = None, num_return_sequences: Optional[int] = None,
+                 return_dict_in_generate: bool = False, generation_config=None, **kwargs):
+        """`model.generate(input_features)` as AB/wavToWhisper.py:59 / fineTuneMidiTester.py:34 and `predict_with_generate` (fineTune.py:172)
+        use it: HF 5.15 `WhisperForConditionalGeneration.generate` for short-form input (generation.py).  Encoder once, cross-attention
+        keys / values once, then one token per step (greedy, or beam search with num_beams > 1 on the native decoder).
+
+        With a Whisper generation config (`generation_config.lang_to_id` / `task_to_id` / `no_timestamps_token_id` / `forced_decoder_ids`,
+        as `from_pretrained` reads from generation_config.json): the prompt <|startoftranscript|> <|lang|> <|task|> <|notimestamps|> is
+        forced (the language detected when unset), `suppress_tokens` / `begin_suppress_tokens` are masked, `max_length` counts generated
+        tokens, and the result holds only the generated tokens, right-padded with pad_token_id.  Without one (a constructed model):
+        [B, <= max_length] ids starting with decoder_start_token_id (or `decoder_input_ids`); rows that emitted EOS continue with pad.
+        return_dict_in_generate: a namespace with `sequences` (as returned otherwise) and `sequences_scores` (beam search, else None)."""
+        from . import generation as G
+        if kwargs:
+            raise TypeError(f"generate: unsupported arguments {sorted(kwargs)}")
+        if return_timestamps:
+            raise ValueError("generate: return_timestamps=True is not supported (timestamp tokens are out of scope)")
+        if do_sample:
+            raise ValueError("generate: do_sample=True is not supported (sampling is out of scope)")
+        if num_return_sequences is not None and num_return_sequences > 1:
+            raise ValueError("generate: num_return_sequences > 1 is not supported")
+        window = 2 * self.encoder.cfg.max_source_positions
+        if input_features.shape[-1] > window:
+            raise ValueError(f"generate: inputs longer than one {window}-frame window (long-form decoding) are not supported")
+        gc = copy.deepcopy(generation_config if generation_config is not None else self.generation_config)
+        nb = int(num_beams if num_beams is not None else (gc.num_beams or 1))
+        if nb < 1 or nb > G.MAX_BEAMS:
+            raise ValueError(f"generate: num_beams must be between 1 and {G.MAX_BEAMS}, got {nb}")
+        if nb > 1 and not self.native_decoder:
+            raise ValueError("generate: beam search (num_beams > 1) needs the native decoder (native_decoder=True)")
+        lp = float(length_penalty if length_penalty is not None else (gc.length_penalty if gc.length_penalty is not None else 1.0))
+        es = early_stopping if early_stopping is not None else (gc.early_stopping if gc.early_stopping is not None else False)
+        whisper = gc.whisper_prompt and decoder_input_ids is None
+        for f in ("decoder_start_token_id", "pad_token_id", "eos_token_id"):      # without a Whisper prompt the model's config decides, as before
+            if not whisper or getattr(gc, f) is None:
+                setattr(gc, f, getattr(self.config, f))
+        eos = eos_token_id if eos_token_id is not None else gc.eos_token_id
+        pad = gc.pad_token_id
+        G.set_language_and_task(gc, language, task, is_multilingual)
+        hidden = self.encoder(input_features).last_hidden_state
+        B = hidden.shape[0]
+        cross = self.decoder.cross_kv(hidden, self.precision) if (self.native_cross_kv or self.native_decoder) else None
+        if whisper:
+            init = G.retrieve_init_tokens(gc, B, detect=lambda: self._detect_language(hidden, cross, gc).tolist())
+            init = torch.tensor(init, dtype=torch.long, device=hidden.device)
+            P = init.shape[1]
+            limit = gc.max_length if max_length is None else max_length
+            max_len = min(int(limit) + min(self.max_target_positions // 2 - 1, P), self.max_target_positions)     # _set_max_new_tokens_and_length
+            suppress, begin = gc.suppress_tokens, gc.begin_suppress_tokens
+        else:
+            init = decoder_input_ids.to(hidden.device) if decoder_input_ids is not None else \
+                torch.full((B, 1), gc.decoder_start_token_id, dtype=torch.long, device=hidden.device)
+            P = init.shape[1]
+            max_len = int(max_length if max_length is not None else (gc.max_length or 225))
+            suppress, begin = gc.suppress_tokens, gc.begin_suppress_tokens
+        steps = self._decode_steps(hidden, cross, B, max_len)
+        scores = None
+        if nb == 1:
+            seqs = G.greedy(steps, init, max_len, eos, pad, suppress, begin)
+        else:
+            seqs, scores, _ = G.beam_search(steps, init, max_len, eos, pad, suppress, begin, nb, lp, es)
+        if whisper:
+            seqs = G.strip_prompt(seqs, P, pad, eos)
+        return SimpleNamespace(sequences=seqs, sequences_scores=scores) if return_dict_in_generate else seqs
+
+    def _decode_steps(self, hidden, cross, B, max_len):
+        from . import generation as G
+        if self.native_decoder:
+            return G._NativeSteps(self.decoder, cross, hidden.shape[1], B, max_len)
+        return G._TorchSteps(self.decoder, hidden, cross, self.decoder_autocast)
+
+    def _detect_language(self, hidden, cross, gc) -> torch.Tensor:
+        """`WhisperGenerationMixin.detect_language` on encoder states: one decoder step from decoder_start_token_id, argmax over the
+        `lang_to_id` tokens (every other token banned in the selection kernel)."""
+        from . import generation as G
+        if gc.lang_to_id is None:
+            raise ValueError("detect_language needs `generation_config.lang_to_id`")
+        B = hidden.shape[0]
+        steps = self._decode_steps(hidden, cross, B, 1)
+        logits = steps.prefill(torch.full((B, 1), gc.decoder_start_token_id, dtype=torch.long, device=hidden.device))
+        banned = G.banned_bits(list(gc.lang_to_id.values()), steps.vocab, hidden.device, invert=True)
+        return G.select_tokens(logits, steps.vocab, banned=banned)[1][:, 0]
+
+    @torch.no_grad()
+    def detect_language(self, input_features: torch.Tensor, generation_config=None) -> torch.Tensor:
+        """[B] language token ids of the clips (HF `model.detect_language(input_features)`)."""
+        gc = generation_config if generation_config is not None else self.generation_config
         hidden = self.encoder(input_features).last_hidden_state
         cross = self.decoder.cross_kv(hidden, self.precision) if (self.native_cross_kv or self.native_decoder) else None
-        with torch.autocast("cuda", dtype=self.decoder_autocast or torch.bfloat16, enabled=self.decoder_autocast is not None):
-            return greedy_decode(self.decoder, hidden, self.config.decoder_start_token_id, self.config.pad_token_id,
-                                 self.config.eos_token_id if eos_token_id is None else eos_token_id, max_length, cross=cross,
-                                 decoder_input_ids=decoder_input_ids)
+        return self._detect_language(hidden, cross, gc)
 
 
 @torch.no_grad()
@@ -344,6 +439,7 @@ class Seq2SeqTrainingArguments:
     per_device_eval_batch_size: int = 8
     predict_with_generate: bool = True
     generation_max_length: int = 225
+    generation_num_beams: Optional[int] = None        # HF's field: num_beams of evaluate()'s generate (None: the model's generation config)
     save_steps: int = 50
     eval_steps: int = 10
     logging_steps: int = 10
@@ -503,7 +599,7 @@ class Seq2SeqTrainer:
             n_tok = int((lab != -100).sum())
             losses.append(float(out.loss) * n_tok); weights.append(n_tok)
             if self.args.predict_with_generate:
-                preds.append(self.model.generate(feats, max_length=self.args.generation_max_length).cpu())
+                preds.append(self.model.generate(feats, max_length=self.args.generation_max_length, num_beams=self.args.generation_num_beams).cpu())
                 labels.append(lab.cpu())
         metrics = {"eval_loss": sum(losses) / max(1, sum(weights))}
         if self.args.predict_with_generate and self.compute_metrics is not None:

@@ -1,0 +1,404 @@
+"""Whisper's `generate` for short-form input: prompt, token suppression, greedy and beam search (HF 5.15
+`WhisperForConditionalGeneration.generate`, transformers/models/whisper/generation_whisper.py, and `GenerationMixin._sample` /
+`_beam_search`, transformers/generation/utils.py).
+
+The reference decodes with `model.generate(input_features)` (AB/wavToWhisper.py:58-59, AB/fineTuneMidiTester.py:34) and
+`predict_with_generate` (AB/fineTune.py:172-174), after setting `generation_config.language` / `task` (AB/fineTune.py:132-134).
+Per step the next tokens come from one libawt op (include/awt.h awt_op_select_tokens: log-softmax, suppression, running beam scores
+and the top 2 x num_beams of a clip's beams in two launches); the native decoder keeps its self-attention keys / values in one
+preallocated cache that beam search reorders with awt_op_kv_gather.  The remaining beam bookkeeping is HF's vectorised algorithm as
+device tensor ops; a step synchronises with the host once (the stop test).
+
+What this module does not build raises: timestamps, inputs longer than one window, sampling, num_return_sequences > 1, num_beams > 8,
+beam search on the torch decoder, prompt_ids.
+"""
+from __future__ import annotations
+
+import copy
+import json
+import os
+from typing import Callable, List, Optional, Sequence
+
+import torch
+
+from . import _lib
+
+MAX_BEAMS = 8
+TASK_IDS = ["translate", "transcribe"]
+# HF's TO_LANGUAGE_CODE (transformers/models/whisper/tokenization_whisper.py): language names -> codes, for `language="english"` etc.
+TO_LANGUAGE_CODE = {
+    "english": "en", "chinese": "zh", "german": "de", "spanish": "es", "russian": "ru", "korean": "ko", "french": "fr", "japanese": "ja",
+    "portuguese": "pt", "turkish": "tr", "polish": "pl", "catalan": "ca", "dutch": "nl", "arabic": "ar", "swedish": "sv", "italian": "it",
+    "indonesian": "id", "hindi": "hi", "finnish": "fi", "vietnamese": "vi", "hebrew": "he", "ukrainian": "uk", "greek": "el", "malay": "ms",
+    "czech": "cs", "romanian": "ro", "danish": "da", "hungarian": "hu", "tamil": "ta", "norwegian": "no", "thai": "th", "urdu": "ur",
+    "croatian": "hr", "bulgarian": "bg", "lithuanian": "lt", "latin": "la", "maori": "mi", "malayalam": "ml", "welsh": "cy", "slovak": "sk",
+    "telugu": "te", "persian": "fa", "latvian": "lv", "bengali": "bn", "serbian": "sr", "azerbaijani": "az", "slovenian": "sl",
+    "kannada": "kn", "estonian": "et", "macedonian": "mk", "breton": "br", "basque": "eu", "icelandic": "is", "armenian": "hy",
+    "nepali": "ne", "mongolian": "mn", "bosnian": "bs", "kazakh": "kk", "albanian": "sq", "swahili": "sw", "galician": "gl",
+    "marathi": "mr", "punjabi": "pa", "sinhala": "si", "khmer": "km", "shona": "sn", "yoruba": "yo", "somali": "so", "afrikaans": "af",
+    "occitan": "oc", "georgian": "ka", "belarusian": "be", "tajik": "tg", "sindhi": "sd", "gujarati": "gu", "amharic": "am",
+    "yiddish": "yi", "lao": "lo", "uzbek": "uz", "faroese": "fo", "haitian creole": "ht", "pashto": "ps", "turkmen": "tk", "nynorsk": "nn",
+    "maltese": "mt", "sanskrit": "sa", "luxembourgish": "lb", "myanmar": "my", "tibetan": "bo", "tagalog": "tl", "malagasy": "mg",
+    "assamese": "as", "tatar": "tt", "hawaiian": "haw", "lingala": "ln", "hausa": "ha", "bashkir": "ba", "javanese": "jw",
+    "sundanese": "su", "cantonese": "yue", "burmese": "my", "valencian": "ca", "flemish": "nl", "haitian": "ht", "letzeburgesch": "lb",
+    "pushto": "ps", "panjabi": "pa", "moldavian": "ro", "moldovan": "ro", "sinhalese": "si", "castilian": "es", "mandarin": "zh",
+}
+
+FIELDS = ("decoder_start_token_id", "pad_token_id", "eos_token_id", "max_length", "num_beams", "length_penalty", "early_stopping",
+          "suppress_tokens", "begin_suppress_tokens", "forced_decoder_ids", "language", "task", "lang_to_id", "task_to_id",
+          "no_timestamps_token_id", "is_multilingual")
+PROMPT_FIELDS = ("lang_to_id", "task_to_id", "no_timestamps_token_id", "forced_decoder_ids")
+
+
+class GenerationConfig:
+    """The fields of `generation_config.json` that Whisper's generate reads; settable attributes, None = absent.  Other keys of a loaded
+    file are kept in `extra` and written back unchanged."""
+
+    def __init__(self, **kw):
+        for f in FIELDS:
+            setattr(self, f, None)
+        self.num_beams, self.length_penalty, self.early_stopping = 1, 1.0, False
+        self.extra = {}
+        for k, v in kw.items():
+            if k in FIELDS:
+                setattr(self, k, v)
+            else:
+                self.extra[k] = v
+
+    @property
+    def whisper_prompt(self) -> bool:
+        """Whether generate builds Whisper's prompt and returns only the generated tokens (any prompt field set)."""
+        return any(getattr(self, f) is not None for f in PROMPT_FIELDS)
+
+    def to_dict(self) -> dict:
+        out = dict(self.extra)
+        out.update({f: getattr(self, f) for f in FIELDS if getattr(self, f) is not None})
+        return out
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "GenerationConfig":
+        return cls(**copy.deepcopy(d))
+
+    @classmethod
+    def from_json_file(cls, path: str) -> "GenerationConfig":
+        with open(path) as f:
+            return cls.from_dict(json.load(f))
+
+    def save(self, directory: str) -> str:
+        path = os.path.join(directory, "generation_config.json")
+        with open(path, "w") as f:
+            json.dump(self.to_dict(), f, indent=2, sort_keys=True)
+        return path
+
+    def __repr__(self):
+        return f"GenerationConfig({self.to_dict()})"
+
+
+def set_language_and_task(gc: GenerationConfig, language, task, is_multilingual) -> None:
+    """`WhisperGenerationMixin._set_language_and_task` (None fields count as absent)."""
+    if is_multilingual is not None:
+        gc.is_multilingual = is_multilingual
+    if gc.is_multilingual is not None and not gc.is_multilingual and (task is not None or language is not None):
+        raise ValueError("Cannot specify `task` or `language` for an English-only model. If the model is intended to be multilingual, pass "
+                         "`is_multilingual=True` to generate, or update the generation config.")
+    if language is not None:
+        if gc.lang_to_id is None:
+            raise ValueError("The generation config has no `lang_to_id`, so the `language` argument is not supported: add Whisper's "
+                             "`lang_to_id` / `task_to_id` / `no_timestamps_token_id` to generation_config.json.")
+        gc.language = language
+    if task is not None:
+        if gc.task_to_id is None:
+            raise ValueError("The generation config has no `task_to_id`, so the `task` argument is not supported.")
+        gc.task = task
+
+
+def _language_to_id(gc: GenerationConfig, language: str) -> int:
+    language = language.lower()
+    if language in gc.lang_to_id:
+        token = language
+    elif language in TO_LANGUAGE_CODE:
+        token = f"<|{TO_LANGUAGE_CODE[language]}|>"
+    elif language in TO_LANGUAGE_CODE.values():
+        token = f"<|{language}|>"
+    else:
+        is_code = len(language) == 2
+        raise ValueError(f"Unsupported language: {language}. Language should be one of:"
+                         f" {list(TO_LANGUAGE_CODE.values()) if is_code else list(TO_LANGUAGE_CODE.keys())}.")
+    if token not in gc.lang_to_id:
+        raise ValueError(f"{token} is not supported by this specific model as it is not in the `generation_config.lang_to_id`. "
+                         "(You should just add it to the generation config)")
+    return int(gc.lang_to_id[token])
+
+
+def retrieve_init_tokens(gc: GenerationConfig, batch_size: int, detect: Optional[Callable[[], Sequence[int]]] = None) -> List[List[int]]:
+    """`WhisperGenerationMixin._retrieve_init_tokens` without timestamps: the per-clip prompt.  `detect()` returns the detected language
+    ids of the clips (called only when the language is unset on a config with `lang_to_id`)."""
+    task, language = gc.task, gc.language
+    init = [gc.decoder_start_token_id]
+    if task is None and language is None and gc.forced_decoder_ids is not None:
+        forced = [list(f) for f in gc.forced_decoder_ids]
+        if forced and forced[0][0] == 1:
+            i = 1
+            while forced and forced[0][0] == i:
+                init.append(forced[0][1])
+                forced = forced[1:]
+                i += 1
+            if forced:
+                raise ValueError(f"You are using token ids in `forced_decoder_ids` that do not seem to correctly follow the prompt pattern of "
+                                 f"Whisper. Make sure that {forced} has an entry for all indices >= 1 and < {forced[0][0]}.")
+    lang_undefined = len(init) <= 1 or init[1] is None
+    if isinstance(language, (list, tuple)):
+        if any(l is None for l in language):
+            raise TypeError("Expected `language` to be `None`, a single string (e.g. `'en'`), or a list of strings with length equal to the "
+                            "batch size (e.g. `('en', 'fr')` for a batch size of 2). Got a list containing `None`.")
+        if len(language) != batch_size:
+            raise ValueError("When passing a list of languages, the length of the list must match the batch size. "
+                             f"Expected length of {batch_size}, but got {len(language)} languages.")
+        languages = list(language)
+    elif language is None:
+        languages = [None] * batch_size
+    else:
+        languages = [language]
+    inits = [list(init) for _ in languages]
+    lang_ids = None
+    if language is not None:
+        lang_ids = [_language_to_id(gc, l) for l in languages]
+    elif gc.lang_to_id is not None and lang_undefined:
+        if detect is None:
+            raise ValueError("language detection needs the input features")
+        lang_ids = [int(t) for t in detect()]
+    if lang_ids is not None:
+        for i in range(len(inits)):
+            if len(inits[i]) > 1:
+                inits[i][1] = lang_ids[i]
+            else:
+                inits[i].append(lang_ids[i])
+    for i in range(len(inits)):
+        if task is not None:
+            if task not in TASK_IDS:
+                raise ValueError(f"The `{task}` task is not supported. The task should be one of `{TASK_IDS}`")
+            task_id = int(gc.task_to_id[task])
+            inits[i].append(task_id)                   # (HF's replace_or_add after this append finds the id and changes nothing)
+        elif language is not None and gc.task_to_id is not None:
+            if not any(int(t) in inits[i] for t in gc.task_to_id.values()):
+                inits[i].append(int(gc.task_to_id["transcribe"]))
+        if gc.no_timestamps_token_id is not None and inits[i][-1] != gc.no_timestamps_token_id:
+            inits[i].append(int(gc.no_timestamps_token_id))
+        inits[i] = [int(t) for t in inits[i] if t is not None]
+    if len(inits) == 1 and batch_size > 1:
+        inits = inits * batch_size
+    return inits
+
+
+# ------------------------------------------------------------------------------------------------ device ops
+def banned_bits(tokens, vocab: int, device, invert: bool = False) -> Optional[torch.Tensor]:
+    """Bit set over the vocabulary ((vocab + 31) / 32 int32 words) with the given tokens set (invert: every other token); None when empty."""
+    toks = sorted({int(t) for t in (tokens or []) if 0 <= int(t) < vocab})
+    if not toks and not invert:
+        return None
+    mask = torch.zeros(((vocab + 31) // 32) * 32, dtype=torch.bool)
+    mask[toks] = True
+    if invert:
+        mask[:vocab] = ~mask[:vocab]
+    words = (mask.view(-1, 32).to(torch.int64) << torch.arange(32, dtype=torch.int64)).sum(dim=1)
+    words = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+    return words.to(device)
+
+
+def select_tokens(logits: torch.Tensor, vocab: int, beams: int = 1, banned: Optional[torch.Tensor] = None, beam_scores: Optional[torch.Tensor] = None,
+                  log_softmax: bool = False, k: int = 1):
+    """awt_op_select_tokens on rows of padded logits (a [rows, >= vocab] fp32 view with unit column stride): (scores [clips, k],
+    tokens int64 [clips, k], parents int32 [clips, k])."""
+    rows = logits.shape[0]
+    ld = logits.stride(0) if rows > 1 else max(logits.shape[1], vocab + (-vocab) % 4)
+    if logits.dtype != torch.float32 or logits.stride(1) != 1 or not logits.is_cuda:
+        raise ValueError("select_tokens needs fp32 device logits with unit column stride")
+    dev = logits.device
+    clips = rows // beams if beams > 0 else 0
+    scores = torch.empty((max(clips, 1), k), dtype=torch.float32, device=dev)
+    tokens = torch.empty((max(clips, 1), k), dtype=torch.int64, device=dev)
+    parents = torch.empty((max(clips, 1), k), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_select_tokens_workspace_bytes(rows, vocab, k), dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.awt_op_select_tokens(_lib.ctx(dev), logits.data_ptr(), int(ld), rows, int(vocab), int(beams), _lib.ptr(banned), _lib.ptr(beam_scores),
+                                          int(bool(log_softmax)), int(k), _lib.ptr(scores), _lib.ptr(tokens), _lib.ptr(parents), _lib.ptr(ws), ws.numel(),
+                                          _lib.stream_handle()))
+    return scores, tokens, parents
+
+
+# ------------------------------------------------------------------------------------------------ decoders behind one step interface
+class _NativeSteps:
+    """The native decoder: preallocated self-attention cache, cross-attention keys / values of the B clips shared by their beams."""
+
+    def __init__(self, dec, cross: torch.Tensor, S: int, B: int, Tmax: int):
+        self.dec, self.cross, self.S, self.B, self.Tmax = dec, cross, S, B, Tmax
+        self.vocab = dec.vocab
+        self.cache = None
+        self.group = 1
+
+    def prefill(self, ids: torch.Tensor) -> torch.Tensor:
+        from .native_decoder import DecodeCache
+        self.cache = DecodeCache(self.dec.n_layers, ids.shape[0], self.Tmax, self.dec.d, ids.device)
+        return self.dec.decode_logits(ids, self.cross, self.S, self.cache)
+
+    def expand(self, beams: int) -> None:
+        """B-row prompt cache -> B x beams rows (parent r / beams), double-buffered for the per-step reorder."""
+        from .native_decoder import DecodeCache
+        big = DecodeCache(self.dec.n_layers, self.B * beams, self.Tmax, self.dec.d, self.cache.buf.device, double=True)
+        parent = torch.arange(self.B * beams, device=big.buf.device, dtype=torch.int32) // beams
+        big.gather(parent, src=self.cache)
+        self.cache, self.group = big, beams
+
+    def reorder(self, parent: torch.Tensor) -> None:
+        self.cache.gather(parent)
+
+    def step(self, tokens: torch.Tensor) -> torch.Tensor:
+        return self.dec.decode_logits(tokens[:, None], self.cross, self.S, self.cache, cross_group=self.group)
+
+
+class _TorchSteps:
+    """The stock-PyTorch decoder (native_decoder=False): its own per-layer caches; logits copied into a 4-aligned pitch for the kernel."""
+
+    def __init__(self, dec, hidden: torch.Tensor, cross, autocast):
+        self.dec, self.hidden, self.cross, self.autocast = dec, hidden, cross, autocast
+        self.vocab = dec.embed_tokens.weight.shape[0]
+        self.caches = [dict() for _ in dec.layers]
+        self.pos = 0
+        if self.cross is None:
+            self.cross = [(l.encoder_attn.k_proj(hidden), l.encoder_attn.v_proj(hidden)) for l in dec.layers]
+
+    def _logits(self, ids):
+        with torch.autocast("cuda", dtype=self.autocast or torch.bfloat16, enabled=self.autocast is not None):
+            lg = self.dec(ids, self.hidden, cross=self.cross, caches=self.caches, position_offset=self.pos)
+        self.pos += ids.shape[1]
+        last = lg[:, -1].float()
+        out = torch.empty((last.shape[0], self.vocab + (-self.vocab) % 4), dtype=torch.float32, device=last.device)
+        out[:, : self.vocab].copy_(last)
+        return out
+
+    def prefill(self, ids):
+        return self._logits(ids)
+
+    def step(self, tokens):
+        return self._logits(tokens[:, None])
+
+
+# ------------------------------------------------------------------------------------------------ decoding loops
+def greedy(steps, init: torch.Tensor, max_len: int, eos_id: Optional[int], pad_id: int, suppress, begin_suppress) -> torch.Tensor:
+    """`GenerationMixin._sample` without sampling: [B, <= max_len] ids starting with the prompt; finished rows continue with pad."""
+    B, P = init.shape
+    dev = init.device
+    vocab = steps.vocab
+    ban = banned_bits(suppress, vocab, dev)
+    ban0 = banned_bits(list(suppress or []) + list(begin_suppress or []), vocab, dev)
+    ids = init
+    done = torch.zeros(B, dtype=torch.bool, device=dev)
+    if ids.shape[1] >= max_len:
+        return ids
+    logits = steps.prefill(init)
+    first = True
+    while True:
+        _, nxt, _ = select_tokens(logits, vocab, banned=ban0 if first else ban)
+        nxt = nxt[:, 0]
+        first = False
+        nxt = torch.where(done, torch.full_like(nxt, pad_id), nxt)
+        ids = torch.cat([ids, nxt[:, None]], dim=1)
+        if eos_id is not None:
+            done = done | (nxt == eos_id)
+        if ids.shape[1] >= max_len or bool(done.all()):
+            return ids
+        logits = steps.step(nxt)
+
+
+def beam_search(steps, init: torch.Tensor, max_len: int, eos_id: Optional[int], pad_id: Optional[int], suppress, begin_suppress, num_beams: int,
+                length_penalty: float, early_stopping):
+    """`GenerationMixin._beam_search` (HF 5.15, vectorised) on device tensors: (sequences [B, P + generated], sequences_scores [B], generated
+    length of each returned hypothesis [B], EOS included)."""
+    B, P = init.shape
+    dev = init.device
+    nb, vocab = num_beams, steps.vocab
+    n_eos = 0 if eos_id is None else 1
+    k = max(2, 1 + n_eos) * nb
+    top_mask = torch.cat([torch.ones(nb, dtype=torch.bool), torch.zeros(k - nb, dtype=torch.bool)]).to(dev)
+    fill = pad_id if pad_id else (eos_id if eos_id is not None else -1)      # HF: `pad_token_id or eos_token_id[0]`
+    ban = banned_bits(suppress, vocab, dev)
+    ban0 = banned_bits(list(suppress or []) + list(begin_suppress or []), vocab, dev)
+    running_sequences = torch.full((B, nb, max_len), fill, dtype=torch.int64, device=dev)
+    running_sequences[:, :, :P] = init[:, None, :]
+    sequences = running_sequences.clone()
+    running_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
+    running_scores[:, 1:] = -1e9
+    beam_scores = torch.full((B, nb), -1e9, dtype=torch.float32, device=dev)
+    finished = torch.zeros((B, nb), dtype=torch.bool, device=dev)
+    finished_len = torch.zeros((B, nb), dtype=torch.int64, device=dev)          # generated tokens of each kept hypothesis (HF: beam_indices >= 0)
+    heur_unsat = torch.ones((B, 1), dtype=torch.bool, device=dev)
+    batch_offset = torch.arange(B, device=dev)[:, None] * nb
+    cur_len = P
+    logits = steps.prefill(init)                                                # [B, Np]: every beam of a clip sees the same prompt
+    logits = logits.repeat_interleave(nb, dim=0) if nb > 1 else logits.contiguous()
+    first = True
+    while True:
+        topk_log_probs, topk_ids, topk_parent = select_tokens(logits, vocab, nb, ban0 if first else ban, running_scores.reshape(-1), True, k)
+        topk_parent = topk_parent.to(torch.int64)
+        topk_sequences = torch.take_along_dim(running_sequences, topk_parent[:, :, None], dim=1)
+        topk_sequences[:, :, cur_len] = topk_ids
+        hits = torch.full_like(topk_ids, cur_len + 1 >= max_len, dtype=torch.bool)
+        if eos_id is not None:
+            hits = hits | (topk_ids == eos_id)
+        # running beams of the next step
+        topk_running = topk_log_probs + hits.to(torch.float32) * -1.0e9
+        nxt = torch.topk(topk_running, k=nb)[1]
+        running_sequences = torch.take_along_dim(topk_sequences, nxt[:, :, None], dim=1)
+        running_scores = torch.take_along_dim(topk_running, nxt, dim=1)
+        parent = (torch.take_along_dim(topk_parent, nxt, dim=1) + batch_offset).reshape(-1)
+        # finished hypotheses
+        did = hits & top_mask[None, :]
+        lp = topk_log_probs / ((cur_len + 1 - P) ** length_penalty)
+        full = torch.all(finished, dim=-1, keepdim=True) & (early_stopping is True)
+        lp = lp + full.to(torch.float32) * -1.0e9
+        lp = lp + (~heur_unsat).to(torch.float32) * -1.0e9
+        lp = lp + (~did) * -1.0e9
+        merged_idx = torch.topk(torch.cat([beam_scores, lp], dim=1), k=nb)[1]
+        sequences = torch.take_along_dim(torch.cat([sequences, topk_sequences], dim=1), merged_idx[:, :, None], dim=1)
+        beam_scores = torch.take_along_dim(torch.cat([beam_scores, lp], dim=1), merged_idx, dim=1)
+        finished_len = torch.take_along_dim(torch.cat([finished_len, torch.full_like(topk_ids, cur_len + 1 - P)], dim=1), merged_idx, dim=1)
+        finished = torch.take_along_dim(torch.cat([finished, did], dim=1), merged_idx, dim=1)
+        cur_len += 1
+        # early-stop heuristic (HF _check_early_stop_heuristic)
+        best_len = (max_len - P) if (early_stopping == "never" and length_penalty > 0.0) else (cur_len - P)
+        best_running = running_scores[:, :1] / (best_len ** length_penalty)
+        worst_finished = torch.where(finished, torch.min(beam_scores, dim=1, keepdim=True)[0], -1.0e9)
+        heur_unsat = heur_unsat & torch.any(best_running > worst_finished, dim=-1, keepdim=True)
+        go = torch.any(heur_unsat) & ~(torch.all(finished) & (early_stopping is True)) & ~torch.all(hits)
+        if not bool(go):
+            break
+        if first:
+            steps.expand(nb)            # every beam of a clip holds the same prompt, so the first reorder is the expansion (parent r / nb)
+        else:
+            steps.reorder(parent)
+        first = False
+        logits = steps.step(running_sequences[:, :, cur_len - 1].reshape(-1))
+    gen = int(finished_len[:, 0].max())                                        # HF: generated length of the longest returned hypothesis
+    return sequences[:, 0, : P + gen], beam_scores[:, 0], finished_len[:, 0]
+
+
+def strip_prompt(seqs: torch.Tensor, P: int, pad_id: Optional[int], eos_id: Optional[int]) -> torch.Tensor:
+    """WhisperGenerationMixin's short-form return: prompt removed; per clip trailing padding (HF counts every pad of the row, one less when
+    pad == eos) and a final EOS dropped; right-padded with pad_token_id to the longest clip."""
+    rows = []
+    for r in seqs[:, P:].cpu():
+        if r.numel() and pad_id is not None and int(r[-1]) == pad_id:
+            n = int((r == pad_id).sum())
+            if pad_id == eos_id:
+                n -= 1
+            if n:
+                r = r[:-n]
+        if r.numel() and eos_id is not None and int(r[-1]) == eos_id:
+            r = r[:-1]
+        rows.append(r)
+    width = max((len(r) for r in rows), default=0)
+    out = torch.full((len(rows), width), pad_id if pad_id is not None else 0, dtype=torch.int64)
+    for i, r in enumerate(rows):
+        out[i, : len(r)] = r
+    return out.to(seqs.device)

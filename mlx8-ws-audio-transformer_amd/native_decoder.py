@@ -330,6 +330,48 @@ def cross_entropy(logits, labels, vocab):
     return loss, dlogits
 
 
+class DecodeCache:
+    """Self-attention keys / values of incremental decoding, preallocated once per generate call: [layers, rows, Tmax, 2 d] (keys in the first
+    d columns).  A step appends its L new positions in place at T; beam search reorders rows into a second buffer of the same shape with
+    awt_op_kv_gather (`gather`) and swaps the two."""
+
+    def __init__(self, layers: int, rows: int, Tmax: int, d: int, device, double: bool = False):
+        self.layers, self.rows, self.Tmax, self.d, self.T = layers, rows, Tmax, d, 0
+        self.buf = torch.empty((layers, rows, Tmax, 2 * d), dtype=torch.float32, device=device)
+        self.spare = torch.empty_like(self.buf) if double else None
+
+    def attend(self, i: int, qkv: torch.Tensor, L: int) -> torch.Tensor:
+        d, T = self.d, self.T + L
+        if T > self.Tmax:
+            raise ValueError(f"decode cache holds {self.Tmax} positions, step needs {T}")
+        self.buf[i, :, self.T:T].copy_(qkv.view(self.rows, L, 3 * d)[:, :, d:])
+        c = self.buf[i]
+        o = torch.empty((self.rows * L, d), dtype=torch.float32, device=qkv.device)
+        with torch.cuda.device(qkv.device):
+            _lib.check(_lib.lib().awt_op_attention_cached(_ctx(qkv), _lib.ptr(qkv), 3 * d, c.data_ptr(), c.data_ptr() + 4 * d, 2 * d, self.Tmax * 2 * d,
+                                                          _lib.ptr(o), d, self.rows, d // 64, L, T, _lib.stream_handle()))
+        return o
+
+    def gather(self, parent: torch.Tensor, src: Optional["DecodeCache"] = None) -> None:
+        """Row r of this cache <- row parent[r] (int32, on the device) of `src` (default: this cache itself, through the spare buffer)."""
+        src_buf, src_rows = (self.buf, self.rows) if src is None else (src.buf, src.rows)
+        dst = self.spare if src is None else self.buf
+        T = self.T if src is None else src.T
+        kv_gather(src_buf, dst, parent, self.layers, src_rows, self.rows, T, self.Tmax, 2 * self.d)
+        if src is None:
+            self.buf, self.spare = self.spare, self.buf
+        else:
+            self.T = src.T
+
+
+def kv_gather(src: torch.Tensor, dst: torch.Tensor, parent: torch.Tensor, layers: int, src_rows: int, dst_rows: int, T: int, Tmax: int, width: int) -> None:
+    """dst[l, r, :T] = src[l, parent[r], :T] over [layers, rows, Tmax, width] buffers (include/awt.h awt_op_kv_gather)."""
+    parent = parent.to(torch.int32).contiguous()
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.lib().awt_op_kv_gather(_ctx(src), _lib.ptr(src), _lib.ptr(dst), _lib.ptr(parent), layers, src_rows, dst_rows, T, Tmax, width,
+                                               _lib.stream_handle()))
+
+
 class _Leaf(nn.Module):
     pass
 
@@ -493,12 +535,16 @@ class NativeWhisperDecoder(nn.Module):
                                                _lib.ptr(x), B * L, L, self.d, int(position_offset), self.vocab, _lib.stream_handle()))
         return x
 
-    def _run(self, ids: torch.Tensor, kv: torch.Tensor, S: int, save: Optional[list], caches=None, position_offset: int = 0) -> torch.Tensor:
+    def _run(self, ids: torch.Tensor, kv: torch.Tensor, S: int, save: Optional[list], caches=None, position_offset: int = 0,
+             cross_group: int = 1) -> torch.Tensor:
         """Token ids [B, L] + cross keys / values (the `cross_kv` tensor, or an `_AbsorbedCross` over the encoder states) -> final-LayerNorm
-        input x [B * L, d] (saving what the backward needs in `save`)."""
+        input x [B * L, d] (saving what the backward needs in `save`).  `caches`: a `DecodeCache` (generate) or per-layer dicts.
+        cross_group: rows of ids per clip of `kv` (beam search: the beams of a clip attend to that clip's keys / values as its query rows)."""
         pk = self.packed()
         B, L = ids.shape
         d, H, nl = self.d, self.heads, self.n_layers
+        if isinstance(caches, DecodeCache):
+            position_offset = caches.T
         x = self._embed(ids, position_offset)
         for i, (lay, p) in enumerate(zip(self.layers, pk["layers"])):
             h = layernorm(x, lay.self_attn_layer_norm.weight, lay.self_attn_layer_norm.bias)
@@ -511,6 +557,8 @@ class NativeWhisperDecoder(nn.Module):
                     qkv[:, col: col + d] += delta
             if caches is None:
                 a, lse = attention_small((qkv, 0), 3 * d, (qkv, d), 3 * d, (qkv, 2 * d), 3 * d, B, H, L, L, True, 0, save is not None)
+            elif isinstance(caches, DecodeCache):                                       # preallocated cache: append in place, attend over T positions
+                a, lse = caches.attend(i, qkv, L), None
             else:                                                                       # incremental decoding: keys / values of all positions so far
                 c = caches[i]
                 kvn = qkv.view(B, L, 3 * d)[:, :, d:]
@@ -527,7 +575,8 @@ class NativeWhisperDecoder(nn.Module):
             if isinstance(kv, _AbsorbedCross):
                 a2, lse2 = kv.attend(i, q, L)                                            # lse2: (q~, P, context) for the backward
             else:
-                a2, lse2 = attention_small((q, 0), d, (kv, 2 * i * d), 2 * nl * d, (kv, (2 * i + 1) * d), 2 * nl * d, B, H, L, S, False, 0, save is not None)
+                a2, lse2 = attention_small((q, 0), d, (kv, 2 * i * d), 2 * nl * d, (kv, (2 * i + 1) * d), 2 * nl * d, B // cross_group, H, L * cross_group, S,
+                                           False, 0, save is not None)
             x2 = p["co"].forward(a2, resid=x1)
             h3 = layernorm(x2, lay.final_layer_norm.weight, lay.final_layer_norm.bias)
             f = p["fc1"].forward(h3)
@@ -535,6 +584,8 @@ class NativeWhisperDecoder(nn.Module):
             if save is not None:
                 save.append((x, qkv, a, lse, x1, q, a2, lse2, x2, f, us))
             x = x3
+        if isinstance(caches, DecodeCache):
+            caches.T += L
         return x
 
     def forward(self, input_ids: torch.Tensor, encoder_hidden_states: torch.Tensor, native_precision: Optional[str] = None, cross=None, caches=None,
@@ -547,6 +598,16 @@ class NativeWhisperDecoder(nn.Module):
             xf = layernorm(x, self.layer_norm.weight, self.layer_norm.bias)
             logits = self.packed()["vocab"].forward(xf)
             return logits.view(B, L, -1)[:, :, : self.vocab]
+
+    def decode_logits(self, ids: torch.Tensor, cross: torch.Tensor, S: int, cache: "DecodeCache", cross_group: int = 1) -> torch.Tensor:
+        """One incremental decoding step for generate: ids [rows, L] at positions cache.T.. -> padded logits of the LAST position, a [rows, Np]
+        view of the vocabulary projection's output (row pitch L * Np; columns >= vocab are padding)."""
+        with torch.no_grad():
+            rows, L = ids.shape
+            x = self._run(ids, cross, S, None, cache, cross_group=cross_group)
+            xf = layernorm(x, self.layer_norm.weight, self.layer_norm.bias)
+            logits = self.packed()["vocab"].forward(xf)
+            return logits.view(rows, L, -1)[:, L - 1]
 
     def loss(self, decoder_input_ids: torch.Tensor, labels: torch.Tensor, encoder_hidden_states: torch.Tensor):
         """(loss, logits [B, L, vocab]): differentiable w.r.t. `encoder_hidden_states` only (the decoder is frozen)."""

@@ -87,20 +87,21 @@ def load_clip_16k(path: Union[str, os.PathLike]) -> torch.Tensor:
 
 
 @torch.no_grad()
-def transcribe_clips(waveforms: Sequence[Any], model, processor: WhisperProcessor, max_length: int = 225) -> List[str]:
-    """A batch of mono 16 kHz waveforms -> stripped transcriptions: `processor` -> `model.generate` -> `processor.batch_decode`."""
+def transcribe_clips(waveforms: Sequence[Any], model, processor: WhisperProcessor, max_length: int = 225, **generate_kwargs) -> List[str]:
+    """A batch of mono 16 kHz waveforms -> stripped transcriptions: `processor` -> `model.generate` -> `processor.batch_decode`.
+    generate_kwargs (num_beams, language, task, ...) go to `model.generate`."""
     inputs = processor([w.numpy() if hasattr(w, "numpy") else w for w in waveforms], sampling_rate=16000, return_tensors="pt")
     dev = model.encoder.device
-    generated_ids = model.generate(inputs["input_features"].to(dev), max_length=max_length)
+    generated_ids = model.generate(inputs["input_features"].to(dev), max_length=max_length, **generate_kwargs)
     return [t.strip() for t in processor.batch_decode(generated_ids.cpu(), skip_special_tokens=True)]
 
 
 def transcribe_audio_FT(input_path, results: List[dict], model, processor: WhisperProcessor, actual: str = "Asmoranomardicadaistinaculdacar",
-                        write_text: bool = True, max_length: int = 225) -> str:
+                        write_text: bool = True, max_length: int = 225, **generate_kwargs) -> str:
     """wavToWhisper.py:44-70 with the model and processor passed in: transcribes one file, writes `<stem>.text` and appends the
     reference's row {"Path", "Transcription", "Actual"} to `results`."""
     input_path = Path(input_path)
-    transcription = transcribe_clips([load_clip_16k(input_path)], model, processor, max_length)[0]
+    transcription = transcribe_clips([load_clip_16k(input_path)], model, processor, max_length, **generate_kwargs)[0]
     if write_text:
         with open(input_path.with_suffix(".text"), "w") as f:
             f.write(f"{input_path.name}: {transcription}\n")
@@ -109,7 +110,7 @@ def transcribe_audio_FT(input_path, results: List[dict], model, processor: Whisp
 
 
 def evaluate_csv(dataset_csv, model, processor: WhisperProcessor, out_csv=None, batch_size: int = 16, max_length: int = 225,
-                 root: Optional[str] = None) -> List[Dict[str, str]]:
+                 root: Optional[str] = None, **generate_kwargs) -> List[Dict[str, str]]:
     """fineTuneMidiTester.py:16-49: every row (WavPath, Labels) of `dataset_csv` -> {"WavPath", "Predicted", "Actual"}; missing files are
     reported and skipped like the reference does.  Clips go through the model `batch_size` at a time (the reference's B = 1 loop
     is `batch_size=1`); `out_csv` writes `midiDatasetResults.csv`."""
@@ -124,7 +125,7 @@ def evaluate_csv(dataset_csv, model, processor: WhisperProcessor, out_csv=None, 
     midi_results: List[Dict[str, str]] = []
     for i in range(0, len(todo), max(1, batch_size)):
         chunk = todo[i: i + max(1, batch_size)]
-        texts = transcribe_clips([load_clip_16k(p) for p, _ in chunk], model, processor, max_length)
+        texts = transcribe_clips([load_clip_16k(p) for p, _ in chunk], model, processor, max_length, **generate_kwargs)
         for (p, actual), pred in zip(chunk, texts):
             midi_results.append({"WavPath": str(p), "Predicted": pred, "Actual": actual})
     if out_csv is not None:
