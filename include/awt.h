@@ -68,6 +68,12 @@ int awt_logmel_whisper(awt_ctx* c, const void* pcm, int pcm_is_i16, int64_t pcm_
 int awt_logmel_whisper_mels(awt_ctx* c, const void* pcm, int pcm_is_i16, int64_t pcm_stride, const int32_t* n_valid,
                             int max_valid, int B, int n_frames_out, int n_mels, float* out, void* workspace, size_t ws_bytes,
                             void* stream);
+/* Long-form input (`processor(audio, truncation=False, padding="longest")`): the clips zero-padded to n_signal samples (the longest
+ * clip), reflect padding only beyond n_signal, the last STFT frame dropped, each clip's max over all its frames.  out is
+ * [B, n_mels, n_signal / 160] (any frame count, 4-byte aligned); n_signal > 200. */
+int awt_logmel_whisper_signal(awt_ctx* c, const void* pcm, int pcm_is_i16, int64_t pcm_stride, const int32_t* n_valid,
+                              int max_valid, int B, int n_signal, int n_mels, float* out, void* workspace, size_t ws_bytes,
+                              void* stream);
 
 /* UrbanSound log-mel (K15).  Stands behind `torch.log(mel_spectrogram(waveform) + 1e-6)`:
  *   /root/reference/.charles/spectrogram.py:79-87,160-162 (torchaudio MelSpectrogram: periodic Hann(n_fft),
@@ -341,6 +347,25 @@ size_t awt_select_tokens_workspace_bytes(int rows, int vocab, int k);
 int awt_op_select_tokens(awt_ctx* c, const float* logits, int ld, int rows, int vocab, int beams, const uint32_t* banned, const float* beam_scores,
                          int log_softmax, int k, float* top_scores, int64_t* top_tokens, int32_t* top_parent, void* workspace, size_t ws_bytes,
                          void* stream);
+/* awt_op_select_tokens with Whisper's timestamp rules (HF WhisperTimeStampLogitsProcessor) applied after `banned`, still two launches.
+ * Per row (its token history: history + row * hist_ld, tokens [begin, cur_len) generated so far; timestamp_begin = no_timestamps + 1):
+ * <|notimestamps|> banned; last token a timestamp and the one before it too (or none before it): timestamps banned; last a timestamp,
+ * the one before not: [0, eos) banned; timestamps below the last timestamp banned (below last + 1 unless the last two are text then
+ * timestamp); at cur_len == begin [0, timestamp_begin) and, when max_initial_timestamp_index >= 0, columns above timestamp_begin +
+ * max_initial_timestamp_index banned; then, when logsumexp(timestamp columns) > max(text columns) of the banned row (no NaN), the text
+ * columns become -inf.  log_softmax stays over the unbanned row.  rules = NULL is awt_op_select_tokens.  Candidates of score -inf come
+ * in no specified order.  workspace: awt_select_tokens_ts_workspace_bytes. */
+typedef struct awt_ts_rules {
+  const int64_t* history;             /* device int64 [rows, hist_ld] */
+  int64_t hist_ld;
+  int begin, cur_len;
+  int eos_token_id, no_timestamps_token_id;
+  int max_initial_timestamp_index;    /* < 0: none */
+} awt_ts_rules;
+size_t awt_select_tokens_ts_workspace_bytes(int rows, int vocab, int k);
+int awt_op_select_tokens_ts(awt_ctx* c, const float* logits, int ld, int rows, int vocab, int beams, const uint32_t* banned, const float* beam_scores,
+                            int log_softmax, int k, const awt_ts_rules* rules, float* top_scores, int64_t* top_tokens, int32_t* top_parent,
+                            void* workspace, size_t ws_bytes, void* stream);
 /* dst[l, r, t, :] = src[l, parent[r], t, :] for l < layers, r < dst_rows, t < T of caches laid out [layers, rows, Tmax, width]
  * (src with src_rows rows, dst with dst_rows; width % 4 == 0; src != dst).  One launch.  A parent outside [0, src_rows) leaves its
  * destination row as it was.  Beam reorder (parent = surviving beams' parents) and the B -> B x beams expansion (parent = r / beams). */

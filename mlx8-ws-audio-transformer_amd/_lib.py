@@ -46,6 +46,7 @@ _SIGNATURES = {
     "awt_logmel_workspace_bytes": (_sz, [_i]),
     "awt_logmel_whisper": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "awt_logmel_whisper_mels": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "awt_logmel_whisper_signal": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "awt_logmel_generic": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp]),
     "awt_logmel_prepare": (_i, [_vp, _i, _i, _f, _f, _i, _i]),
     "awt_resample_prepare": (_i, [_vp, _i, _i]),
@@ -107,6 +108,8 @@ _SIGNATURES = {
     "awt_op_attention_cached": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i, _vp]),
     "awt_select_tokens_workspace_bytes": (_sz, [_i, _i, _i]),
     "awt_op_select_tokens": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "awt_select_tokens_ts_workspace_bytes": (_sz, [_i, _i, _i]),
+    "awt_op_select_tokens_ts": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "awt_op_kv_gather": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "awt_tuning_set": (_i, [C.c_char_p, _i]),
     "awt_prof_enable": (_i, [_vp, _i]),

@@ -158,6 +158,12 @@ extern "C" int awt_logmel_whisper_mels(awt_ctx* c, const void* pcm, int pcm_is_i
   return logmel_whisper_impl(c, pcm, pcm_is_i16, pcm_stride, n_valid, max_valid, B, n_frames_out, n_mels, out, workspace, ws_bytes,
                              (hipStream_t)stream);
 }
+extern "C" int awt_logmel_whisper_signal(awt_ctx* c, const void* pcm, int pcm_is_i16, int64_t pcm_stride, const int32_t* n_valid,
+                                         int max_valid, int B, int n_signal, int n_mels, float* out, void* workspace, size_t ws_bytes,
+                                         void* stream) {
+  return logmel_whisper_impl(c, pcm, pcm_is_i16, pcm_stride, n_valid, max_valid, B, 0, n_mels, out, workspace, ws_bytes, (hipStream_t)stream,
+                             n_signal);
+}
 extern "C" int awt_logmel_generic(awt_ctx* c, const float* pcm, int64_t pcm_stride, int B, int n_samples, int sample_rate,
                                   int n_fft, int hop, int n_mels, float f_min, float f_max, float log_eps, float* out,
                                   void* stream) {

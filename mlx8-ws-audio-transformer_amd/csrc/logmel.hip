@@ -187,6 +187,21 @@ __global__ __launch_bounds__(256) void logmel_finalize_kernel(float* out, const 
   }
 }
 
+// The same for any T_out (truncation=False, padding="longest": n_signal / 160 frames), one value per lane.
+__global__ __launch_bounds__(256) void logmel_finalize_rows_kernel(float* out, const unsigned* clip_max, const int32_t* n_valid,
+                                                                   int max_valid, int L, int n_fft, int hop, int n_mels, int T_out) {
+  const int b = blockIdx.y;
+  int nv = n_valid ? n_valid[b] : max_valid;
+  nv = nv < L ? nv : L;
+  const int n_live = live_frames(nv, n_fft, hop, T_out);
+  const float thr = float_from_key(clip_max[b]) - 8.0f;
+  float* o = out + (int64_t)b * n_mels * T_out;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_mels * T_out; i += gridDim.x * blockDim.x) {
+    const float v = (i % T_out) < n_live ? o[i] : -10.f;
+    o[i] = (fmaxf(v, thr) + 4.0f) * 0.25f;
+  }
+}
+
 // ------------------------------------------------------------------------------------------ host-side tables
 double hz_to_mel(double f, bool slaney) {
   if (!slaney) return 2595.0 * log10(1.0 + f / 700.0);                  // HF:audio_utils.py:466-467
@@ -346,9 +361,15 @@ int logmel_prepare_impl(awt_ctx* c, int n_fft, int n_mels, double f_min, double 
 int resample_prepare_impl(awt_ctx* c, int sr_in, int sr_out);
 
 int logmel_whisper_impl(awt_ctx* c, const void* pcm, int pcm_is_i16, int64_t pcm_stride, const int32_t* n_valid,
-                        int max_valid, int B, int n_frames_out, int n_mels, float* out, void* workspace, size_t ws_bytes, hipStream_t s) {
+                        int max_valid, int B, int n_frames_out, int n_mels, float* out, void* workspace, size_t ws_bytes, hipStream_t s,
+                        int n_signal) {
   AWT_REQUIRE(c && pcm && out && workspace, AWT_ERR_INVALID, "logmel_whisper: null argument");
-  AWT_REQUIRE(B > 0 && n_frames_out > 0 && n_frames_out % 4 == 0, AWT_ERR_INVALID, "logmel_whisper: B > 0 and n_frames_out % 4 == 0 required");
+  if (n_signal > 0) {                   // explicit signal length (reflected at its end): n_signal / 160 frames, any count
+    AWT_REQUIRE(n_signal > 200, AWT_ERR_INVALID, "logmel_whisper: the signal must be longer than n_fft / 2 = 200 samples (reflect padding)");
+    n_frames_out = n_signal / 160;
+  }
+  AWT_REQUIRE(B > 0 && n_frames_out > 0 && (n_signal > 0 || n_frames_out % 4 == 0), AWT_ERR_INVALID,
+              "logmel_whisper: B > 0 and n_frames_out % 4 == 0 required");
   AWT_REQUIRE(max_valid >= 0 && (pcm_stride >= max_valid || B == 1), AWT_ERR_INVALID, "logmel_whisper: pcm_stride < max_valid");
   AWT_REQUIRE(ws_bytes >= awt_logmel_workspace_bytes(B), AWT_ERR_WORKSPACE, "logmel_whisper: workspace too small");
   AWT_REQUIRE(((uintptr_t)out & 15) == 0, AWT_ERR_INVALID, "logmel_whisper: out must be 16-byte aligned");
@@ -359,7 +380,7 @@ int logmel_whisper_impl(awt_ctx* c, const void* pcm, int pcm_is_i16, int64_t pcm
   rc = get_mel(c, n_fft / 2 + 1, n_mels, 0.0, 8000.0, 16000, true, &mt); if (rc) return rc;
   LogmelParams p{};
   p.pcm = pcm; p.pcm_is_i16 = pcm_is_i16; p.pcm_stride = pcm_stride; p.n_valid = n_valid; p.max_valid = max_valid;
-  p.L = n_frames_out * hop; p.n_fft = n_fft; p.hop = hop; p.n_bins = n_fft / 2 + 1; p.n_bin_tiles = bt.n_bin_tiles;
+  p.L = n_signal > 0 ? n_signal : n_frames_out * hop; p.n_fft = n_fft; p.hop = hop; p.n_bins = n_fft / 2 + 1; p.n_bin_tiles = bt.n_bin_tiles;
   p.nbp = bt.n_bin_tiles * 16 + 1; p.n_mels = n_mels; p.T_out = n_frames_out; p.basis = bt.basis;
   p.mel_start = mt.start; p.mel_count = mt.count; p.mel_off = mt.off; p.mel_w = mt.w;
   p.log_mode = 0; p.log_eps = 0.0; p.out = out; p.clip_max = reinterpret_cast<unsigned*>(workspace);
@@ -369,10 +390,17 @@ int logmel_whisper_impl(awt_ctx* c, const void* pcm, int pcm_is_i16, int64_t pcm
   hipLaunchKernelGGL(logmel_init_max_kernel, dim3((B + 255) / 256), dim3(256), 0, s, p.clip_max, B);
   AWT_HIP_CHECK(hipGetLastError());
   rc = launch_stage1<2>(p, B, max_live, s); if (rc) return rc;
-  const int work = n_mels * (n_frames_out / 4);
-  int gx = (work + 255) / 256; if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(logmel_finalize_kernel, dim3(gx, B), dim3(256), 0, s, out, p.clip_max, n_valid, max_valid, p.L, n_fft, hop,
-                     n_mels, n_frames_out);
+  if (n_frames_out % 4 == 0) {
+    const int work = n_mels * (n_frames_out / 4);
+    int gx = (work + 255) / 256; if (gx > 64) gx = 64;
+    hipLaunchKernelGGL(logmel_finalize_kernel, dim3(gx, B), dim3(256), 0, s, out, p.clip_max, n_valid, max_valid, p.L, n_fft, hop,
+                       n_mels, n_frames_out);
+  } else {
+    const int work = n_mels * n_frames_out;
+    int gx = (work + 255) / 256; if (gx > 256) gx = 256;
+    hipLaunchKernelGGL(logmel_finalize_rows_kernel, dim3(gx, B), dim3(256), 0, s, out, p.clip_max, n_valid, max_valid, p.L, n_fft, hop,
+                       n_mels, n_frames_out);
+  }
   AWT_HIP_CHECK(hipGetLastError());
   return AWT_OK;
 }

@@ -12,7 +12,8 @@ Reference interface kept (names, argument meaning, error behaviour):
 
 Behaviour restated from transformers' `WhisperFeatureExtractor.__call__`
 (HF:models/whisper/feature_extraction_whisper.py:193-346): ValueError unless sampling_rate == 16000 (:265-271),
-mono only (:279-280), zero-pad / truncate to 30 s (:300-307), results returned on the CPU.
+mono only (:279-280), zero-pad / truncate to 30 s (:300-307), results returned on the CPU.  `truncation=False, padding="longest"`
+(the long-form call) pads every clip to the longest one and returns `n // 160` frames (`awt_logmel_whisper_signal`).
 The arithmetic runs in libawt (`awt_logmel_whisper`); without the library or a GPU this module raises.
 """
 from __future__ import annotations
@@ -65,6 +66,33 @@ def logmel_whisper_device(pcm: torch.Tensor, n_valid: Optional[torch.Tensor] = N
     return out
 
 
+def frame_attention_mask(lens, n_samples: int, hop_length: int = 160) -> np.ndarray:
+    """HF's `attention_mask` of the features: the per-sample mask of clips padded to n_samples, taken every hop_length samples, its last
+    column dropped when n_samples is not a multiple of hop_length (the features have n_samples // hop_length frames then;
+    feature_extraction_whisper.py:333-341 in transformers 5.15).  int32 [B, n_samples // hop_length] (or [B, n_samples / hop_length])."""
+    lens = np.asarray(lens)
+    mask = (np.arange(n_samples)[None, :] < lens[:, None]).astype(np.int32)[:, ::hop_length]
+    if n_samples % hop_length != 0:
+        mask = mask[:, :-1]
+    return mask
+
+
+def logmel_whisper_longest(pcm: torch.Tensor, n_valid: torch.Tensor, n_mels: int = 80) -> torch.Tensor:
+    """Device PCM [B, n] (clips zero-padded to the longest, n samples) -> device float32 [B, n_mels, n // 160]: HF's
+    `truncation=False, padding="longest"` features (reflect padding only beyond n, the last frame dropped)."""
+    if pcm.dim() != 2 or pcm.dtype not in (torch.int16, torch.float32):
+        raise ValueError("pcm must be a [B, n] int16 or float32 device tensor")
+    B, n = pcm.shape
+    n_valid = n_valid.to(device=pcm.device, dtype=torch.int32).contiguous()
+    out = torch.empty((B, n_mels, n // 160), dtype=torch.float32, device=pcm.device)
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_logmel_workspace_bytes(B), pcm.device)
+    with torch.cuda.device(pcm.device):
+        _lib.check(L.awt_logmel_whisper_signal(_lib.ctx(pcm.device), _lib.ptr(pcm), int(pcm.dtype == torch.int16), pcm.stride(0), _lib.ptr(n_valid),
+                                               int(n), B, int(n), int(n_mels), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
+    return out
+
+
 class WhisperFeatureExtractor:
     """Whisper log-mel extractor with transformers' defaults (feature_extraction_whisper.py:69-103)."""
 
@@ -96,12 +124,17 @@ class WhisperFeatureExtractor:
                 f" was sampled with {self.sampling_rate} and not {sampling_rate}.")
         if do_normalize:
             raise NotImplementedError("do_normalize is not used by the reference and not implemented natively")
-        if padding not in ("max_length", None) or pad_to_multiple_of is not None or not truncation:
-            raise NotImplementedError("only padding='max_length' with truncation (the reference's call) is implemented")
+        longest = not truncation and padding == "longest"
+        if (padding not in ("max_length", None) or not truncation) and not longest or pad_to_multiple_of is not None:
+            raise NotImplementedError("implemented: padding='max_length' with truncation (the reference's call), and truncation=False with "
+                                      "padding='longest' (long-form input)")
         clips = self._to_clip_list(raw_speech)
-        n_samples = int(max_length) if max_length else self.n_samples
-        if n_samples % (4 * self.hop_length) != 0:
-            raise ValueError("max_length must be a multiple of 640 samples")
+        if longest:
+            n_samples = max(max(c.size for c in clips), 1)
+        else:
+            n_samples = int(max_length) if max_length else self.n_samples
+            if n_samples % (4 * self.hop_length) != 0:
+                raise ValueError("max_length must be a multiple of 640 samples")
         n_frames = n_samples // self.hop_length
         lens = np.array([min(c.size, n_samples) for c in clips], dtype=np.int32)
         width = max(int(lens.max()), 1)
@@ -112,14 +145,17 @@ class WhisperFeatureExtractor:
             host[i, : lens[i]] = torch.from_numpy(c[: lens[i]])
         dev = torch.device(device or self.device)
         pcm = host.to(dev, non_blocking=True)
-        feats = logmel_whisper_device(pcm, torch.from_numpy(lens), int(lens.max()), n_frames, n_mels=self.feature_size)
+        if longest:
+            feats = logmel_whisper_longest(pcm, torch.from_numpy(lens), n_mels=self.feature_size)
+        else:
+            feats = logmel_whisper_device(pcm, torch.from_numpy(lens), int(lens.max()), n_frames, n_mels=self.feature_size)
         out = BatchFeature()
         if keep_on_device and return_tensors != "pt":
             raise ValueError("keep_on_device needs return_tensors='pt'")
         feats_cpu = feats if keep_on_device else feats.cpu()  # the reference's extractor returns host arrays
         want_mask = self.return_attention_mask if return_attention_mask is None else return_attention_mask
         if want_mask:
-            mask = (np.arange(n_samples)[None, :] < lens[:, None]).astype(np.int32)[:, :: self.hop_length]
+            mask = frame_attention_mask(lens, n_samples, self.hop_length)
         if return_tensors == "pt":
             out["input_features"] = feats_cpu
             if want_mask:

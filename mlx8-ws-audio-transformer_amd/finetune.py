@@ -292,7 +292,10 @@ class WhisperLoRAModel(nn.Module):
                  decoder_input_ids: Optional[torch.Tensor] = None, num_beams: Optional[int] = None, length_penalty: Optional[float] = None,
                  early_stopping=None, language=None, task: Optional[str] = None, is_multilingual: Optional[bool] = None,
                  return_timestamps: Optional[bool] = None, do_sample: Optional[bool] = None, num_return_sequences: Optional[int] = None,
-                 return_dict_in_generate: bool = False, generation_config=None, **kwargs):
+                 return_dict_in_generate: bool = False, generation_config=None, attention_mask: Optional[torch.Tensor] = None,
+                 return_segments: bool = False, temperature=None, compression_ratio_threshold=None, logprob_threshold=None,
+                 no_speech_threshold=None, condition_on_prev_tokens: Optional[bool] = None, return_token_timestamps: Optional[bool] = None,
+                 **kwargs):
         """`model.generate(input_features)` as AB/wavToWhisper.py:59 / fineTuneMidiTester.py:34 and `predict_with_generate` (fineTune.py:172)
         use it: HF 5.15 `WhisperForConditionalGeneration.generate` for short-form input (generation.py).  Encoder once, cross-attention
         keys / values once, then one token per step (greedy, or beam search with num_beams > 1 on the native decoder).
@@ -302,20 +305,39 @@ class WhisperLoRAModel(nn.Module):
         forced (the language detected when unset), `suppress_tokens` / `begin_suppress_tokens` are masked, `max_length` counts generated
         tokens, and the result holds only the generated tokens, right-padded with pad_token_id.  Without one (a constructed model):
         [B, <= max_length] ids starting with decoder_start_token_id (or `decoder_input_ids`); rows that emitted EOS continue with pad.
-        return_dict_in_generate: a namespace with `sequences` (as returned otherwise) and `sequences_scores` (beam search, else None)."""
+        return_dict_in_generate: a namespace with `sequences` (as returned otherwise) and `sequences_scores` (beam search, else None).
+
+        return_timestamps=True (or `generation_config.extra["return_timestamps"]`), and input features longer than one 3000-frame
+        window (`processor(audio, truncation=False, padding="longest", return_attention_mask=True)`, with `attention_mask` for a batch):
+        HF's seek loop with timestamp tokens (generation.longform_generate).  Returns the [B, T] ids of all segments, or with
+        return_segments=True / return_dict_in_generate=True a dict {"sequences", "segments"} (per clip a list of
+        {start, end, tokens, idxs}, times in seconds)."""
         from . import generation as G
         if kwargs:
             raise TypeError(f"generate: unsupported arguments {sorted(kwargs)}")
-        if return_timestamps:
-            raise ValueError("generate: return_timestamps=True is not supported (timestamp tokens are out of scope)")
         if do_sample:
             raise ValueError("generate: do_sample=True is not supported (sampling is out of scope)")
         if num_return_sequences is not None and num_return_sequences > 1:
             raise ValueError("generate: num_return_sequences > 1 is not supported")
+        for name, val in (("temperature", temperature), ("compression_ratio_threshold", compression_ratio_threshold),
+                          ("logprob_threshold", logprob_threshold), ("no_speech_threshold", no_speech_threshold)):
+            if val is not None:
+                raise ValueError(f"generate: {name} is not supported (sampling and temperature fallback are out of scope)")
+        if condition_on_prev_tokens:
+            raise ValueError("generate: condition_on_prev_tokens=True is not supported")
+        if return_token_timestamps:
+            raise ValueError("generate: return_token_timestamps (word-level timestamps) is not supported")
         window = 2 * self.encoder.cfg.max_source_positions
-        if input_features.shape[-1] > window:
-            raise ValueError(f"generate: inputs longer than one {window}-frame window (long-form decoding) are not supported")
         gc = copy.deepcopy(generation_config if generation_config is not None else self.generation_config)
+        ts = return_timestamps if return_timestamps is not None else gc.extra.get("return_timestamps")
+        longform = input_features.shape[-1] > window
+        if longform and ts is False:
+            raise ValueError(f"generate: more than one {window}-frame window of input features enables long-form generation, which needs "
+                             "timestamp tokens: pass return_timestamps=True or at most one window")
+        ts = bool(ts) or longform
+        if ts and (gc.no_timestamps_token_id is None or int(gc.no_timestamps_token_id) + 1 >= self.decoder.embed_tokens.weight.shape[0]):
+            raise ValueError(f"generate: return_timestamps / long-form decoding (input longer than one {window}-frame window) needs "
+                             "timestamp tokens after generation_config.no_timestamps_token_id, and this model has none")
         nb = int(num_beams if num_beams is not None else (gc.num_beams or 1))
         if nb < 1 or nb > G.MAX_BEAMS:
             raise ValueError(f"generate: num_beams must be between 1 and {G.MAX_BEAMS}, got {nb}")
@@ -330,6 +352,12 @@ class WhisperLoRAModel(nn.Module):
         eos = eos_token_id if eos_token_id is not None else gc.eos_token_id
         pad = gc.pad_token_id
         G.set_language_and_task(gc, language, task, is_multilingual)
+        if ts:
+            if decoder_input_ids is not None:
+                raise ValueError("generate: decoder_input_ids cannot be combined with return_timestamps / long-form input")
+            gc.eos_token_id = eos
+            return self._generate_timestamps(input_features, attention_mask, gc, max_length, nb, lp, es, window,
+                                             return_segments or return_dict_in_generate)
         hidden = self.encoder(input_features).last_hidden_state
         B = hidden.shape[0]
         cross = self.decoder.cross_kv(hidden, self.precision) if (self.native_cross_kv or self.native_decoder) else None
@@ -355,6 +383,40 @@ class WhisperLoRAModel(nn.Module):
         if whisper:
             seqs = G.strip_prompt(seqs, P, pad, eos)
         return SimpleNamespace(sequences=seqs, sequences_scores=scores) if return_dict_in_generate else seqs
+
+    def _generate_timestamps(self, input_features, attention_mask, gc, max_length, nb, lp, es, window, want_segments):
+        """generate with timestamp tokens: prompt without <|notimestamps|> (language detected on the first window), then the seek loop."""
+        from . import generation as G
+        dev = self.encoder.device if hasattr(self.encoder, "device") else input_features.device
+        feats = input_features.to(dev)
+        B = feats.shape[0]
+
+        def detect():
+            first = feats[:, :, :window]
+            if first.shape[-1] < window:
+                first = torch.nn.functional.pad(first, (0, window - first.shape[-1]))
+            hidden = self.encoder(first).last_hidden_state
+            cross = self.decoder.cross_kv(hidden, self.precision) if (self.native_cross_kv or self.native_decoder) else None
+            return self._detect_language(hidden, cross, gc).tolist()
+
+        init = torch.tensor(G.retrieve_init_tokens(gc, B, detect=detect, return_timestamps=True), dtype=torch.long, device=dev)
+        rules = G.TimestampRules(gc.eos_token_id if gc.eos_token_id is not None else gc.decoder_start_token_id, gc.no_timestamps_token_id,
+                                 init.shape[1], gc.extra.get("max_initial_timestamp_index"))
+
+        def decode(seg, init_rows, max_len):
+            hidden = self.encoder(seg).last_hidden_state
+            cross = self.decoder.cross_kv(hidden, self.precision) if (self.native_cross_kv or self.native_decoder) else None
+            steps = self._decode_steps(hidden, cross, seg.shape[0], max_len)
+            if nb == 1:
+                return G.greedy(steps, init_rows, max_len, gc.eos_token_id, gc.pad_token_id, gc.suppress_tokens, gc.begin_suppress_tokens, rules)
+            return G.beam_search(steps, init_rows, max_len, gc.eos_token_id, gc.pad_token_id, gc.suppress_tokens, gc.begin_suppress_tokens, nb,
+                                 lp, es, rules)[0]
+
+        limit = int(gc.max_length if max_length is None else max_length)
+        seqs, segments = G.longform_generate(feats, attention_mask, init, gc, limit, self.max_target_positions, window, decode, rules)
+        if want_segments:
+            return {"sequences": seqs, "segments": segments}
+        return seqs
 
     def _decode_steps(self, hidden, cross, B, max_len):
         from . import generation as G

@@ -9,8 +9,12 @@ and the top 2 x num_beams of a clip's beams in two launches); the native decoder
 preallocated cache that beam search reorders with awt_op_kv_gather.  The remaining beam bookkeeping is HF's vectorised algorithm as
 device tensor ops; a step synchronises with the host once (the stop test).
 
-What this module does not build raises: timestamps, inputs longer than one window, sampling, num_return_sequences > 1, num_beams > 8,
-beam search on the torch decoder, prompt_ids.
+With `return_timestamps=True`, and for inputs longer than one window, `longform_generate` restates HF's seek loop
+(`WhisperGenerationMixin.generate` with timestamps): the selection op then also applies `WhisperTimeStampLogitsProcessor`
+(awt_op_select_tokens_ts), each row's rule state derived on the device from the token history the loop already holds.
+
+What this module does not build raises: sampling and temperature fallback, num_return_sequences > 1, num_beams > 8, beam search on the
+torch decoder, prompt_ids, condition_on_prev_tokens, word-level timestamps.
 """
 from __future__ import annotations
 
@@ -130,9 +134,10 @@ def _language_to_id(gc: GenerationConfig, language: str) -> int:
     return int(gc.lang_to_id[token])
 
 
-def retrieve_init_tokens(gc: GenerationConfig, batch_size: int, detect: Optional[Callable[[], Sequence[int]]] = None) -> List[List[int]]:
-    """`WhisperGenerationMixin._retrieve_init_tokens` without timestamps: the per-clip prompt.  `detect()` returns the detected language
-    ids of the clips (called only when the language is unset on a config with `lang_to_id`)."""
+def retrieve_init_tokens(gc: GenerationConfig, batch_size: int, detect: Optional[Callable[[], Sequence[int]]] = None,
+                         return_timestamps: bool = False) -> List[List[int]]:
+    """`WhisperGenerationMixin._retrieve_init_tokens`: the per-clip prompt.  `detect()` returns the detected language ids of the clips
+    (called only when the language is unset on a config with `lang_to_id`).  With timestamps, <|notimestamps|> is left out."""
     task, language = gc.task, gc.language
     init = [gc.decoder_start_token_id]
     if task is None and language is None and gc.forced_decoder_ids is not None:
@@ -182,8 +187,10 @@ def retrieve_init_tokens(gc: GenerationConfig, batch_size: int, detect: Optional
         elif language is not None and gc.task_to_id is not None:
             if not any(int(t) in inits[i] for t in gc.task_to_id.values()):
                 inits[i].append(int(gc.task_to_id["transcribe"]))
-        if gc.no_timestamps_token_id is not None and inits[i][-1] != gc.no_timestamps_token_id:
+        if not return_timestamps and gc.no_timestamps_token_id is not None and inits[i][-1] != gc.no_timestamps_token_id:
             inits[i].append(int(gc.no_timestamps_token_id))
+        elif return_timestamps and inits[i][-1] == gc.no_timestamps_token_id:
+            inits[i] = inits[i][:-1]
         inits[i] = [int(t) for t in inits[i] if t is not None]
     if len(inits) == 1 and batch_size > 1:
         inits = inits * batch_size
@@ -205,10 +212,56 @@ def banned_bits(tokens, vocab: int, device, invert: bool = False) -> Optional[to
     return words.to(device)
 
 
+class TimestampRules:
+    """HF `WhisperTimeStampLogitsProcessor`'s settings: eos (`eos_token_id or bos_token_id`), <|notimestamps|> (timestamps follow it),
+    `max_initial_timestamp_index` (None: no clamp) and `begin`, the index of the first generated token in each row's history."""
+
+    def __init__(self, eos_token_id: int, no_timestamps_token_id: int, begin: int, max_initial_timestamp_index: Optional[int] = None):
+        self.eos, self.no_ts, self.begin = int(eos_token_id), int(no_timestamps_token_id), int(begin)
+        self.mii = -1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
+
+    @property
+    def timestamp_begin(self) -> int:
+        return self.no_ts + 1
+
+    def struct(self, history: torch.Tensor, cur_len: int):
+        """The awt_ts_rules of one step: history is a device int64 [rows, >= cur_len] view with unit column stride."""
+        import ctypes as C
+
+        class _Rules(C.Structure):
+            _fields_ = [("history", C.c_void_p), ("hist_ld", C.c_int64), ("begin", C.c_int), ("cur_len", C.c_int), ("eos_token_id", C.c_int),
+                        ("no_timestamps_token_id", C.c_int), ("max_initial_timestamp_index", C.c_int)]
+        if history.dtype != torch.int64 or history.stride(-1) != 1:
+            raise ValueError("the token history must be int64 with unit column stride")
+        ld = history.stride(0) if history.shape[0] > 1 else history.shape[-1]
+        return _Rules(history.data_ptr(), int(ld), self.begin, int(cur_len), self.eos, self.no_ts, self.mii)
+
+
 def select_tokens(logits: torch.Tensor, vocab: int, beams: int = 1, banned: Optional[torch.Tensor] = None, beam_scores: Optional[torch.Tensor] = None,
-                  log_softmax: bool = False, k: int = 1):
+                  log_softmax: bool = False, k: int = 1, rules: Optional[TimestampRules] = None, history: Optional[torch.Tensor] = None,
+                  cur_len: int = 0):
     """awt_op_select_tokens on rows of padded logits (a [rows, >= vocab] fp32 view with unit column stride): (scores [clips, k],
-    tokens int64 [clips, k], parents int32 [clips, k])."""
+    tokens int64 [clips, k], parents int32 [clips, k]).  With `rules`: awt_op_select_tokens_ts on the rows' token history
+    ([rows, >= cur_len] int64, the first cur_len tokens live)."""
+    if rules is not None:
+        import ctypes as C
+        rows = logits.shape[0]
+        ld = logits.stride(0) if rows > 1 else max(logits.shape[1], vocab + (-vocab) % 4)
+        if logits.dtype != torch.float32 or logits.stride(1) != 1 or not logits.is_cuda:
+            raise ValueError("select_tokens needs fp32 device logits with unit column stride")
+        dev = logits.device
+        clips = rows // beams if beams > 0 else 0
+        scores = torch.empty((max(clips, 1), k), dtype=torch.float32, device=dev)
+        tokens = torch.empty((max(clips, 1), k), dtype=torch.int64, device=dev)
+        parents = torch.empty((max(clips, 1), k), dtype=torch.int32, device=dev)
+        L = _lib.lib()
+        ws = _lib.workspace(L.awt_select_tokens_ts_workspace_bytes(rows, vocab, k), dev)
+        st = rules.struct(history, cur_len)
+        with torch.cuda.device(dev):
+            _lib.check(L.awt_op_select_tokens_ts(_lib.ctx(dev), logits.data_ptr(), int(ld), rows, int(vocab), int(beams), _lib.ptr(banned),
+                                                 _lib.ptr(beam_scores), int(bool(log_softmax)), int(k), C.addressof(st), _lib.ptr(scores),
+                                                 _lib.ptr(tokens), _lib.ptr(parents), _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
+        return scores, tokens, parents
     rows = logits.shape[0]
     ld = logits.stride(0) if rows > 1 else max(logits.shape[1], vocab + (-vocab) % 4)
     if logits.dtype != torch.float32 or logits.stride(1) != 1 or not logits.is_cuda:
@@ -285,8 +338,10 @@ class _TorchSteps:
 
 
 # ------------------------------------------------------------------------------------------------ decoding loops
-def greedy(steps, init: torch.Tensor, max_len: int, eos_id: Optional[int], pad_id: int, suppress, begin_suppress) -> torch.Tensor:
-    """`GenerationMixin._sample` without sampling: [B, <= max_len] ids starting with the prompt; finished rows continue with pad."""
+def greedy(steps, init: torch.Tensor, max_len: int, eos_id: Optional[int], pad_id: int, suppress, begin_suppress,
+           rules: Optional[TimestampRules] = None) -> torch.Tensor:
+    """`GenerationMixin._sample` without sampling: [B, <= max_len] ids starting with the prompt; finished rows continue with pad.
+    `rules`: Whisper's timestamp rules, applied from the history in `ids`."""
     B, P = init.shape
     dev = init.device
     vocab = steps.vocab
@@ -299,7 +354,7 @@ def greedy(steps, init: torch.Tensor, max_len: int, eos_id: Optional[int], pad_i
     logits = steps.prefill(init)
     first = True
     while True:
-        _, nxt, _ = select_tokens(logits, vocab, banned=ban0 if first else ban)
+        _, nxt, _ = select_tokens(logits, vocab, banned=ban0 if first else ban, rules=rules, history=ids, cur_len=ids.shape[1])
         nxt = nxt[:, 0]
         first = False
         nxt = torch.where(done, torch.full_like(nxt, pad_id), nxt)
@@ -312,7 +367,7 @@ def greedy(steps, init: torch.Tensor, max_len: int, eos_id: Optional[int], pad_i
 
 
 def beam_search(steps, init: torch.Tensor, max_len: int, eos_id: Optional[int], pad_id: Optional[int], suppress, begin_suppress, num_beams: int,
-                length_penalty: float, early_stopping):
+                length_penalty: float, early_stopping, rules: Optional[TimestampRules] = None):
     """`GenerationMixin._beam_search` (HF 5.15, vectorised) on device tensors: (sequences [B, P + generated], sequences_scores [B], generated
     length of each returned hypothesis [B], EOS included)."""
     B, P = init.shape
@@ -339,7 +394,8 @@ def beam_search(steps, init: torch.Tensor, max_len: int, eos_id: Optional[int], 
     logits = logits.repeat_interleave(nb, dim=0) if nb > 1 else logits.contiguous()
     first = True
     while True:
-        topk_log_probs, topk_ids, topk_parent = select_tokens(logits, vocab, nb, ban0 if first else ban, running_scores.reshape(-1), True, k)
+        topk_log_probs, topk_ids, topk_parent = select_tokens(logits, vocab, nb, ban0 if first else ban, running_scores.reshape(-1), True, k,
+                                                              rules=rules, history=running_sequences.view(B * nb, max_len), cur_len=cur_len)
         topk_parent = topk_parent.to(torch.int64)
         topk_sequences = torch.take_along_dim(running_sequences, topk_parent[:, :, None], dim=1)
         topk_sequences[:, :, cur_len] = topk_ids
@@ -402,3 +458,120 @@ def strip_prompt(seqs: torch.Tensor, P: int, pad_id: Optional[int], eos_id: Opti
     for i, r in enumerate(rows):
         out[i, : len(r)] = r
     return out.to(seqs.device)
+
+
+# ------------------------------------------------------------------------------------------------ timestamps and long-form (seek loop)
+TIME_PRECISION = 0.02               # seconds per timestamp token
+TIME_PRECISION_FEATURES = 0.01      # seconds per log-mel frame
+INPUT_STRIDE = 2                    # log-mel frames per encoder position (conv1 stride x conv2 stride)
+
+
+def strip_generated(row: torch.Tensor, pad_id: Optional[int], eos_id: Optional[int]) -> torch.Tensor:
+    """`generate_with_fallback`'s clean-up of one generated row: trailing padding removed (HF counts every pad of the row, one less when
+    pad == eos), then a final EOS."""
+    if row.numel() and pad_id is not None and int(row[-1]) == pad_id:
+        n = int((row == pad_id).sum())
+        if pad_id == eos_id:
+            n -= 1
+        if n:
+            row = row[:-n]
+    if row.numel() and eos_id is not None and int(row[-1]) == eos_id:
+        row = row[:-1]
+    return row
+
+
+def retrieve_segment(seq: torch.Tensor, time_offset: float, timestamp_begin: int, seek_num_frames: int, idx_offset: int):
+    """`WhisperGenerationMixin._retrieve_segment` for one clip's generated tokens (CPU int64): ([{start, end, tokens, idxs}], seek advance
+    in frames).  Two consecutive timestamps end a segment; a single final timestamp means no speech after it (seek the whole window);
+    otherwise the unfinished tail is dropped and the seek goes to the last timestamp."""
+    ts = seq.ge(timestamp_begin)
+    single_ending = ts[-2:].tolist() == [False, True]
+    cuts = (torch.where(ts[:-1] & ts[1:])[0] + 1).tolist()
+    if cuts:
+        segments = []
+        if single_ending:
+            cuts.append(len(seq))
+        else:
+            cuts[-1] += 1
+        last = 0
+        for i, cur in enumerate(cuts):
+            is_last = i == len(cuts) - 1
+            toks = seq[last:cur]
+            start_pos = int(toks[0]) - timestamp_begin
+            end_pos = int(toks[-1 if not is_last or single_ending else -2]) - timestamp_begin
+            segments.append({"start": time_offset + float(start_pos) * TIME_PRECISION, "end": time_offset + float(end_pos) * TIME_PRECISION,
+                             "tokens": toks, "idxs": (idx_offset + last, idx_offset + cur)})
+            last = cur
+        if single_ending:
+            offset = seek_num_frames
+        else:
+            offset = (int(seq[last - 2]) - timestamp_begin) * INPUT_STRIDE
+        return segments, offset
+    stamps = seq[ts]
+    # HF: a long tensor times python floats is float32 arithmetic, then int()
+    last_pos = int(torch.tensor(seek_num_frames, dtype=torch.long) * TIME_PRECISION_FEATURES / TIME_PRECISION)
+    if stamps.numel() > 0 and int(stamps[-1]) != timestamp_begin:
+        last_pos = float(int(stamps[-1]) - timestamp_begin)
+    return [{"start": time_offset, "end": time_offset + last_pos * TIME_PRECISION, "tokens": seq,
+             "idxs": (idx_offset, idx_offset + len(seq))}], seek_num_frames
+
+
+def pad_segments(segments: List[list], pad_id: int, device=None) -> torch.Tensor:
+    """The final `_pad_to_max_length`: each clip's segment tokens concatenated, right-padded with pad_token_id to the longest clip."""
+    rows = [torch.cat([d["tokens"] for d in segs]) if segs else torch.zeros(0, dtype=torch.int64) for segs in segments]
+    width = max((len(r) for r in rows), default=0)
+    out = torch.full((len(rows), width), pad_id, dtype=torch.int64)
+    for i, r in enumerate(rows):
+        out[i, : len(r)] = r
+    return out if device is None else out.to(device)
+
+
+def max_frames_and_seek(batch_size: int, attention_mask: Optional[torch.Tensor], total_frames: int, is_shortform: bool):
+    """`_retrieve_max_frames_and_seek`."""
+    if batch_size > 1 and not is_shortform and attention_mask is None:
+        raise ValueError("When doing batched long-form audio transcription, make sure to pass an `attention_mask`. You can retrieve the "
+                         "`attention_mask` by doing `processor(audio, ..., return_attention_mask=True)`")
+    if batch_size > 1 and not is_shortform:
+        max_frames = torch.as_tensor(attention_mask).sum(-1).cpu().to(torch.long)
+    else:
+        max_frames = torch.ones((batch_size,), dtype=torch.long) * total_frames
+    return max_frames, torch.zeros((batch_size,), dtype=torch.long)
+
+
+def longform_generate(input_features: torch.Tensor, attention_mask, init_tokens: torch.Tensor, gc: GenerationConfig, max_length: int,
+                      max_target_positions: int, num_segment_frames: int, decode: Callable, rules: TimestampRules):
+    """HF 5.15 `WhisperGenerationMixin.generate` with `return_timestamps=True` (short-form and long-form): the seek loop over 30 s windows.
+    `decode(segment_input [b, mels, window], init [b, P], max_len)` returns the generated rows [b, >= P] (prompt included).  Returns
+    (sequences [B, T] on the input's device, segments: per clip a list of {start, end, tokens, idxs, seek})."""
+    B, total = input_features.shape[0], input_features.shape[-1]
+    is_shortform = total <= num_segment_frames
+    max_frames, seek = max_frames_and_seek(B, attention_mask, total, is_shortform)
+    P = init_tokens.shape[1]
+    idx_map = list(range(B))
+    feats = input_features
+    segments: List[list] = [[] for _ in range(B)]
+    tb = rules.timestamp_begin
+    while bool((seek < max_frames).any()):
+        # _maybe_reduce_batch
+        keep = [i for i, prev in enumerate(idx_map) if seek[prev] < max_frames[prev]]
+        if len(keep) != len(idx_map):
+            feats = feats[keep]
+            idx_map = [idx_map[i] for i in keep]
+        time_offset = seek.to(torch.float64) * TIME_PRECISION / INPUT_STRIDE
+        seek_num_frames = (max_frames - seek).clamp(max=num_segment_frames)
+        # _get_input_segment: the window from seek, zero-padded in log-mel space
+        seg = torch.zeros((len(idx_map), feats.shape[1], num_segment_frames), dtype=feats.dtype, device=feats.device)
+        for i, prev in enumerate(idx_map):
+            sl = feats[i, :, int(seek[prev]): int(seek[prev]) + int(seek_num_frames[prev])]    # slice, then zero-pad (HF slices past the end too)
+            seg[i, :, : sl.shape[-1]] = sl
+        # _set_max_new_tokens_and_length: HF writes the grown max_length back into the generation config every pass
+        max_length = min(max_length + min(max_target_positions // 2 - 1, P), max_target_positions)
+        out = decode(seg, init_tokens[idx_map], max_length).cpu()
+        for i, prev in enumerate(idx_map):
+            seq = strip_generated(out[i, P:], gc.pad_token_id, gc.eos_token_id)
+            segs, offset = retrieve_segment(seq, float(time_offset[prev]), tb, int(seek_num_frames[prev]), P)
+            for d in segs:
+                d["seek"] = int(seek[prev])             # the window's first frame (openai-whisper's segment "seek")
+            seek[prev] += offset
+            segments[prev] += segs
+    return pad_segments(segments, gc.pad_token_id, input_features.device), segments

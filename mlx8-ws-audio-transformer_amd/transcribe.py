@@ -24,6 +24,7 @@ import os
 from pathlib import Path
 from typing import Any, Dict, Iterable, List, Optional, Sequence, Union
 
+import numpy as np
 import torch
 
 from .feature_extraction import WhisperProcessor
@@ -94,6 +95,46 @@ def transcribe_clips(waveforms: Sequence[Any], model, processor: WhisperProcesso
     dev = model.encoder.device
     generated_ids = model.generate(inputs["input_features"].to(dev), max_length=max_length, **generate_kwargs)
     return [t.strip() for t in processor.batch_decode(generated_ids.cpu(), skip_special_tokens=True)]
+
+
+@torch.no_grad()
+def transcribe(model, processor: WhisperProcessor, audio_or_path, language: Optional[str] = None, task: Optional[str] = None, num_beams: int = 1,
+               batch_size: int = 16, **generate_kwargs):
+    """openai-whisper's `model.transcribe(path, language=...)` (AB/wavToWhisper.py:10-14) over the native path: long-form, timestamp-driven
+    decoding of a path, a waveform or a list of either (16 kHz mono).  Returns {"text", "segments": [{"id", "seek", "start", "end", "text",
+    "tokens"}], "language"} (a list of them for a list input).  Segment text is the tokenizer's decode of the segment's text tokens
+    (ids below the first timestamp token); the language is detected on the first window when not given."""
+    single = not isinstance(audio_or_path, (list, tuple))
+    items = [audio_or_path] if single else list(audio_or_path)
+    waves = [load_clip_16k(a) if isinstance(a, (str, os.PathLike)) else torch.as_tensor(np.asarray(a, dtype=np.float32)) for a in items]
+    gc = model.generation_config
+    if gc.no_timestamps_token_id is None:
+        raise ValueError("transcribe needs a Whisper generation config with no_timestamps_token_id (timestamp tokens follow it)")
+    tb = int(gc.no_timestamps_token_id) + 1
+    id_to_lang = {int(v): k.strip("<|>") for k, v in (gc.lang_to_id or {}).items()}
+    dev = model.encoder.device
+    results = []
+    for b0 in range(0, len(waves), batch_size):
+        batch = [w.numpy() for w in waves[b0: b0 + batch_size]]
+        inputs = processor(batch, sampling_rate=16000, truncation=False, padding="longest", return_attention_mask=True, return_tensors="pt")
+        feats = inputs["input_features"].to(dev)
+        langs = [language] * len(batch)
+        if language is None and gc.lang_to_id is not None:
+            window = 2 * model.encoder.cfg.max_source_positions
+            first = feats[:, :, :window]
+            if first.shape[-1] < window:
+                first = torch.nn.functional.pad(first, (0, window - first.shape[-1]))
+            langs = [id_to_lang.get(int(t)) for t in model.detect_language(first).tolist()]
+        out = model.generate(feats, attention_mask=inputs["attention_mask"], language=langs if langs[0] is not None else None, task=task,
+                             num_beams=num_beams, return_timestamps=True, return_segments=True, **generate_kwargs)
+        for c, segs in enumerate(out["segments"]):
+            segments = []
+            for j, d in enumerate(segs):
+                toks = [int(t) for t in d["tokens"].tolist() if int(t) < tb]
+                segments.append({"id": j, "seek": d["seek"], "start": float(d["start"]), "end": float(d["end"]),
+                                 "text": processor.decode(toks), "tokens": toks})
+            results.append({"text": "".join(s["text"] for s in segments), "segments": segments, "language": langs[c]})
+    return results[0] if single else results
 
 
 def transcribe_audio_FT(input_path, results: List[dict], model, processor: WhisperProcessor, actual: str = "Asmoranomardicadaistinaculdacar",
