@@ -374,19 +374,18 @@ int awt_op_kv_gather(awt_ctx* c, const float* src, float* dst, const int32_t* pa
 
 /* Process-wide tuning / test hooks.  key "gemm_tile": 0 = choose the GEMM block tile from the shape (default), 64 / 128 / 256 =
  * force the 64 x 128, 128 x 128 or 128 x 256 tile (256 falls back to 128 when N is not a multiple of 256) so that tests can
- * drive every tiling on small shapes; 512 = the 256 x 256 eight-wave tile of the f16f8 GEMM (same results, slower).
- * "gemm_gm": row panels per tile-order group (0 = default).  "attn_shape": workgroup shape of the f16f8 attention kernel, 0 =
- * automatic; 1..5 keep the e4m3 cross terms of P V (plain 4x32 / 4x64 / 6x32 queries, software-pipelined 4 / 8 waves), 6 / 7 =
- * software-pipelined 4 / 8 waves with P V as one fp16 product (what 0 selects for inference).  Only the last choice changes
- * results (within the tolerances of DESIGN.md section 3); every other value is bit-neutral.
+ * drive every tiling on small shapes.
+ * "gemm_gm": row panels per tile-order group (0 = default).  "attn_shape": form of the f16f8 attention kernel (software-pipelined,
+ * 32 queries per wave), 0 = automatic: P V as one fp16 product on 4 waves without lse (inference), every cross term with lse
+ * (training; 8 waves when the grid has at least 256 eight-wave workgroups, else 4); 4 / 5 = every cross term, the e4m3 cross terms of
+ * P V included, on 4 / 8 waves; 6 = P V as one fp16 product on 4 waves (what 0 selects for inference).  Other values are refused.
+ * Only dropping P V's cross terms changes results (within the tolerances of DESIGN.md section 3); the number of waves is bit-neutral.
  * "gemm_pp": the persistent 256 x 256 eight-wave "ping-pong" f16f8 GEMM (csrc/gemm_pp.h: both operands by LDS-DMA, split-line
  * activations, 16 x 16 MFMAs, one workgroup per CU walking its tiles): 0 = off, 1 = automatic (default: inference launches of at
  * least one tile per CU whose tile count fills its rounds of persistent workgroups to 5/6 or better, on weights that are not fp16-exact), 2 = wherever it applies (N % 256 == 0, K % 64 == 0, K >= 128, no adapter; also
  * awt_op_linear).  "gemm_pp_mask": which projections of a layer may take it, a bit set (1 qkv, 2 out_proj, 4 fc1, 8 fc2; fc2 only with
  * fc1; default 12 = the MLP pair, where it is measurably ahead).  Same products and the same accumulation order per output as the
  * 128 x 256 kernel's 16 x 16 form: bit-identical results where both apply.
- * "gemm_pp_stagger": start-up de-phasing of the persistent workgroups in sixteenths of a tile's K loop per group of CUs (0 = off, default;
- * measured: no gain, profiles/r04_gemm_pp16_epilogue.txt).
  * "gemm_mfma16": 1 (default) = the 128 x 256 f16f8 GEMM issues its products as 16 x 16 MFMAs (both e4m3 cross terms in one block-scaled
  * instruction), 0 = the 32 x 32 form (results differ by the fp32 summation order only). */
 int awt_tuning_set(const char* key, int value);

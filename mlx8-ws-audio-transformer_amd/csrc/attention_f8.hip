@@ -50,52 +50,6 @@ __device__ __forceinline__ int swz_v16(int row) { return ((row >> 1) & 1) << 2; 
 __device__ __forceinline__ int swz_k8(int row) { return (row >> 2) & 3; }       // K8 planes: 64-byte rows read by ds_read_b128
 __device__ __forceinline__ int swz_v8(int row) { return ((row >> 3) & 1) << 1; }   // V8 planes: rows k and k + 8 land in different 32-byte halves
 
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) { glds16_asm(gsrc, lds_wave_base); }   // common.h: invisible to hipcc's vmcnt bookkeeping
-__device__ __forceinline__ bf16x4 tr_read16(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)p);
-}
-__device__ __forceinline__ i32x2 tr_read8(const char* p) {
-  return __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) i32x2*)p);
-}
-
-// One K/V tile, global -> LDS.  The tile is 8 + 8 groups of 64 sixteen-byte slots in the fp16 planes and 4 groups in each of the
-// four e4m3 planes (an LDS-DMA instruction fills one group: wave-uniform base + lane * 16); wave w of NW takes groups w, w + NW, ...
-template <int NW>
-__device__ __forceinline__ void stage_kv(const Attn8Args& a, int64_t head_off, int kt, char* stage, int wave, int lane) {
-  const int64_t tile_off = head_off + (int64_t)kt * (KB * 64);
-  const int last = a.S - 1 - kt * KB;          // rows past the sequence end re-read its last key (masked in the tail tile)
-  const bf16_t* k16 = a.k16 + tile_off; const bf16_t* v16 = a.v16 + tile_off;
-#pragma unroll
-  for (int g0 = 0; g0 < 8; g0 += NW) {
-    const int grp = g0 + wave;
-    if (grp < 8) {
-      const int p = grp * 64 + lane;
-      const int row = p >> 3;
-      const unsigned off = (unsigned)(min(row, last) * 64 + (((p & 7) ^ swz16(row)) << 3));
-      const unsigned offv16 = (unsigned)(min(row, last) * 64 + (((p & 7) ^ swz_v16(row)) << 3));
-      char* dst = stage + grp * 1024;
-      glds16(k16 + off, dst + OFF_K16);
-      glds16(v16 + offv16, dst + OFF_V16);
-    }
-  }
-#pragma unroll
-  for (int g0 = 0; g0 < 4; g0 += NW) {
-    const int grp = g0 + wave;
-    if (grp < 4) {
-      const int p = grp * 64 + lane;
-      const int row = p >> 2, c = p & 3;
-      const int r = min(row, last);
-      const unsigned offk = (unsigned)(r * 64 + ((c ^ swz_k8(row)) << 4));
-      const unsigned offv = (unsigned)(r * 64 + ((c ^ swz_v8(row)) << 4));
-      char* dst = stage + grp * 1024;
-      glds16(a.k8 + tile_off + offk, dst + OFF_K8);
-      glds16(a.kl8 + tile_off + offk, dst + OFF_KL8);
-      glds16(a.v8 + tile_off + offv, dst + OFF_V8);
-      glds16(a.vl8 + tile_off + offv, dst + OFF_VL8);
-    }
-  }
-}
-
 // probabilities p in [0, 1] -> e4m3 of p 2^E without clamping (p 2^8 <= 256, (p - fp16(p)) 2^19 <= 128): the conversion
 // instruction applies the power-of-two scale itself (it divides by its scale operand)
 template <int E>
@@ -108,221 +62,14 @@ __device__ __forceinline__ int fp8x4_scaled(float a, float b, float c, float d) 
   return __builtin_bit_cast(int, r);
 }
 
-template <int QT, int NW>
-__global__ __launch_bounds__(64 * NW, (QT == 1 && NW == 6) ? 3 : 2) void attention_f16f8_kernel(Attn8Args a) {
-  constexpr int QW = 32 * QT, QB = NW * QW;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // XCD-aware 1-D grid (attention.hip): the query blocks of one head share an XCD's L2 copy of the head's K and V
-  const int nqb = (a.S + QB - 1) / QB;
-  const int nwg = nqb * a.B * a.H;
-  const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  const int qd = nwg >> 3, rm = nwg & 7;
-  const int logical = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
-  const int bh = logical / nqb;
-  const int b = bh / a.H, h = bh - b * a.H;
-  const int q0 = (logical - bh * nqb) * QB + wave * QW;
-  const int64_t head_off = (int64_t)bh * a.S * 64;
-  const int ql = lane & 31, half = lane >> 5;
-
-  // ---- Q fragments: fp16 (lane holds Q[q][16 ks + 8 half + j]) and the two e4m3 operands (dims 32 half .. + 31)
-  bf16x8 q16[QT][4];
-  i32x8 q8[QT], ql8[QT];
-#pragma unroll
-  for (int t = 0; t < QT; ++t) {
-    int q = q0 + 32 * t + ql; q = q < a.S ? q : a.S - 1;
-    const int64_t off = head_off + (int64_t)q * 64;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) q16[t][ks] = *reinterpret_cast<const bf16x8*>(a.q16 + off + half * 8 + ks * 16);
-    const uint4 x0 = *reinterpret_cast<const uint4*>(a.q8 + off + half * 32), x1 = *reinterpret_cast<const uint4*>(a.q8 + off + half * 32 + 16);
-    const uint4 y0 = *reinterpret_cast<const uint4*>(a.ql8 + off + half * 32), y1 = *reinterpret_cast<const uint4*>(a.ql8 + off + half * 32 + 16);
-    q8[t] = (i32x8){(int)x0.x, (int)x0.y, (int)x0.z, (int)x0.w, (int)x1.x, (int)x1.y, (int)x1.z, (int)x1.w};
-    ql8[t] = (i32x8){(int)y0.x, (int)y0.y, (int)y0.z, (int)y0.w, (int)y1.x, (int)y1.y, (int)y1.z, (int)y1.w};
-  }
-
-  f32x16 oacc[QT][2];
-  float m_run[QT], l_run[QT];
-#pragma unroll
-  for (int t = 0; t < QT; ++t) { oacc[t][0] = (f32x16){}; oacc[t][1] = (f32x16){}; m_run[t] = -1.0e30f; l_run[t] = 0.f; }
-
-  // ---- loop-invariant LDS byte offsets
-  //   K16 fragment (row = 32 kt2 + ql, chunk 2 ks + half): koff[ks] + 4096 kt2          (as attention.hip)
-  //   K8 fragment (row = 32 kt2 + ql, chunks 2 half, 2 half + 1): k8off[c] + 2048 kt2    (swz_k8 repeats every 16 rows)
-  //   V16^T blocks: voff / voffx as attention.hip
-  //   V8^T blocks (read n = 0..3 covers operand bytes 8 n .. 8 n + 7): row = 16 n + 8 (q >> 2) + (q & 3) + 4 half_of_group,
-  //     16-byte chunk (g & 1) + 2 et, XOR 2 (q >> 2):  v8off + 1024 n, dim-tile et toggles byte bit 5
-  int koff[4], k8off[2];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) koff[ks] = ql * 128 + (((2 * ks + half) ^ swz16(ql)) << 4);
-#pragma unroll
-  for (int c = 0; c < 2; ++c) k8off[c] = ql * 64 + (((2 * half + c) ^ swz_k8(ql)) << 4);
-  const int g = lane >> 4, li = lane & 15, qq = li >> 2, pp = li & 3;
-  const int vkey = 4 * (g >> 1) + qq;
-  const int voff = vkey * 128 + (((2 * (g & 1) + (pp >> 1)) ^ swz_v16(vkey)) << 4) + 8 * (pp & 1);
-  const int voffx = voff ^ 64;
-  const int tq = li >> 1, tp = li & 1;
-  const int v8key = 8 * (tq >> 2) + (tq & 3) + 4 * (g >> 1);
-  const int v8off = v8key * 64 + ((((g & 1)) ^ swz_v8(v8key)) << 4) + 8 * tp;
-
-  const int ntiles = (a.S + KB - 1) / KB;
-  stage_kv<NW>(a, head_off, 0, smem, wave, lane);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  auto tile = [&](auto tail_t, int kt) {
-    constexpr bool TAIL = decltype(tail_t)::value;
-    const char* cur = smem + (kt & 1) * STAGE;
-    if (kt + 1 < ntiles) stage_kv<NW>(a, head_off, kt + 1, smem + ((kt + 1) & 1) * STAGE, wave, lane);
-
-    // ---- S^T = K Q^T
-    f32x16 sacc[QT][2];
-#pragma unroll
-    for (int kt2 = 0; kt2 < 2; ++kt2) {
-#pragma unroll
-      for (int t = 0; t < QT; ++t) sacc[t][kt2] = (f32x16){};
-      {
-        const uint4 x0 = *reinterpret_cast<const uint4*>(cur + OFF_K8 + k8off[0] + kt2 * 2048), x1 = *reinterpret_cast<const uint4*>(cur + OFF_K8 + k8off[1] + kt2 * 2048);
-        const uint4 y0 = *reinterpret_cast<const uint4*>(cur + OFF_KL8 + k8off[0] + kt2 * 2048), y1 = *reinterpret_cast<const uint4*>(cur + OFF_KL8 + k8off[1] + kt2 * 2048);
-        const i32x8 k8 = {(int)x0.x, (int)x0.y, (int)x0.z, (int)x0.w, (int)x1.x, (int)x1.y, (int)x1.z, (int)x1.w};
-        const i32x8 kl8 = {(int)y0.x, (int)y0.y, (int)y0.z, (int)y0.w, (int)y1.x, (int)y1.y, (int)y1.z, (int)y1.w};
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-          sacc[t][kt2] = mfma32_f8<e8m0(-kF8KV), e8m0(-kF8Q - kF8Lo)>(k8, ql8[t], sacc[t][kt2]);
-          sacc[t][kt2] = mfma32_f8<e8m0(-kF8KV - kF8Lo), e8m0(-kF8Q)>(kl8, q8[t], sacc[t][kt2]);
-        }
-      }
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const bf16x8 kh = *reinterpret_cast<const bf16x8*>(cur + OFF_K16 + koff[ks] + kt2 * 4096);
-#pragma unroll
-        for (int t = 0; t < QT; ++t) sacc[t][kt2] = mfma32<true>(kh, q16[t][ks], sacc[t][kt2]);
-      }
-    }
-
-    // ---- online softmax, then the accumulator tile becomes the three P operands in place
-    bf16x8 p16[QT][4];        // fp16 B fragments of k-steps (kt2, s2): registers 8 s2 .. 8 s2 + 7 of sub-tile kt2
-    i32x8 p8[QT], pl8[QT];    // e4m3 operands: byte 16 kt2 + r
-#pragma unroll
-    for (int t = 0; t < QT; ++t) {
-      float tmax = -1.0e30f;
-#pragma unroll
-      for (int kt2 = 0; kt2 < 2; ++kt2)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          if (TAIL) {
-            const int key = kt * KB + kt2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            sacc[t][kt2][r] = key < a.S ? sacc[t][kt2][r] : -1.0e30f;
-          }
-          tmax = fmaxf(tmax, sacc[t][kt2][r]);
-        }
-      tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
-      const float m_new = fmaxf(m_run[t], tmax);
-      const float alpha = __builtin_amdgcn_exp2f(m_run[t] - m_new);
-      m_run[t] = m_new;
-      float psum = 0.f;
-#pragma unroll
-      for (int kt2 = 0; kt2 < 2; ++kt2)
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-          float pv[4], lo[4]; bf16_t hb[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            pv[j] = __builtin_amdgcn_exp2f(sacc[t][kt2][4 * r4 + j] - m_new);
-            psum += pv[j];
-            hb[j] = f32_to_f16(pv[j]);
-            lo[j] = __builtin_fmaf(f16_to_f32(hb[j]), -1.0f, pv[j]);
-            p16[t][2 * kt2 + (r4 >> 1)][4 * (r4 & 1) + j] = (short)hb[j];
-          }
-          p8[t][4 * kt2 + r4] = fp8x4_scaled<kF8P>(pv[0], pv[1], pv[2], pv[3]);
-          pl8[t][4 * kt2 + r4] = fp8x4_scaled<kF8P + kF8Lo>(lo[0], lo[1], lo[2], lo[3]);
-        }
-      l_run[t] = l_run[t] * alpha + psum;
-#pragma unroll
-      for (int et = 0; et < 2; ++et)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[t][et][r] *= alpha;
-    }
-
-    // ---- O^T += V^T P^T : fp16 part (k-steps of 16 keys, V16^T by ds_read_b64_tr_b16) ...
-#pragma unroll
-    for (int kt2 = 0; kt2 < 2; ++kt2)
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-        for (int et = 0; et < 2; ++et) {
-          const int cst = kt2 * 4096 + s2 * 2048;
-          const int off0 = (et == 0 ? voff : voffx) + cst;
-          const int off1 = (et == 0 ? voff : voffx) + cst + 1024;     // keys + 8: swz_v16 repeats every 4 rows, so the same lane offset (under swz16 it was the other one)
-          const bf16x4 va = tr_read16(cur + OFF_V16 + off0), vb = tr_read16(cur + OFF_V16 + off1);
-          const bf16x8 vh = {va[0], va[1], va[2], va[3], vb[0], vb[1], vb[2], vb[3]};
-#pragma unroll
-          for (int t = 0; t < QT; ++t) oacc[t][et] = mfma32<true>(vh, p16[t][2 * kt2 + s2], oacc[t][et]);
-        }
-    // ---- ... and the two cross terms on the scaled e4m3 MFMA (one instruction covers the tile's 64 keys)
-#pragma unroll
-    for (int et = 0; et < 2; ++et) {
-      i32x8 v8, vl8;
-#pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        const int off = (v8off ^ (et << 5)) + n * 1024;
-        const i32x2 x = tr_read8(cur + OFF_V8 + off), y = tr_read8(cur + OFF_VL8 + off);
-        v8[2 * n] = x[0]; v8[2 * n + 1] = x[1];
-        vl8[2 * n] = y[0]; vl8[2 * n + 1] = y[1];
-      }
-#pragma unroll
-      for (int t = 0; t < QT; ++t) {
-        oacc[t][et] = mfma32_f8<e8m0(-kF8KV), e8m0(-kF8P - kF8Lo)>(v8, pl8[t], oacc[t][et]);
-        oacc[t][et] = mfma32_f8<e8m0(-kF8KV - kF8Lo), e8m0(-kF8P)>(vl8, p8[t], oacc[t][et]);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  };
-  for (int kt = 0; kt + 1 < ntiles; ++kt) tile(std::false_type{}, kt);
-  if (a.S % KB) tile(std::true_type{}, ntiles - 1);
-  else tile(std::false_type{}, ntiles - 1);
-
-  // ---- normalise and store: lane holds query (lane & 31) of each query tile, dims (r & 3) + 8 (r >> 2) + 4 half
-#pragma unroll
-  for (int t = 0; t < QT; ++t) {
-    const float l_tot = l_run[t] + __shfl_xor(l_run[t], 32);
-    const float inv = 1.0f / l_tot;
-    const int q = q0 + 32 * t + ql;
-    if (a.lse && q < a.S && half == 0) a.lse[(int64_t)bh * a.S + q] = m_run[t] + __builtin_amdgcn_logf(l_tot);
-    if (q < a.S) {
-      const int64_t row = ((int64_t)b * a.S + q) * (a.H * 64) + h * 64;
-#pragma unroll
-      for (int et = 0; et < 2; ++et)
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          const int e = 32 * et + 8 * g4 + 4 * half;
-          float v[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = oacc[t][et][4 * g4 + j] * inv;
-          if (a.o_f32) {
-            *reinterpret_cast<float4*>(a.o_f32 + row + e) = make_float4(v[0], v[1], v[2], v[3]);
-          } else {
-            uint2 h16; unsigned hi8, lo8;
-            f16f8x4<kF8Act>(v, h16, hi8, lo8);
-            if (a.o_ilv) { store_ilv4(a.o_ilv, row + e, h16, hi8, lo8); continue; }
-            *reinterpret_cast<uint2*>(a.o16 + row + e) = h16;
-            if (a.o8) *reinterpret_cast<unsigned*>(a.o8 + row + e) = hi8;
-            *reinterpret_cast<unsigned*>(a.ol8 + row + e) = lo8;
-          }
-        }
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ software-pipelined form
-// The kernel above runs, per wave and K/V tile, 1024 cycles of MFMA and ~350 VALU instructions (~1400 issue cycles) strictly one
-// after the other, and the two waves of a SIMD do not interleave on their own: 3000 cycles per tile where the matrix pipe
-// needs 1024.  Here each wave overlaps them itself: iteration k issues the S^T = K Q^T MFMAs of tile k + 1 with the softmax
-// VALU work of tile k in the gaps between them (an MFMA occupies the issue port for 8 of its 32 / 64 cycles), then the
-// O^T += V^T P^T MFMAs of tile k with the e4m3 packing of P between them.  K is therefore staged two tiles ahead and consumed
-// one iteration early (K(k + 2) lands in the buffer K(k) left in iteration k - 1), V one tile ahead; still two 32 KB stages.
-// One 32-query tile per wave (the second accumulator tile takes the registers of the second query tile), four waves.
+// Per wave and K/V tile there are 1024 cycles of MFMA and ~350 VALU instructions (~1400 issue cycles).  Issued strictly one after
+// the other they take 3000 cycles per tile where the matrix pipe needs 1024: the two waves of a SIMD do not interleave on their own
+// (the un-pipelined form).  Here each wave overlaps them itself: iteration k issues the S^T = K Q^T MFMAs of
+// tile k + 1 with the softmax VALU work of tile k in the gaps between them (an MFMA occupies the issue port for 8 of its 32 / 64
+// cycles), then the O^T += V^T P^T MFMAs of tile k with the e4m3 packing of P between them.  K is therefore staged two tiles ahead
+// and consumed one iteration early (K(k + 2) lands in the buffer K(k) left in iteration k - 1), V one tile ahead; still two 32 KB
+// stages.  One 32-query tile per wave, four or eight waves.
 // K (or V) planes of tile kt -> stage: 8 groups of 64 sixteen-byte slots in the fp16 plane, 4 in each e4m3 plane.  Four waves: two
 // fp16 groups and one group of each e4m3 plane per wave; eight waves: one fp16 group and one e4m3 group (waves 0-3 hi8, 4-7 lo8).
 // RING3 (the single-product P V form): `stage` is the tile's own slot of a three-deep ring -- K slots [K16 | K8 | Klo8] of 16 KB, V slots
@@ -432,6 +179,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f16f8_pipe_kernel(Attn8A
   // V two): a tile's LDS-DMA then has two iterations (~4 us) to land instead of one, and the wait at the end of an iteration only covers
   // the loads of the iteration before (counted vmcnt).  With one iteration of slack the timing-only build without the wait ran 18 % faster.
   constexpr bool RING3 = !PV8;
+  static_assert(!RING3 || NW == 4, "the ring form runs on four waves (its counted vmcnt waits assume one group of each e4m3 plane per wave)");
   constexpr int KO8 = RING3 ? K3_O8 : OFF_K8, KOL8 = RING3 ? K3_OL8 : OFF_KL8, VO16 = RING3 ? 0 : OFF_V16;
   // LDS byte addresses (not pointers: the per-lane read addresses below are plain 32-bit integers the compiler cannot re-derive per read)
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)(smem);
@@ -617,7 +365,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f16f8_pipe_kernel(Attn8A
     if constexpr (RING3 && !LAST) {
       // only the loads of the PREVIOUS iteration have to have landed: this iteration issued NK (fp16 groups + e4m3 groups) K and NV V
       // LDS-DMA instructions per wave (fewer near the end of the key range)
-      constexpr int NK = 8 / NW + (NW == 4 ? 2 : 1), NV = 8 / NW;
+      constexpr int NK = 8 / NW + 2, NV = 8 / NW;
       if (kt + 3 < ntiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NK + NV) : "memory");
       else if (kt + 2 < ntiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NV) : "memory");
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -676,19 +424,32 @@ int launch_pipe(const Attn8Args& a, hipStream_t s) {
   return launch_kernel<attention_f16f8_pipe_kernel<NW, PV8>>(dim3(((a.S + QB - 1) / QB) * a.B * a.H), dim3(64 * NW), lds, s, a);
 }
 
-template <int QT, int NW>
-int launch_t(const Attn8Args& a, hipStream_t s) {
-  constexpr int lds = 2 * STAGE;
-  constexpr int QB = NW * 32 * QT;
-  return launch_kernel<attention_f16f8_kernel<QT, NW>>(dim3(((a.S + QB - 1) / QB) * a.B * a.H), dim3(64 * NW), lds, s, a);
+// The f16f8 attention form: waves per workgroup, and whether P V keeps its two e4m3 cross terms (only then does the kernel read v's
+// e4m3 planes).  Decided here and nowhere else: launch_attention_f16f8 runs this form, attention_f16f8_reads_v8 reports it to the
+// encoder's QKV epilogue.
+struct F8Form { int nw; bool pv8; };
+F8Form f16f8_form(bool with_lse, int B, int H, int S) {
+  // awt_tuning_set("attn_shape"): 4 / 5 = every cross term on 4 / 8 waves; 6 = P V as one fp16 product on 4 waves
+  if (g_attn_shape == 4) return {4, true};
+  if (g_attn_shape == 5) return {8, true};
+  if (g_attn_shape == 6) return {4, false};
+  // measured at B = 64, H = 12, S = 1500 (tools/attn_bench.py, profiles/r02_attention_shapes.txt): software-pipelined 4 x 32 queries
+  // 1.16 ms, 8 x 32 queries 1.19 ms; pipelined with the single fp16 product for P V: 0.82 ms on 4 waves, 0.86 ms on 8.  The kernel is
+  // VALU-bound (33 v_exp_f32 + ~260 other VALU instructions against 24 MFMAs per wave and key tile), so dropping the two e4m3 cross
+  // terms of P V -- their P_lo = P - fp16(P) arithmetic and e4m3 packing is 40 % of that VALU work -- is what buys the time.  Cost: P
+  // and V enter that product with 11 significant bits (error <= 2^-12 |v|_max per output against 2^-15); q k^T keeps its cross terms
+  // because an error in a logit is amplified by exp.  Small grids take the four-wave form (twice the workgroups).
+  if (with_lse) return {(int64_t)((S + 255) / 256) * B * H >= 256 ? 8 : 4, true};   // training keeps every cross term
+  return {4, false};      // 4 waves beat 8 here (0.82 vs 0.86 ms): two workgroups per CU drift apart, which is what lets VALU and MFMA phases overlap
 }
 
 }  // namespace
 
 int g_attn_shape = 0;
 void awt_attn_force_shape(int v) { g_attn_shape = v; }
-// must mirror the selection in launch_attention_f16f8: shapes 1 .. 5 and the training (lse) form keep P V's e4m3 cross terms
-bool attention_f16f8_reads_v8(bool with_lse) { return with_lse || (g_attn_shape >= 1 && g_attn_shape <= 5); }
+
+// whether v's e4m3 planes must be written: the form reads them (which does not depend on the shape), or the call is a training one
+bool attention_f16f8_reads_v8(bool with_lse) { return with_lse || f16f8_form(with_lse, 1, 1, 1).pv8; }
 
 int launch_attention_f16f8(awt_ctx* c, const F8Planes& q, const F8Planes& k, const F8Planes& v, const F8Planes& o, float* o_f32,
                            float* lse, int B, int H, int S, hipStream_t s, char* o_ilv) {
@@ -700,25 +461,7 @@ int launch_attention_f16f8(awt_ctx* c, const F8Planes& q, const F8Planes& k, con
   Attn8Args a{q.p16, k.p16, v.p16, q.hi8, q.lo8, k.hi8, k.lo8, v.hi8, v.lo8, o.p16, o.hi8, o.lo8, o_f32, lse, B, H, S};
   a.o_ilv = o_f32 ? nullptr : o_ilv;
   ProfScope prof(c, AWT_PROF_ATTENTION, s, 4.0 * (double)B * H * (double)S * S * 64);
-  // shapes (awt_tuning_set "attn_shape"): 0 = auto; 1 = 4 waves x 32 queries; 2 = 4 waves x 64 queries; 3 = 6 waves x 32 queries
-  // (three waves per SIMD: one wave's softmax VALU work runs beside the others' MFMAs); 4 / 5 = software-pipelined, 4 / 8 waves,
-  // every cross term; 6 / 7 = the same with P V as one fp16 product
-  const int shape = g_attn_shape;
-  if (shape == 1) return launch_t<1, 4>(a, s);
-  if (shape == 2) return launch_t<2, 4>(a, s);
-  if (shape == 3) return launch_t<1, 6>(a, s);
-  if (shape == 4) return launch_pipe<4, true>(a, s);
-  if (shape == 5) return launch_pipe<8, true>(a, s);
-  if (shape == 6) return launch_pipe<4, false>(a, s);
-  if (shape == 7) return launch_pipe<8, false>(a, s);
-  // measured at B = 64, H = 12, S = 1500 (tools/attn_bench.py, profiles/r02_attention_shapes.txt): plain 4 x 32 queries 1.28 ms,
-  // 4 x 64 queries 1.44 ms (70 spilled registers), 6 x 32 queries 1.68 ms; software-pipelined 4 x 32 queries 1.16 ms, 8 x 32 queries
-  // 1.19 ms; pipelined with the single fp16 product for P V (shapes 6 / 7): 0.82 / 0.86 ms.  The kernel is VALU-bound (33 v_exp_f32 +
-  // ~260 other VALU instructions against 24 MFMAs per wave and key tile), so dropping the two e4m3 cross terms of P V -- their
-  // P_lo = P - fp16(P) arithmetic and e4m3 packing is 40 % of that VALU work -- is what buys the time.  Cost: P and V enter that
-  // product with 11 significant bits (error <= 2^-12 |v|_max per output against 2^-15); q k^T keeps its cross terms because an
-  // error in a logit is amplified by exp.  Small grids take the four-wave form (twice the workgroups).
-  const int64_t wg8 = (int64_t)((S + 255) / 256) * B * H;
-  if (lse) return wg8 >= 256 ? launch_pipe<8, true>(a, s) : launch_pipe<4, true>(a, s);   // training keeps every cross term
-  return launch_pipe<4, false>(a, s);      // 4 waves beat 8 here (0.82 vs 0.86 ms): two workgroups per CU drift apart, which is what lets VALU and MFMA phases overlap
+  const F8Form f = f16f8_form(lse != nullptr, B, H, S);
+  if (f.pv8) return f.nw == 8 ? launch_pipe<8, true>(a, s) : launch_pipe<4, true>(a, s);
+  return launch_pipe<4, false>(a, s);
 }

@@ -42,7 +42,7 @@ static int g_pp_mask = 12;   // tuning knob "gemm_pp_mask": which of a layer's f
 extern "C" int awt_tuning_set(const char* key, int value) {
   AWT_REQUIRE(key, AWT_ERR_INVALID, "tuning_set: null key");
   if (!strcmp(key, "gemm_tile")) {
-    AWT_REQUIRE(value == 0 || value == 64 || value == 128 || value == 256 || value == 512, AWT_ERR_INVALID, "tuning_set: gemm_tile must be 0 (auto), 64, 128, 256 or 512");
+    AWT_REQUIRE(value == 0 || value == 64 || value == 128 || value == 256, AWT_ERR_INVALID, "tuning_set: gemm_tile must be 0 (auto), 64, 128 or 256");
     awt_gemm_force_tile(value);
     return AWT_OK;
   }
@@ -61,18 +61,13 @@ extern "C" int awt_tuning_set(const char* key, int value) {
     g_pp_mask = value;
     return AWT_OK;
   }
-  if (!strcmp(key, "gemm_pp_stagger")) {
-    AWT_REQUIRE(value >= 0 && value <= 16, AWT_ERR_INVALID, "tuning_set: gemm_pp_stagger must be 0 (off) .. 16");
-    awt_gemm_set_pp_stagger(value);
-    return AWT_OK;
-  }
   if (!strcmp(key, "gemm_mfma16")) {
     AWT_REQUIRE(value == 0 || value == 1, AWT_ERR_INVALID, "tuning_set: gemm_mfma16 must be 1 (default: the f16f8 GEMM's 16 x 16 MFMA form where it applies) or 0 (32 x 32 only)");
     awt_gemm_set_mfma16(value);
     return AWT_OK;
   }
   if (!strcmp(key, "attn_shape")) {
-    AWT_REQUIRE(value >= 0 && value <= 9, AWT_ERR_INVALID, "tuning_set: attn_shape must be 0 (auto) or 1 .. 9");
+    AWT_REQUIRE(value == 0 || (value >= 4 && value <= 6), AWT_ERR_INVALID, "tuning_set: attn_shape must be 0 (auto), 4, 5 or 6");
     awt_attn_force_shape(value);
     return AWT_OK;
   }

@@ -373,7 +373,6 @@ size_t gemm_pp_weight_bytes(int N, int K);          // packed image of an [N, K]
 int launch_pack_weight_pp(awt_ctx* c, const float* src, int N, int K, int row_off, char* dst, hipStream_t s);
 int awt_gemm_pp_mode();                             // tuning knob "gemm_pp": 0 off, 1 automatic (default), 2 wherever supported
 void awt_gemm_set_pp_mode(int v);
-void awt_gemm_set_pp_stagger(int v);
 void awt_gemm_set_mfma16(int v);                    // tuning knob "gemm_mfma16": 1 (default) = the 16 x 16 MFMA form of the f16f8 GEMM wherever its weight copies exist, 0 = off
 
 // out_f32 (the final layer_norm) or operand planes of precision `prec`
@@ -412,9 +411,9 @@ int64_t resampled_length(int n_in, int sr_in, int sr_out);
 int logmel_prepare_impl(awt_ctx* c, int n_fft, int n_mels, double f_min, double f_max, int sample_rate, int slaney);
 int resample_prepare_impl(awt_ctx* c, int sr_in, int sr_out);
 void awt_free_tables(awt_ctx* c);
-void awt_attn_force_shape(int v);   // f16f8 attention workgroup shape: 0 auto, 1 / 2 / 3 (attention_f8.hip)
+void awt_attn_force_shape(int v);   // f16f8 attention form (tuning knob "attn_shape"): 0 auto, 4 / 5 / 6 (attention_f8.hip)
 void awt_gemm_set_gm(int v);       // row panels per tile group of the GEMM tile order (0 = default)
-bool attention_f16f8_reads_v8(bool with_lse);   // whether the f16f8 attention kernel that would be selected now stages the e4m3 images of v
+bool attention_f16f8_reads_v8(bool with_lse);   // whether v's e4m3 images must be written for the f16f8 attention form selected now
 void awt_gemm_force_tile(int t);  // 0 auto, 64 / 128 / 256: tuning / tests (awt_tuning_set)
 
 // ---- backward-pass launchers

@@ -23,7 +23,6 @@
 // * epilogue: accumulators are transposed through a per-wave LDS patch so every store is a whole 256 B row
 //   segment; side inputs are prefetched one strip ahead.
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 #include "common.h"
 #include "gemm_pp.h"
@@ -40,7 +39,6 @@ typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
 struct GemmArgs {
   int M, N, nseg, tiles_m, tiles_n;
-  int group_n;           // > 0: walk tiles in groups of group_n column tiles (weight slice L2-resident); 0: groups of GM row panels
   int gm;                // row panels per group (tuning knob "gemm_gm"; default AWT_GEMM_GM)
   GemmSeg seg[kMaxSeg];
   GemmOut out;
@@ -325,24 +323,14 @@ __global__ __launch_bounds__(CFG::WM * CFG::WN * 64, 2) void gemm_kernel(GemmArg
   const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
   const int q = nwg >> 3, r = nwg & 7;
   const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  // Tile order inside an XCD's run (launch_one picks it from the shape):
-  //  group_n = 0 (default): groups of GM row panels, row panel fastest -- GM activation panels stay L2-resident and each
-  //    weight tile is read by GM workgroups at once.
-  //  group_n > 0: groups of group_n column tiles, walked row panel by row panel: the group's weight slice stays in the
-  //    XCD's 4 MB L2 for the whole pass over M; the activations are streamed tiles_n / group_n times.
+  // Tile order inside an XCD's run: groups of GM row panels, row panel fastest -- GM activation panels stay L2-resident and each
+  // weight tile is read by GM workgroups at once.  (Groups of column tiles, which keep a weight slice L2-resident instead, cut the
+  // L2 -> fabric reads by 10 - 25 % but ran 1.5 % slower end to end: DESIGN.md section 4.2, profiles/r01_gemm_tile_order.txt.)
   const int GM = g.gm;
-  int tm, tn;
-  if (g.group_n > 0) {
-    const int grp = tile / (g.group_n * g.tiles_m);
-    const int gn = min(g.group_n, g.tiles_n - grp * g.group_n);
-    const int within = tile - grp * g.group_n * g.tiles_m;
-    tm = within / gn; tn = grp * g.group_n + (within - tm * gn);
-  } else {
-    const int grp = tile / (GM * g.tiles_n);
-    const int gm = min(GM, g.tiles_m - grp * GM);
-    const int within = tile - grp * GM * g.tiles_n;
-    tn = within / gm; tm = grp * GM + (within - tn * gm);
-  }
+  const int grp = tile / (GM * g.tiles_n);
+  const int gm = min(GM, g.tiles_m - grp * GM);
+  const int within = tile - grp * GM * g.tiles_n;
+  const int tn = within / gm, tm = grp * GM + (within - tn * gm);
   const int m0 = tm * T::BM, n0 = tn * T::BN;
 
   int ktiles = 0;
@@ -483,12 +471,8 @@ __global__ __launch_bounds__(CFG::WM * CFG::WN * 64, 2) void gemm_kernel(GemmArg
 // unused) so that the loop body has no branches.
 struct CfgF8W4 { static constexpr int WM = 1, WN = 4, TM = 4, TN = 2; };     // 128 x 256
 struct CfgF8Sq { static constexpr int WM = 2, WN = 2, TM = 2, TN = 2; };     // 128 x 128
-// 256 x 256 on 8 waves (one workgroup per CU): two 128 x 256 halves that share nothing in LDS, only the W fragment loads -- the two wave
-// rows request the same weight bytes within a few cycles of each other, so the second request is served by the CU's vector L1 and the
-// L2 -> CU traffic per output tile drops from 96 KB to 64 KB per 128 x 256 x 64 of work.  Measured (tools/gemm_tile_sweep.py,
-// profiles/r02_gemm_tile_sweep.txt): bit-identical results, 2 - 15 % SLOWER than two independent 128 x 256 workgroups per CU (all eight
-// waves meet at one barrier per K-tile), so it is not selected automatically; awt_tuning_set("gemm_tile", 512) runs it.
-struct CfgF8Big { static constexpr int WM = 2, WN = 4, TM = 4, TN = 2; };
+// (A 256 x 256 tile on 8 waves, whose two wave rows share the W fragment loads through the vector L1, gave bit-identical results but ran
+// 2 - 15 % slower than two independent 128 x 256 workgroups per CU -- all eight waves meet at one barrier per K-tile: DESIGN.md section 8.)
 
 template <int OFF>
 __device__ __forceinline__ bf16x8 gload16(unsigned voff, const void* sbase) {
@@ -557,10 +541,10 @@ struct F8IssueOrder {
 // zero and the x_hi w_lo cross term vanishes: one e4m3 MFMA per fragment pair (x_lo8 w_hi8) instead of two, and neither the A hi8 image nor the W lo8
 // image is moved at all -- 1.5 instead of 2 bf16-MFMA-equivalents and 3 instead of 4 operand bytes per element, with the same result to rounding.
 template <int EPI, class CFG, bool MULTI, bool WX = false>
-__global__ __launch_bounds__(CFG::WM * CFG::WN * 64, CFG::WM * CFG::WN == 4 ? 2 : 1) void gemm_f8_kernel(GemmArgs g) {
+__global__ __launch_bounds__(256, 2) void gemm_f8_kernel(GemmArgs g) {
   constexpr int WM = CFG::WM, WN = CFG::WN, TM = CFG::TM, TN = CFG::TN;
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32, BK = 64, NT = WM * WN * 64;
-  static_assert((BM == 128 && NT == 256) || (BM == 256 && NT == 512), "128 rows per four waves");
+  static_assert(BM == 128 && NT == 256, "128 rows on four waves");
   constexpr int PL16 = BM * BK * 2, PL8 = BM * BK, STAGE = PL16 + 2 * PL8;     // 16 + 8 + 8 KB per 128 rows
   constexpr int IT16 = PL16 / 16 / NT, IT8 = PL8 / 16 / NT;                     // LDS-DMA pieces per thread: 4, 2 (+ 2)
   static_assert(!(WX && MULTI), "the exact-weight form is single-segment");
@@ -1146,10 +1130,10 @@ __global__ __launch_bounds__(256, 2) void gemm_f8s_kernel(GemmArgs g) {
 // Every launch of a GemmArgs kernel: the tile counts of its bm x bn block tiling and the tile order, one workgroup per tile (and per matrix of a
 // batched launch: blockIdx.y), then launch_kernel (common.h).  N % bn != 0: the last column tile is partly empty (its stores are masked by n_valid).
 template <auto Kernel>
-int launch_tiles(GemmArgs a, int bm, int bn, int threads, int lds, hipStream_t s, int group_n = 0, int batch = 1) {
+int launch_tiles(GemmArgs a, int bm, int bn, int threads, int lds, hipStream_t s, int batch = 1) {
   a.tiles_m = (a.M + bm - 1) / bm;
   a.tiles_n = (a.N + bn - 1) / bn;
-  a.group_n = group_n; a.gm = g_gm;
+  a.gm = g_gm;
   return launch_kernel<Kernel>(dim3(a.tiles_m * a.tiles_n, batch), dim3(threads), lds, s, a);
 }
 
@@ -1240,21 +1224,17 @@ int launch_pp(const pp::Args& a, const GemmOut& o, int grid, hipStream_t s) {
 }
 
 int g_force_tile = 0;  // 0 = auto, 64 / 128 / 256 = forced (tuning and tests)
-// Tile order (see the kernel).  Measured on the encoder's shapes (tools/gemm_traffic_shapes.sh, profiles/r01_gemm_tile_order.txt):
-// column-tile groups of 3 cut the L2 -> fabric reads by 10 - 25 % but run 1.5 % slower end to end than groups of GM = 4 row
-// panels, so row-panel groups are the default; AWT_GEMM_GROUP_N=n selects column groups for experiments.
-int g_group_n = 0;
 
 template <int TERMS, int BK, int EPI, class CFG, bool F16 = false, bool WX = false>
 int launch_one(GemmArgs a, hipStream_t s) {
   using T = Tile<TERMS, BK, CFG, WX>;
-  return launch_tiles<gemm_kernel<TERMS, BK, EPI, CFG, F16, WX>>(a, T::BM, T::BN, T::THREADS, T::LDS_BYTES, s, g_group_n);
+  return launch_tiles<gemm_kernel<TERMS, BK, EPI, CFG, F16, WX>>(a, T::BM, T::BN, T::THREADS, T::LDS_BYTES, s);
 }
 // batched launch (launch_gemm_batched): `batch` independent matrices of one shape, blockIdx.y = matrix
 template <int TERMS, int BK, int EPI, class CFG>
 int launch_batched_one(GemmArgs a, int batch, hipStream_t s) {
   using T = Tile<TERMS, BK, CFG, false>;
-  return launch_tiles<gemm_kernel<TERMS, BK, EPI, CFG, false, false, true>>(a, T::BM, T::BN, T::THREADS, T::LDS_BYTES, s, 0, batch);
+  return launch_tiles<gemm_kernel<TERMS, BK, EPI, CFG, false, false, true>>(a, T::BM, T::BN, T::THREADS, T::LDS_BYTES, s, batch);
 }
 
 // Tile choice by tile count: a launch should put at least one tile on each of the 512 workgroup slots (256 CUs x 2) --
@@ -1284,9 +1264,8 @@ int launch_epi(GemmArgs a, int prec, hipStream_t s) {
     const int64_t t256f = (int64_t)((a.M + 127) / 128) * (f8s_ok ? n256 / 256 : a.N / 256);
     int tile = g_force_tile;
     if (!tile) tile = ((a.N % 256 == 0 || f8s_ok) && t256f >= kSlots) ? 256 : 128;
-    if (tile == 512 && a.N % 256 == 0 && a.nseg == 1) return launch_f8<EPI, CfgF8Big>(a, s);
     if (tile == 256 && f8s_ok) return launch_f8s<EPI>(a, s);
-    if (tile >= 256 && a.N % 256 == 0) return launch_f8<EPI, CfgF8W4>(a, s);
+    if (tile == 256 && a.N % 256 == 0) return launch_f8<EPI, CfgF8W4>(a, s);
     return launch_f8<EPI, CfgF8Sq>(a, s);
   }
   const int tile = pick_tile(a.M, a.N);
@@ -1350,8 +1329,6 @@ int launch_gemm_batched(awt_ctx* c, int batch, int M, int N, int K, const bf16_t
 // awt_api.hip's gemm_pp_mask), 2 = wherever supported.  Measured on the headline step (profiles/r04_gemm_pp16_masks.txt, A/B interleaved in one process): the MLP
 // pair on this kernel 46.98 ms per step against 47.50 on the 128 x 256 kernel, QKV + out_proj neutral.
 int g_pp_mode = 1;
-int g_pp_stagger = 0;   // tuning knob "gemm_pp_stagger": start-up de-phasing of the persistent workgroups (gemm_pp.h Args::stagger), 0 = off
-void awt_gemm_set_pp_stagger(int v) { g_pp_stagger = v; }
 int awt_gemm_pp_mode() { return g_pp_mode; }
 void awt_gemm_set_pp_mode(int v) { g_pp_mode = v; }
 // persistent workgroups of a ping-pong launch = CUs of the current device (0 on error)
@@ -1374,7 +1351,7 @@ int launch_gemm_pp(awt_ctx* c, int M, int N, const GemmSeg& seg, GemmEpilogue ep
   pp::Args a{};
   a.A = seg.a_ilv; a.a_row_bytes = (int64_t)seg.lda * 4; a.W = seg.w_pp;
   a.M = M; a.N = N; a.K = seg.K; a.nk = seg.K / 32;
-  a.tiles_m = (M + pp::BM - 1) / pp::BM; a.tiles_n = N / pp::BN; a.ntiles = a.tiles_m * a.tiles_n; a.gm = g_gm; a.stagger = g_pp_stagger;
+  a.tiles_m = (M + pp::BM - 1) / pp::BM; a.tiles_n = N / pp::BN; a.ntiles = a.tiles_m * a.tiles_n; a.gm = g_gm;
   const int grid = std::min(a.ntiles, gemm_pp_slots());          // one persistent workgroup per CU (all of its LDS)
   ProfScope prof(c, AWT_PROF_GEMM, s, 2.0 * (double)M * (double)out.n_valid * (double)seg.K);
   switch (epi) {
@@ -1399,8 +1376,6 @@ int launch_gemm(awt_ctx* c, int M, int N, const GemmSeg* segs, int nseg, int pre
   AWT_REQUIRE(prec_known(prec), AWT_ERR_INVALID, "gemm: unknown operand precision");
   const int terms = prec_products(prec);
   AWT_REQUIRE(c && c->zeros, AWT_ERR_INVALID, "gemm: context without a zero page");
-  static const bool env_read = [] { if (const char* e = getenv("AWT_GEMM_GROUP_N")) g_group_n = std::max(0, atoi(e)); return true; }();   // tile-order experiments (tools/)
-  (void)env_read;
   GemmArgs a{};
   a.M = M; a.N = N; a.nseg = nseg; a.out = out; a.zeros = (const bf16_t*)c->zeros;
   double ksum = 0;

@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC counters of the attention kernels at the bench shape (GPU box): where the wave cycles go, per precision / workgroup shape.
+# PMC counters of the attention kernels at the bench shape (GPU box): where the wave cycles go, per precision / attention form (attn_shape).
 # Usage: bash tools/attn_pmc.sh <outdir-tag>
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 tag=${1:-attn}
@@ -16,7 +16,7 @@ _lib.tuning_set("attn_shape", shape)
 for _ in range(6): ops.attention(q, k, v, prec)
 torch.cuda.synchronize()
 PY
-IFS=";" read -ra CFGS <<< "${AWT_PMC_CFGS:-bf16x3 0;f16f8 1;f16f8 2;f16f8 3}"
+IFS=";" read -ra CFGS <<< "${AWT_PMC_CFGS:-bf16x3 0;f16f8 4;f16f8 5;f16f8 6}"
 for cfg in "${CFGS[@]}"; do
   set -- $cfg
   for pass in A B; do
