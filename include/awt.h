@@ -372,6 +372,34 @@ int awt_op_select_tokens_ts(awt_ctx* c, const float* logits, int ld, int rows, i
 int awt_op_kv_gather(awt_ctx* c, const float* src, float* dst, const int32_t* parent, int layers, int src_rows, int dst_rows, int T, int Tmax,
                      int width, void* stream);
 
+/* Token-level timestamps of generate (csrc/alignment.hip; HF `_extract_token_timestamps`): three launches, no atomics, bit-reproducible.
+ *
+ * awt_op_alignment_weights: out[clip, s, t, :frames] = softmax_j(0.125 q . k_j) over ALL S <= 1536 encoder positions (the crop to
+ * `frames` <= S applies to the stores only) for the n_sel selected heads s and token rows t < T.  q: the query rows kept while decoding,
+ * fp32 [n_slots, rows, Tmax, d], position t0 + t; heads: device int32 [n_sel, 3] = (slot in q, decoder layer, head), out-of-range entries
+ * are clamped; src_row: device int32 [clips, T], the row of q that decoded (clip, t) (beam search), clamped to [0, rows), or NULL: row
+ * clip x group.  Keys: cross_kv fp32 [(rows / group) S, 2 n_layers d] (keys of layer l at column 2 l d), those of clip src_row / group.
+ * Scores are formed as awt_op_attention_small forms them (fp32 operands, the same summation order).
+ *
+ * awt_op_alignment_matrix: weights fp32 [clips, n_sel, T, frames] -> out fp32 [clips, T, frames]: per (clip, head, frame) the z-score over
+ * the T rows ((w - mean) / std, population std), a median of odd `width` <= 15 along the clip's first num_frames[clip] frames (device
+ * int32, NULL: all `frames`) with reflect padding (no filter when that count is <= width / 2), then the mean over heads (n_sel <= 32).
+ * Frames at and beyond a clip's count are written as 0.
+ *
+ * awt_op_dtw: HF `_dynamic_time_warping` of (negate ? -matrix : matrix)[clip, :T, :num_frames[clip]], matrix fp32 [clips, T, frames],
+ * T <= 448: a float32 cost array whose cells are float(double(m) + double(c)), c the smallest of diagonal / up / left (strictly smaller
+ * than both others wins, diagonal first, then up, otherwise left).  jump_frame int32 [clips, T]: the first frame of every token row on
+ * the path.  The path itself (HF's text_indices / time_indices) ends at element T + frames of text_idx / time_idx (int32
+ * [clips, T + frames]) and starts at path_start[clip].  workspace: awt_dtw_workspace_bytes (the trace). */
+int awt_op_alignment_weights(awt_ctx* c, const float* q, int n_slots, int rows, int Tmax, int d, int group, const float* cross_kv, int n_layers,
+                             int S, const int32_t* heads, int n_sel, const int32_t* src_row, int clips, int t0, int T, float* out, int frames,
+                             void* stream);
+int awt_op_alignment_matrix(awt_ctx* c, const float* weights, int clips, int n_sel, int T, int frames, const int32_t* num_frames, int width,
+                            float* out, void* stream);
+size_t awt_dtw_workspace_bytes(int clips, int T, int frames);
+int awt_op_dtw(awt_ctx* c, const float* matrix, int clips, int T, int frames, const int32_t* num_frames, int negate, int32_t* jump_frame,
+               int32_t* text_idx, int32_t* time_idx, int32_t* path_start, void* workspace, size_t ws_bytes, void* stream);
+
 /* Process-wide tuning / test hooks.  key "gemm_tile": 0 = choose the GEMM block tile from the shape (default), 64 / 128 / 256 =
  * force the 64 x 128, 128 x 128 or 128 x 256 tile (256 falls back to 128 when N is not a multiple of 256) so that tests can
  * drive every tiling on small shapes.

@@ -141,6 +141,11 @@ def encoder_config_from_hf(cfg: dict, name: str = "checkpoint") -> EncoderConfig
                          int(cfg.get("encoder_ffn_dim", 1536)), int(cfg.get("num_mel_bins", 80)), int(cfg.get("max_source_positions", 1500)), name)
 
 
+def median_filter_width(cfg: dict) -> int:
+    """`WhisperConfig.median_filter_width` (default 7): the frames the token-timestamp alignment's median filter spans."""
+    return int(cfg.get("median_filter_width", 7))
+
+
 def save_pretrained_dir(path: str, cfg: dict, encoder_sd: Dict[str, torch.Tensor], decoder_sd: Dict[str, torch.Tensor], fmt: str = "safetensors",
                         dtype: torch.dtype = torch.float32) -> str:
     """Writes what `WhisperForConditionalGeneration.save_pretrained` writes for the two formats the reference's versions produce

@@ -190,7 +190,8 @@ class WhisperLoRAModel(nn.Module):
             self.decoder = nd
         for n, p in self.decoder.named_parameters():
             p.requires_grad = "lora_" in n      # frozen base model: only the adapters train
-        self.config = SimpleNamespace(decoder_start_token_id=DECODER_START, pad_token_id=PAD_ID, eos_token_id=EOS_ID, d_model=cfg.d_model)
+        self.config = SimpleNamespace(decoder_start_token_id=DECODER_START, pad_token_id=PAD_ID, eos_token_id=EOS_ID, d_model=cfg.d_model,
+                                      median_filter_width=7)
         self.max_target_positions = max_target_positions
         # what generate reads (HF `model.generation_config`); a constructed model has no Whisper prompt fields and decodes as it always did
         from .generation import GenerationConfig
@@ -228,7 +229,8 @@ class WhisperLoRAModel(nn.Module):
             if hf.get(key) is not None:
                 setattr(model.config, attr, int(hf[key]))
                 setattr(model.generation_config, attr, int(hf[key]))
-        from .checkpoint import load_generation_config
+        from .checkpoint import load_generation_config, median_filter_width
+        model.config.median_filter_width = median_filter_width(hf)
         gc = load_generation_config(path)
         if gc is not None:
             model.generation_config = gc
@@ -261,7 +263,7 @@ class WhisperLoRAModel(nn.Module):
                "decoder_ffn_dim": d.layers[0].fc1.weight.shape[0], "vocab_size": d.embed_tokens.weight.shape[0],
                "max_target_positions": d.embed_positions.weight.shape[0], "decoder_start_token_id": self.config.decoder_start_token_id,
                "pad_token_id": self.config.pad_token_id, "eos_token_id": self.config.eos_token_id, "activation_function": "gelu",
-               "scale_embedding": False, "torch_dtype": "float32"}
+               "scale_embedding": False, "torch_dtype": "float32", "median_filter_width": int(getattr(self.config, "median_filter_width", 7))}
         out = save_pretrained_dir(os.fspath(path), cfg, enc, dec, fmt=fmt)
         gc = getattr(self, "generation_config", None)
         if gc is not None and gc.whisper_prompt:                    # a Whisper generation config travels with the weights
@@ -311,7 +313,13 @@ class WhisperLoRAModel(nn.Module):
         window (`processor(audio, truncation=False, padding="longest", return_attention_mask=True)`, with `attention_mask` for a batch):
         HF's seek loop with timestamp tokens (generation.longform_generate).  Returns the [B, T] ids of all segments, or with
         return_segments=True / return_dict_in_generate=True a dict {"sequences", "segments"} (per clip a list of
-        {start, end, tokens, idxs}, times in seconds)."""
+        {start, end, tokens, idxs}, times in seconds).
+
+        return_token_timestamps=True (with return_timestamps=True, native decoder): a time for every token, HF's
+        `_extract_token_timestamps` (cross-attention of `generation_config.alignment_heads`, a list of [layer, head], z-scored,
+        median-filtered over `config.median_filter_width` frames, averaged, then dynamic time warping; all on the device,
+        generation.extract_token_timestamps).  Returns a dict {"sequences", "token_timestamps" (float32 [B, T], seconds), "segments"},
+        every segment with its own "token_timestamps".  With `attention_mask` the alignment is cropped to each clip's frames."""
         from . import generation as G
         if kwargs:
             raise TypeError(f"generate: unsupported arguments {sorted(kwargs)}")
@@ -325,10 +333,20 @@ class WhisperLoRAModel(nn.Module):
                 raise ValueError(f"generate: {name} is not supported (sampling and temperature fallback are out of scope)")
         if condition_on_prev_tokens:
             raise ValueError("generate: condition_on_prev_tokens=True is not supported")
-        if return_token_timestamps:
-            raise ValueError("generate: return_token_timestamps (word-level timestamps) is not supported")
         window = 2 * self.encoder.cfg.max_source_positions
         gc = copy.deepcopy(generation_config if generation_config is not None else self.generation_config)
+        align = None
+        if return_token_timestamps:
+            if not self.native_decoder:
+                raise ValueError("generate: return_token_timestamps=True needs the native decoder (native_decoder=True)")
+            if return_timestamps is not True:
+                raise ValueError("generate: return_token_timestamps=True needs return_timestamps=True (token timestamps without timestamp "
+                                 "tokens are not supported)")
+            if gc.extra.get("alignment_heads") is None:
+                raise ValueError("Model generation config has no `alignment_heads`, token-level timestamps not available. "
+                                 "See https://gist.github.com/hollance/42e32852f24243b748ae6bc1f985b13a on how to add this property to the "
+                                 "generation config. (generate: return_token_timestamps=True reads generation_config.alignment_heads)")
+            align = G.Alignment(gc.extra["alignment_heads"], getattr(self.config, "median_filter_width", 7), self.decoder.n_layers, self.decoder.heads)
         ts = return_timestamps if return_timestamps is not None else gc.extra.get("return_timestamps")
         longform = input_features.shape[-1] > window
         if longform and ts is False:
@@ -357,7 +375,7 @@ class WhisperLoRAModel(nn.Module):
                 raise ValueError("generate: decoder_input_ids cannot be combined with return_timestamps / long-form input")
             gc.eos_token_id = eos
             return self._generate_timestamps(input_features, attention_mask, gc, max_length, nb, lp, es, window,
-                                             return_segments or return_dict_in_generate)
+                                             return_segments or return_dict_in_generate, align)
         hidden = self.encoder(input_features).last_hidden_state
         B = hidden.shape[0]
         cross = self.decoder.cross_kv(hidden, self.precision) if (self.native_cross_kv or self.native_decoder) else None
@@ -384,8 +402,9 @@ class WhisperLoRAModel(nn.Module):
             seqs = G.strip_prompt(seqs, P, pad, eos)
         return SimpleNamespace(sequences=seqs, sequences_scores=scores) if return_dict_in_generate else seqs
 
-    def _generate_timestamps(self, input_features, attention_mask, gc, max_length, nb, lp, es, window, want_segments):
-        """generate with timestamp tokens: prompt without <|notimestamps|> (language detected on the first window), then the seek loop."""
+    def _generate_timestamps(self, input_features, attention_mask, gc, max_length, nb, lp, es, window, want_segments, align=None):
+        """generate with timestamp tokens: prompt without <|notimestamps|> (language detected on the first window), then the seek loop.
+        align (a generation.Alignment): token-level timestamps as well."""
         from . import generation as G
         dev = self.encoder.device if hasattr(self.encoder, "device") else input_features.device
         feats = input_features.to(dev)
@@ -403,16 +422,30 @@ class WhisperLoRAModel(nn.Module):
         rules = G.TimestampRules(gc.eos_token_id if gc.eos_token_id is not None else gc.decoder_start_token_id, gc.no_timestamps_token_id,
                                  init.shape[1], gc.extra.get("max_initial_timestamp_index"))
 
-        def decode(seg, init_rows, max_len):
+        def decode(seg, init_rows, max_len, window_frames=None):
             hidden = self.encoder(seg).last_hidden_state
             cross = self.decoder.cross_kv(hidden, self.precision) if (self.native_cross_kv or self.native_decoder) else None
             steps = self._decode_steps(hidden, cross, seg.shape[0], max_len)
+            if align is None:
+                if nb == 1:
+                    return G.greedy(steps, init_rows, max_len, gc.eos_token_id, gc.pad_token_id, gc.suppress_tokens, gc.begin_suppress_tokens, rules)
+                return G.beam_search(steps, init_rows, max_len, gc.eos_token_id, gc.pad_token_id, gc.suppress_tokens, gc.begin_suppress_tokens, nb,
+                                     lp, es, rules)[0]
+            steps.align = align                         # the steps keep the alignment layers' cross-attention queries
+            bi = None
             if nb == 1:
-                return G.greedy(steps, init_rows, max_len, gc.eos_token_id, gc.pad_token_id, gc.suppress_tokens, gc.begin_suppress_tokens, rules)
-            return G.beam_search(steps, init_rows, max_len, gc.eos_token_id, gc.pad_token_id, gc.suppress_tokens, gc.begin_suppress_tokens, nb,
-                                 lp, es, rules)[0]
+                out = G.greedy(steps, init_rows, max_len, gc.eos_token_id, gc.pad_token_id, gc.suppress_tokens, gc.begin_suppress_tokens, rules)
+            else:
+                out, _, _, bi = G.beam_search(steps, init_rows, max_len, gc.eos_token_id, gc.pad_token_id, gc.suppress_tokens,
+                                              gc.begin_suppress_tokens, nb, lp, es, rules, return_beam_indices=True)
+            return out, G.extract_token_timestamps(steps, align, out.shape[0], out.shape[1], init_rows.shape[1], window_frames, bi)
 
         limit = int(gc.max_length if max_length is None else max_length)
+        if align is not None:
+            num_frames = None if attention_mask is None else torch.as_tensor(attention_mask).sum(-1).cpu().to(torch.long)      # _set_num_frames
+            seqs, segments, token_ts = G.longform_generate(feats, attention_mask, init, gc, limit, self.max_target_positions, window, decode, rules,
+                                                           return_token_timestamps=True, num_frames=num_frames)
+            return {"sequences": seqs, "token_timestamps": token_ts, "segments": segments}
         seqs, segments = G.longform_generate(feats, attention_mask, init, gc, limit, self.max_target_positions, window, decode, rules)
         if want_segments:
             return {"sequences": seqs, "segments": segments}

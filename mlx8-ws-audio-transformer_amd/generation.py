@@ -13,8 +13,14 @@ With `return_timestamps=True`, and for inputs longer than one window, `longform_
 (`WhisperGenerationMixin.generate` with timestamps): the selection op then also applies `WhisperTimeStampLogitsProcessor`
 (awt_op_select_tokens_ts), each row's rule state derived on the device from the token history the loop already holds.
 
+With `return_token_timestamps=True` every token also gets a time (HF `_extract_token_timestamps`): the decoding steps keep the
+cross-attention query rows of the alignment layers, and after each decode call three libawt ops (csrc/alignment.hip) turn them into the
+alignment heads' probabilities (awt_op_alignment_weights), the z-scored, median-filtered head mean (awt_op_alignment_matrix) and the DTW
+path's first frame per token (awt_op_dtw); `extract_token_timestamps` is the host glue, one synchronisation per decode call.
+`dtw_reference` / `alignment_matrix_reference` restate HF's host code for the tests.
+
 What this module does not build raises: sampling and temperature fallback, num_return_sequences > 1, num_beams > 8, beam search on the
-torch decoder, prompt_ids, condition_on_prev_tokens, word-level timestamps.
+torch decoder, prompt_ids, condition_on_prev_tokens, token timestamps without timestamp tokens, grouping tokens into words.
 """
 from __future__ import annotations
 
@@ -289,6 +295,7 @@ class _NativeSteps:
         self.vocab = dec.vocab
         self.cache = None
         self.group = 1
+        self.align: Optional["Alignment"] = None        # set: the steps after the prompt keep the alignment layers' cross-attention queries
 
     def prefill(self, ids: torch.Tensor) -> torch.Tensor:
         from .native_decoder import DecodeCache
@@ -307,6 +314,8 @@ class _NativeSteps:
         self.cache.gather(parent)
 
     def step(self, tokens: torch.Tensor) -> torch.Tensor:
+        if self.align is not None and self.cache.align_q is None:
+            self.cache.keep_queries(self.align.layers)
         return self.dec.decode_logits(tokens[:, None], self.cross, self.S, self.cache, cross_group=self.group)
 
 
@@ -367,9 +376,10 @@ def greedy(steps, init: torch.Tensor, max_len: int, eos_id: Optional[int], pad_i
 
 
 def beam_search(steps, init: torch.Tensor, max_len: int, eos_id: Optional[int], pad_id: Optional[int], suppress, begin_suppress, num_beams: int,
-                length_penalty: float, early_stopping, rules: Optional[TimestampRules] = None):
+                length_penalty: float, early_stopping, rules: Optional[TimestampRules] = None, return_beam_indices: bool = False):
     """`GenerationMixin._beam_search` (HF 5.15, vectorised) on device tensors: (sequences [B, P + generated], sequences_scores [B], generated
-    length of each returned hypothesis [B], EOS included)."""
+    length of each returned hypothesis [B], EOS included).  return_beam_indices: a fourth element, HF's `beam_indices` [B, generated]
+    (int64): the row of the B x num_beams batch whose logits produced each token of the returned hypothesis, -1 after its end."""
     B, P = init.shape
     dev = init.device
     nb, vocab = num_beams, steps.vocab
@@ -389,6 +399,10 @@ def beam_search(steps, init: torch.Tensor, max_len: int, eos_id: Optional[int], 
     finished_len = torch.zeros((B, nb), dtype=torch.int64, device=dev)          # generated tokens of each kept hypothesis (HF: beam_indices >= 0)
     heur_unsat = torch.ones((B, 1), dtype=torch.bool, device=dev)
     batch_offset = torch.arange(B, device=dev)[:, None] * nb
+    running_beam_indices = beam_indices = None
+    if return_beam_indices:
+        running_beam_indices = torch.full((B, nb, max_len - P), -1, dtype=torch.int64, device=dev)
+        beam_indices = running_beam_indices.clone()
     cur_len = P
     logits = steps.prefill(init)                                                # [B, Np]: every beam of a clip sees the same prompt
     logits = logits.repeat_interleave(nb, dim=0) if nb > 1 else logits.contiguous()
@@ -407,6 +421,10 @@ def beam_search(steps, init: torch.Tensor, max_len: int, eos_id: Optional[int], 
         nxt = torch.topk(topk_running, k=nb)[1]
         running_sequences = torch.take_along_dim(topk_sequences, nxt[:, :, None], dim=1)
         running_scores = torch.take_along_dim(topk_running, nxt, dim=1)
+        if return_beam_indices:
+            topk_beam_indices = torch.take_along_dim(running_beam_indices, topk_parent[:, :, None], dim=1)
+            topk_beam_indices[:, :, cur_len - P] = topk_parent + batch_offset
+            running_beam_indices = torch.take_along_dim(topk_beam_indices, nxt[:, :, None], dim=1)
         parent = (torch.take_along_dim(topk_parent, nxt, dim=1) + batch_offset).reshape(-1)
         # finished hypotheses
         did = hits & top_mask[None, :]
@@ -420,6 +438,8 @@ def beam_search(steps, init: torch.Tensor, max_len: int, eos_id: Optional[int], 
         beam_scores = torch.take_along_dim(torch.cat([beam_scores, lp], dim=1), merged_idx, dim=1)
         finished_len = torch.take_along_dim(torch.cat([finished_len, torch.full_like(topk_ids, cur_len + 1 - P)], dim=1), merged_idx, dim=1)
         finished = torch.take_along_dim(torch.cat([finished, did], dim=1), merged_idx, dim=1)
+        if return_beam_indices:
+            beam_indices = torch.take_along_dim(torch.cat([beam_indices, topk_beam_indices], dim=1), merged_idx[:, :, None], dim=1)
         cur_len += 1
         # early-stop heuristic (HF _check_early_stop_heuristic)
         best_len = (max_len - P) if (early_stopping == "never" and length_penalty > 0.0) else (cur_len - P)
@@ -436,6 +456,8 @@ def beam_search(steps, init: torch.Tensor, max_len: int, eos_id: Optional[int], 
         first = False
         logits = steps.step(running_sequences[:, :, cur_len - 1].reshape(-1))
     gen = int(finished_len[:, 0].max())                                        # HF: generated length of the longest returned hypothesis
+    if return_beam_indices:
+        return sequences[:, 0, : P + gen], beam_scores[:, 0], finished_len[:, 0], beam_indices[:, 0, :gen]
     return sequences[:, 0, : P + gen], beam_scores[:, 0], finished_len[:, 0]
 
 
@@ -480,10 +502,17 @@ def strip_generated(row: torch.Tensor, pad_id: Optional[int], eos_id: Optional[i
     return row
 
 
-def retrieve_segment(seq: torch.Tensor, time_offset: float, timestamp_begin: int, seek_num_frames: int, idx_offset: int):
+def retrieve_segment(seq: torch.Tensor, time_offset: float, timestamp_begin: int, seek_num_frames: int, idx_offset: int,
+                     token_timestamps: Optional[torch.Tensor] = None):
     """`WhisperGenerationMixin._retrieve_segment` for one clip's generated tokens (CPU int64): ([{start, end, tokens, idxs}], seek advance
     in frames).  Two consecutive timestamps end a segment; a single final timestamp means no speech after it (seek the whole window);
-    otherwise the unfinished tail is dropped and the seek goes to the last timestamp."""
+    otherwise the unfinished tail is dropped and the seek goes to the last timestamp.  token_timestamps: the window's float32 row (prompt
+    included); every segment then carries "token_timestamps", its slice plus the window's time offset."""
+    if token_timestamps is not None:
+        segments, offset = retrieve_segment(seq, time_offset, timestamp_begin, seek_num_frames, idx_offset)
+        for d in segments:
+            d["token_timestamps"] = token_timestamps[d["idxs"][0]: d["idxs"][1]] + torch.tensor(time_offset, dtype=torch.float64)
+        return segments, offset
     ts = seq.ge(timestamp_begin)
     single_ending = ts[-2:].tolist() == [False, True]
     cuts = (torch.where(ts[:-1] & ts[1:])[0] + 1).tolist()
@@ -526,6 +555,18 @@ def pad_segments(segments: List[list], pad_id: int, device=None) -> torch.Tensor
     return out if device is None else out.to(device)
 
 
+def pad_token_timestamps(rows: List[list], width: int) -> torch.Tensor:
+    """`_pad_to_max_length(return_token_timestamps=True)`: each clip's slices concatenated, right-padded to `width` with the row's last
+    value (0.0 for a clip without segments)."""
+    out = torch.zeros((len(rows), width), dtype=torch.float32)
+    for i, parts in enumerate(rows):
+        r = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.float32)
+        out[i, : len(r)] = r
+        if len(r):
+            out[i, len(r):] = r[-1]
+    return out
+
+
 def max_frames_and_seek(batch_size: int, attention_mask: Optional[torch.Tensor], total_frames: int, is_shortform: bool):
     """`_retrieve_max_frames_and_seek`."""
     if batch_size > 1 and not is_shortform and attention_mask is None:
@@ -539,10 +580,16 @@ def max_frames_and_seek(batch_size: int, attention_mask: Optional[torch.Tensor],
 
 
 def longform_generate(input_features: torch.Tensor, attention_mask, init_tokens: torch.Tensor, gc: GenerationConfig, max_length: int,
-                      max_target_positions: int, num_segment_frames: int, decode: Callable, rules: TimestampRules):
+                      max_target_positions: int, num_segment_frames: int, decode: Callable, rules: TimestampRules,
+                      return_token_timestamps: bool = False, num_frames: Optional[torch.Tensor] = None):
     """HF 5.15 `WhisperGenerationMixin.generate` with `return_timestamps=True` (short-form and long-form): the seek loop over 30 s windows.
     `decode(segment_input [b, mels, window], init [b, P], max_len)` returns the generated rows [b, >= P] (prompt included).  Returns
-    (sequences [B, T] on the input's device, segments: per clip a list of {start, end, tokens, idxs, seek})."""
+    (sequences [B, T] on the input's device, segments: per clip a list of {start, end, tokens, idxs, seek}).
+
+    return_token_timestamps: `decode(segment_input, init, max_len, window_frames)` returns (rows, float32 token timestamps of the same
+    shape, seconds from the window's start), window_frames the live clips' `num_frames - seek` (None without `num_frames`, HF
+    `_set_num_frames` / `_postprocess_outputs`); the segments gain "token_timestamps" and a third result is HF's padded
+    `token_timestamps` [B, T] (float32: each clip's segment slices, right-padded with the row's last value, 0.0 for an empty row)."""
     B, total = input_features.shape[0], input_features.shape[-1]
     is_shortform = total <= num_segment_frames
     max_frames, seek = max_frames_and_seek(B, attention_mask, total, is_shortform)
@@ -551,6 +598,7 @@ def longform_generate(input_features: torch.Tensor, attention_mask, init_tokens:
     feats = input_features
     segments: List[list] = [[] for _ in range(B)]
     tb = rules.timestamp_begin
+    raw: List[list] = [[] for _ in range(B)]            # per clip the segments' slices of the windows' token timestamps, without the offset
     while bool((seek < max_frames).any()):
         # _maybe_reduce_batch
         keep = [i for i, prev in enumerate(idx_map) if seek[prev] < max_frames[prev]]
@@ -566,12 +614,199 @@ def longform_generate(input_features: torch.Tensor, attention_mask, init_tokens:
             seg[i, :, : sl.shape[-1]] = sl
         # _set_max_new_tokens_and_length: HF writes the grown max_length back into the generation config every pass
         max_length = min(max_length + min(max_target_positions // 2 - 1, P), max_target_positions)
-        out = decode(seg, init_tokens[idx_map], max_length).cpu()
+        ts = None
+        if return_token_timestamps:
+            window_frames = None if num_frames is None else [int(num_frames[prev]) - int(seek[prev]) for prev in idx_map]
+            out, ts = decode(seg, init_tokens[idx_map], max_length, window_frames)
+            out, ts = out.cpu(), ts.cpu()
+        else:
+            out = decode(seg, init_tokens[idx_map], max_length).cpu()
         for i, prev in enumerate(idx_map):
             seq = strip_generated(out[i, P:], gc.pad_token_id, gc.eos_token_id)
-            segs, offset = retrieve_segment(seq, float(time_offset[prev]), tb, int(seek_num_frames[prev]), P)
+            segs, offset = retrieve_segment(seq, float(time_offset[prev]), tb, int(seek_num_frames[prev]), P, None if ts is None else ts[i])
             for d in segs:
                 d["seek"] = int(seek[prev])             # the window's first frame (openai-whisper's segment "seek")
+                if ts is not None:
+                    raw[prev].append(ts[i, d["idxs"][0]: d["idxs"][1]])
             seek[prev] += offset
             segments[prev] += segs
-    return pad_segments(segments, gc.pad_token_id, input_features.device), segments
+    seqs = pad_segments(segments, gc.pad_token_id, input_features.device)
+    if return_token_timestamps:
+        return seqs, segments, pad_token_timestamps(raw, seqs.shape[1]).to(input_features.device)
+    return seqs, segments
+
+
+# ------------------------------------------------------------------------------------------------ token-level timestamps (cross-attention DTW)
+MAX_MEDIAN_WIDTH = 15
+MAX_ALIGNMENT_HEADS = 32
+
+
+class Alignment:
+    """`generation_config.alignment_heads` ([layer, head] pairs, in HF's order) and the model config's `median_filter_width`, checked
+    against the decoder's shape.  `layers`: the distinct decoder layers, in the order of the kept-query buffer's slots."""
+
+    def __init__(self, alignment_heads, median_filter_width: int, n_layers: int, n_heads: int):
+        try:
+            heads = [(int(l), int(h)) for l, h in alignment_heads]
+        except (TypeError, ValueError):
+            raise ValueError(f"generation_config.alignment_heads must be a list of [layer, head] pairs, got {alignment_heads!r}")
+        if not heads or len(heads) > MAX_ALIGNMENT_HEADS:
+            raise ValueError(f"generation_config.alignment_heads must hold between 1 and {MAX_ALIGNMENT_HEADS} [layer, head] pairs, got {len(heads)}")
+        for l, h in heads:
+            if not (0 <= l < n_layers and 0 <= h < n_heads):
+                raise ValueError(f"generation_config.alignment_heads: [{l}, {h}] is out of range for a decoder of {n_layers} layers with {n_heads} heads")
+        w = median_filter_width
+        if not isinstance(w, int) or isinstance(w, bool) or w <= 0 or w % 2 != 1 or w > MAX_MEDIAN_WIDTH:
+            raise ValueError(f"median_filter_width must be an odd number between 1 and {MAX_MEDIAN_WIDTH}, got {w!r}")
+        self.heads, self.width, self.n_layers = heads, w, n_layers
+        self.layers = sorted({l for l, _ in heads})
+        self._table = None
+
+    def table(self, device) -> torch.Tensor:
+        """Device int32 [n_sel, 3]: (slot in the kept-query buffer, decoder layer, head)."""
+        if self._table is None or self._table.device != torch.device(device):
+            slot = {l: s for s, l in enumerate(self.layers)}
+            self._table = torch.tensor([[slot[l], l, h] for l, h in self.heads], dtype=torch.int32).to(device)
+        return self._table
+
+
+def dtw_reference(matrix, return_cost: bool = False):
+    """HF `_dynamic_time_warping` (generation_whisper.py:64-115) on the host: (text_indices, time_indices) of the cheapest monotone path
+    through `matrix` [tokens, frames].  The cost array is float32; a cell is float32(float64(matrix) + float64(c)), c the smallest of
+    diagonal / up / left: strictly smaller than both others wins, diagonal tested first, then up, otherwise left.  return_cost: the
+    float32 cost array [tokens + 1, frames + 1] as a third result."""
+    import numpy as np
+    matrix = np.asarray(matrix, dtype=np.float64)
+    n, m = matrix.shape
+    cost = np.full((n + 1, m + 1), np.inf, dtype=np.float32)
+    trace = np.full((n + 1, m + 1), -1, dtype=np.int8)
+    cost[0, 0] = 0
+    with np.errstate(invalid="ignore", over="ignore"):
+        for i in range(1, n + 1):                       # row by row instead of HF's column by column: every cell sees the same three neighbours
+            up = cost[i - 1]
+            row = cost[i]
+            mrow = matrix[i - 1]
+            trow = trace[i]
+            left = row[0]
+            for j in range(1, m + 1):
+                c0, c1 = up[j - 1], up[j]
+                if c0 < c1 and c0 < left:
+                    c, t = c0, 0
+                elif c1 < c0 and c1 < left:
+                    c, t = c1, 1
+                else:
+                    c, t = left, 2
+                left = np.float32(mrow[j - 1] + np.float64(c))
+                row[j] = left
+                trow[j] = t
+    trace[0, :] = 2
+    trace[:, 0] = 1
+    i, j = n, m
+    text, time = [], []
+    while i > 0 or j > 0:
+        text.append(i - 1)
+        time.append(j - 1)
+        t = trace[i, j]
+        if t == 0:
+            i, j = i - 1, j - 1
+        elif t == 1:
+            i -= 1
+        else:
+            j -= 1
+    path = np.array(text, dtype=np.int64)[::-1], np.array(time, dtype=np.int64)[::-1]
+    return path + (cost,) if return_cost else path
+
+
+def alignment_matrix_reference(weights: torch.Tensor, width: int) -> torch.Tensor:
+    """Steps 4-5 of `_extract_token_timestamps` in HF's torch ops and order: weights [..., heads, tokens, frames] -> [..., tokens, frames]:
+    z-score over tokens (population std), median of `width` along frames with reflect padding (unfiltered when frames <= width // 2),
+    mean over heads."""
+    if width <= 0 or width % 2 != 1:
+        raise ValueError("`filter_width` should be an odd number")
+    std = torch.std(weights, dim=-2, keepdim=True, unbiased=False)
+    mean = torch.mean(weights, dim=-2, keepdim=True)
+    w = (weights - mean) / std
+    pad = width // 2
+    if w.shape[-1] > pad:
+        lead = w.shape[:-2]
+        w = torch.nn.functional.pad(w.reshape((-1,) + w.shape[-2:])[None], (pad, pad, 0, 0), mode="reflect")[0].reshape(lead + (w.shape[-2], -1))
+        w = w.unfold(-1, width, 1).sort()[0][..., pad]
+    return w.mean(dim=-3)
+
+
+def alignment_weights(q: torch.Tensor, cross_kv: torch.Tensor, n_layers: int, S: int, table: torch.Tensor, clips: int, group: int, t0: int,
+                      T: int, frames: int, src_row: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """awt_op_alignment_weights: q [slots, rows, Tmax, d] kept queries, cross_kv the `cross_kv` tensor -> fp32 [clips, n_sel, T, frames]."""
+    slots, rows, Tmax, d = q.shape
+    out = torch.empty((clips, table.shape[0], T, frames), dtype=torch.float32, device=q.device)
+    with torch.cuda.device(q.device):
+        _lib.check(_lib.lib().awt_op_alignment_weights(_lib.ctx(q.device), _lib.ptr(q), slots, rows, Tmax, d, int(group), _lib.ptr(cross_kv), int(n_layers),
+                                                       int(S), _lib.ptr(table), table.shape[0], _lib.ptr(src_row), int(clips), int(t0), int(T), _lib.ptr(out),
+                                                       int(frames), _lib.stream_handle()))
+    return out
+
+
+def alignment_matrix(weights: torch.Tensor, width: int, num_frames: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """awt_op_alignment_matrix: weights fp32 [clips, heads, T, frames] (+ device int32 frames per clip) -> fp32 [clips, T, frames]."""
+    clips, n_sel, T, frames = weights.shape
+    out = torch.empty((clips, T, frames), dtype=torch.float32, device=weights.device)
+    with torch.cuda.device(weights.device):
+        _lib.check(_lib.lib().awt_op_alignment_matrix(_lib.ctx(weights.device), _lib.ptr(weights), clips, n_sel, T, frames, _lib.ptr(num_frames), int(width),
+                                                      _lib.ptr(out), _lib.stream_handle()))
+    return out
+
+
+def dtw(matrix: torch.Tensor, num_frames: Optional[torch.Tensor] = None, negate: bool = True):
+    """awt_op_dtw on fp32 [clips, T, frames] (negate: of -matrix, as HF calls it): (jump_frame int32 [clips, T], text_idx, time_idx int32
+    [clips, T + frames], path_start int32 [clips]); clip c's path is text_idx[c, path_start[c]:] / time_idx[c, path_start[c]:]."""
+    clips, T, frames = matrix.shape
+    dev = matrix.device
+    jump = torch.empty((clips, T), dtype=torch.int32, device=dev)
+    text = torch.empty((clips, T + frames), dtype=torch.int32, device=dev)
+    time = torch.empty((clips, T + frames), dtype=torch.int32, device=dev)
+    start = torch.empty((clips,), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_dtw_workspace_bytes(clips, T, frames), dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.awt_op_dtw(_lib.ctx(dev), _lib.ptr(matrix), clips, T, frames, _lib.ptr(num_frames), int(bool(negate)), _lib.ptr(jump), _lib.ptr(text),
+                                _lib.ptr(time), _lib.ptr(start), _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
+    return jump, text, time, start
+
+
+def alignment_matrix_of(steps, align: Alignment, rows: int, L: int, P: int, window_frames=None, beam_indices: Optional[torch.Tensor] = None):
+    """Steps 1-5 of `_extract_token_timestamps` for one decode call on the native decoder: (matrix fp32 [rows, L - 1 - P, frames], device
+    int32 frames per clip or None).  `steps`: the `_NativeSteps` that decoded, its cache holding the kept queries."""
+    T = L - 1 - P
+    S = steps.S
+    dev = steps.cross.device
+    nf = None
+    frames = S
+    if window_frames is not None:
+        # HF crops to num_frames // 2 (a slice: never more than S).  A window of a single frame would leave nothing to align; keep one frame.
+        counts = [min(max(int(n) // 2, 1), S) for n in window_frames]
+        frames = max(counts)
+        nf = torch.tensor(counts, dtype=torch.int32).to(dev)
+    src = None
+    if beam_indices is not None:
+        # input position P + t was decoded by the row that produced token P + t + 1; after a hypothesis' end (-1) HF gathers row 0 of the batch
+        src = beam_indices[:, 1: 1 + T].clamp(min=0).to(torch.int32).contiguous()
+    w = alignment_weights(steps.cache.align_q, steps.cross, align.n_layers, S, align.table(dev), rows, steps.group, P, T, frames, src)
+    return alignment_matrix(w, align.width, nf), nf
+
+
+def extract_token_timestamps(steps, align: Alignment, rows: int, L: int, P: int, window_frames=None,
+                             beam_indices: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`_extract_token_timestamps` for one decode call: float32 CPU [rows, L], seconds from the window's start: zeros for the P prompt
+    tokens, 0.02 x the first frame of each token's stretch of the DTW path, the last value repeated for the final token (whose
+    cross-attention no step computed).  Fewer than two generated tokens: all zeros."""
+    import numpy as np
+    out = torch.zeros((rows, L), dtype=torch.float32)
+    T = L - 1 - P
+    if T <= 0:
+        return out
+    matrix, nf = alignment_matrix_of(steps, align, rows, L, P, window_frames, beam_indices)
+    jump = dtw(matrix, nf, negate=True)[0].cpu().numpy()                     # the decode call's one host synchronisation for this feature
+    times = torch.from_numpy((jump.astype(np.float64) * TIME_PRECISION).astype(np.float32))
+    out[:, P: P + T] = times
+    out[:, P + T] = times[:, -1]
+    return out

@@ -333,12 +333,22 @@ def cross_entropy(logits, labels, vocab):
 class DecodeCache:
     """Self-attention keys / values of incremental decoding, preallocated once per generate call: [layers, rows, Tmax, 2 d] (keys in the first
     d columns).  A step appends its L new positions in place at T; beam search reorders rows into a second buffer of the same shape with
-    awt_op_kv_gather (`gather`) and swaps the two."""
+    awt_op_kv_gather (`gather`) and swaps the two.
+
+    `keep_queries(layers)` (token timestamps, generation.extract_token_timestamps): from then on every step also stores the cross-attention
+    query rows of those decoder layers at their positions in `align_q` [len(layers), rows, Tmax, d].  That buffer is never reordered: a
+    row of it is the batch row that ran the step, and beam search's `beam_indices` say which row that was for each returned token."""
 
     def __init__(self, layers: int, rows: int, Tmax: int, d: int, device, double: bool = False):
         self.layers, self.rows, self.Tmax, self.d, self.T = layers, rows, Tmax, d, 0
         self.buf = torch.empty((layers, rows, Tmax, 2 * d), dtype=torch.float32, device=device)
         self.spare = torch.empty_like(self.buf) if double else None
+        self.align_q: Optional[torch.Tensor] = None
+        self.align_slots: Dict[int, int] = {}
+
+    def keep_queries(self, layers) -> None:
+        self.align_slots = {int(l): s for s, l in enumerate(layers)}
+        self.align_q = torch.zeros((len(self.align_slots), self.rows, self.Tmax, self.d), dtype=torch.float32, device=self.buf.device)
 
     def attend(self, i: int, qkv: torch.Tensor, L: int) -> torch.Tensor:
         d, T = self.d, self.T + L
@@ -572,6 +582,8 @@ class NativeWhisperDecoder(nn.Module):
             if ab is not None:
                 us["cq"], delta = self._lora_term(h2, ab)
                 q += delta
+            if isinstance(caches, DecodeCache) and caches.align_q is not None and i in caches.align_slots:
+                caches.align_q[caches.align_slots[i], :, caches.T: caches.T + L].copy_(q.view(B, L, d))
             if isinstance(kv, _AbsorbedCross):
                 a2, lse2 = kv.attend(i, q, L)                                            # lse2: (q~, P, context) for the backward
             else:

@@ -99,11 +99,13 @@ def transcribe_clips(waveforms: Sequence[Any], model, processor: WhisperProcesso
 
 @torch.no_grad()
 def transcribe(model, processor: WhisperProcessor, audio_or_path, language: Optional[str] = None, task: Optional[str] = None, num_beams: int = 1,
-               batch_size: int = 16, **generate_kwargs):
+               batch_size: int = 16, token_timestamps: bool = False, **generate_kwargs):
     """openai-whisper's `model.transcribe(path, language=...)` (AB/wavToWhisper.py:10-14) over the native path: long-form, timestamp-driven
     decoding of a path, a waveform or a list of either (16 kHz mono).  Returns {"text", "segments": [{"id", "seek", "start", "end", "text",
     "tokens"}], "language"} (a list of them for a list input).  Segment text is the tokenizer's decode of the segment's text tokens
-    (ids below the first timestamp token); the language is detected on the first window when not given."""
+    (ids below the first timestamp token); the language is detected on the first window when not given.
+    token_timestamps=True: every segment also has "token_timestamps", the time in seconds of each of its "tokens"
+    (generate(return_token_timestamps=True); needs `generation_config.alignment_heads`)."""
     single = not isinstance(audio_or_path, (list, tuple))
     items = [audio_or_path] if single else list(audio_or_path)
     waves = [load_clip_16k(a) if isinstance(a, (str, os.PathLike)) else torch.as_tensor(np.asarray(a, dtype=np.float32)) for a in items]
@@ -126,13 +128,16 @@ def transcribe(model, processor: WhisperProcessor, audio_or_path, language: Opti
                 first = torch.nn.functional.pad(first, (0, window - first.shape[-1]))
             langs = [id_to_lang.get(int(t)) for t in model.detect_language(first).tolist()]
         out = model.generate(feats, attention_mask=inputs["attention_mask"], language=langs if langs[0] is not None else None, task=task,
-                             num_beams=num_beams, return_timestamps=True, return_segments=True, **generate_kwargs)
+                             num_beams=num_beams, return_timestamps=True, return_segments=True, **({"return_token_timestamps": True} if token_timestamps else {}),
+                             **generate_kwargs)
         for c, segs in enumerate(out["segments"]):
             segments = []
             for j, d in enumerate(segs):
                 toks = [int(t) for t in d["tokens"].tolist() if int(t) < tb]
                 segments.append({"id": j, "seek": d["seek"], "start": float(d["start"]), "end": float(d["end"]),
                                  "text": processor.decode(toks), "tokens": toks})
+                if token_timestamps:
+                    segments[-1]["token_timestamps"] = [float(x) for t, x in zip(d["tokens"].tolist(), d["token_timestamps"].tolist()) if int(t) < tb]
             results.append({"text": "".join(s["text"] for s in segments), "segments": segments, "language": langs[c]})
     return results[0] if single else results
 
