@@ -137,6 +137,9 @@ typedef struct awt_encoder_cfg {
                                f16f8 operand format (2 instead of 3 MFMA-equivalents, 2^-16 per operand like split-bf16), everything
                                else in split-bf16; fp16 planes want gradients of order one: see awt_encoder_set_grad_scale_log2.
                                No fc1 / fc2 adapters.                                                                       */
+  int32_t train_base;       /* != 0 (with training != 0, lora_rank = 0, backward_terms != 5): full-parameter fine-tuning -- the backward
+                               pass produces the gradient of every base parameter except embed_positions.weight (see "Full-parameter
+                               fine-tune step" below).  0 = the adapter-only library, unchanged bit for bit.                   */
 } awt_encoder_cfg;
 
 enum { AWT_LORA_Q = 1, AWT_LORA_K = 2, AWT_LORA_V = 4, AWT_LORA_OUT = 8, AWT_LORA_FC1 = 16, AWT_LORA_FC2 = 32 };
@@ -198,6 +201,25 @@ int awt_encoder_backward(awt_encoder* e, const float* d_last_hidden_state, int B
 enum { AWT_BWD_ACCUMULATE = 1, AWT_BWD_ALLREDUCE = 2 };
 int awt_encoder_backward_ex(awt_encoder* e, const float* d_last_hidden_state, int B, void* saved, size_t saved_bytes,
                             float* lora_grads, size_t n_grads, uint32_t flags, void* stream);
+
+/* ---- Full-parameter fine-tune step (awt_encoder_cfg.train_base; build-defined like the adapter mode): what `trainer.train()` of
+ * /root/reference/AB/fineTune.py:131-199 does to the encoder -- every parameter of it is trained, except the sinusoid table, which HF freezes too
+ * (`embed_positions.requires_grad_(False)`).  awt_encoder_forward_train additionally keeps the conv stem's operands (im2col rows, conv1 output and
+ * pre-activation) and every layer's fc2 input in `saved` (awt_encoder_train_workspace_bytes reports the size of this mode).
+ * awt_encoder_backward[_ex] then takes, in place of `lora_grads`, ONE flat float32 buffer of awt_encoder_base_grad_count(e) elements and writes
+ * into it: per layer dW and db of q_proj, k_proj (no bias), v_proj, out_proj, fc1, fc2 and dgamma / dbeta of both LayerNorms; dgamma / dbeta of the
+ * final layer_norm; and -- the pass continues below layer 0, through its first LayerNorm, the position add and both GELUs -- dW and db of conv2 and
+ * conv1, conv weights in the [out, in, 3] layout of the HF parameters.  No gradient for embed_positions.weight or the input features.
+ * dW[n, k] = sum_m dY[m, n] X[m, k] runs on an MFMA weight-gradient GEMM over the pass' bf16 planes (csrc/wgrad.hip: products per
+ * backward_terms, slab partials summed in a fixed order: bit-reproducible).
+ * Layout of the buffer: the non-layer parameters first, then one contiguous block per layer, layers in order; query it, do not hard-code it:
+ * awt_encoder_base_grad_params(e) parameters, and for index i < that count awt_encoder_base_grad_param gives the HF state-dict key (a string owned
+ * by the handle), the element offset, the shape (3 entries, unused ones 1) and its rank.
+ * AWT_BWD_ACCUMULATE and awt_encoder_set_grad_scale_log2 apply as for adapters.  AWT_BWD_ALLREDUCE reduces layer groups on the side stream as they
+ * finish; the lowest group is reduced last, after the conv stem, together with the non-layer parameters in front of it. */
+size_t awt_encoder_base_grad_count(const awt_encoder* e);
+int awt_encoder_base_grad_params(const awt_encoder* e);
+int awt_encoder_base_grad_param(const awt_encoder* e, int index, const char** name, size_t* offset, int64_t* shape /* [3] */, int* rank);
 
 /* ------------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange over RCCL / xGMI (build-defined: the reference has no distributed code, SURVEY.md
@@ -305,6 +327,17 @@ size_t awt_op_param_grad_workspace_bytes(int M, int d);
 int awt_op_layernorm_param_grad(awt_ctx* c, const float* dy, const float* x, float* dgamma, float* dbeta, int M, int d, float eps,
                                 void* workspace, size_t ws_bytes, void* stream);
 int awt_op_column_sums(awt_ctx* c, const float* a, float* sums, int M, int d, void* workspace, size_t ws_bytes, void* stream);
+/* The weight-gradient GEMM of the full-parameter backward as an operator (csrc/wgrad.hip):
+ *   out[n * sn + k * sk] (+)= scale * sum_{m < M} dy[m, ycol + n] * x[row(m), xcol + k]      n < N, k < K
+ * dy fp32 [M, ldy], x fp32 [rows_x, ldx]; both are split into bf16 hi / lo planes inside; terms = 1 (one bf16 product) or 3 (split-bf16).
+ * rows_out = 0: row(m) = m and rows_x = M.  rows_out > 0 (M % rows_out == 0, rows_x = M / rows_out * rows_in): row(m) =
+ * (m / rows_out) * rows_in + (m % rows_out) * row_mul + row_add, and a row outside [0, rows_in) of its group reads as zero (conv2's taps:
+ * rows_out = S, rows_in = 2 S, row_mul = 2, row_add = tap - 1).  N, K, ldy, ldx, ycol, xcol: multiples of 8; M * ldy, rows_x * ldx: multiples of 4.
+ * accumulate != 0 adds to `out`.  Deterministic: the slab count depends on (M, N, K) only. */
+size_t awt_op_weight_grad_workspace_bytes(int M, int rows_x, int ldy, int ldx, int N, int K);
+int awt_op_weight_grad(awt_ctx* c, const float* dy, int ldy, int ycol, int N, const float* x, int rows_x, int ldx, int xcol, int K, int M,
+                       int rows_out, int rows_in, int row_mul, int row_add, int terms, float scale, int accumulate, float* out, int64_t sn,
+                       int64_t sk, void* workspace, size_t ws_bytes, void* stream);
 /* CrossEntropyLoss(ignore_index = -100, mean) over the first `vocab` of `ld` columns: *loss and d(loss)/d(logits) [M, ld]
  * (padding columns zero).  scratch: (M + 1) * 4 bytes.                    HF:modeling_whisper.py:1079-1086
  * Only -100 is ignored.  Any other target outside [0, vocab) -- torch raises for it -- makes *loss NaN (the call itself cannot fail
@@ -426,7 +459,8 @@ int awt_tuning_set(const char* key, int value);
  * for one class, then resets that class. */
 enum { AWT_PROF_LOGMEL = 0, AWT_PROF_GEMM = 1, AWT_PROF_ATTENTION = 2, AWT_PROF_LAYERNORM = 3, AWT_PROF_OTHER = 4,
        AWT_PROF_ATTENTION_BWD = 5,     /* the attention backward launches (fine-tune step), apart from the forward kernel */
-       AWT_PROF_NCLASSES = 6 };
+       AWT_PROF_WGRAD = 6,             /* the weight-gradient GEMM launches of the full-parameter backward (both of each pair) */
+       AWT_PROF_NCLASSES = 7 };
 int awt_prof_enable(awt_ctx* c, int mask);
 int awt_prof_collect(awt_ctx* c, int klass, double* total_ms, int64_t* launches, double* flops);
 

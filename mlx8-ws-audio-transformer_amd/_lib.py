@@ -28,14 +28,16 @@ class AwtError(RuntimeError):
 class EncoderCfg(C.Structure):
     _fields_ = [("d_model", C.c_int32), ("n_layers", C.c_int32), ("n_heads", C.c_int32), ("ffn_dim", C.c_int32),
                 ("n_mels", C.c_int32), ("n_ctx", C.c_int32), ("mfma_terms", C.c_int32), ("lora_rank", C.c_int32),
-                ("lora_alpha", C.c_float), ("lora_targets", C.c_uint32), ("chunk_clips", C.c_int32), ("training", C.c_int32), ("backward_terms", C.c_int32)]
+                ("lora_alpha", C.c_float), ("lora_targets", C.c_uint32), ("chunk_clips", C.c_int32), ("training", C.c_int32), ("backward_terms", C.c_int32),
+                ("train_base", C.c_int32)]
 
 
 MFMA_PER_PAIR = {"bf16": 1, "fp16": 1, "bf16x3": 3, "fp16x3": 3, "f16f8": 2}   # MFMA-equivalents issued per fragment pair, by precision mode
 BWD_ACCUMULATE, BWD_ALLREDUCE = 1, 2
 COMM_ID_BYTES = 128
 LORA_BITS = {"q_proj": 1, "k_proj": 2, "v_proj": 4, "out_proj": 8, "fc1": 16, "fc2": 32}
-PROF_CLASSES = {"logmel": 0, "gemm": 1, "attention": 2, "layernorm": 3, "other": 4, "attention_bwd": 5}
+PROF_CLASSES = {"logmel": 0, "gemm": 1, "attention": 2, "layernorm": 3, "other": 4, "attention_bwd": 5,
+                "wgrad": 6}   # the weight-gradient GEMMs of the full-parameter backward: timed on request only (prof_enable's default leaves it out)
 
 _vp, _i, _i64, _sz, _f = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float
 _SIGNATURES = {
@@ -60,6 +62,9 @@ _SIGNATURES = {
     "awt_encoder_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "awt_encoder_train_workspace_bytes": (_sz, [_vp, _i]),
     "awt_encoder_lora_grad_count": (_sz, [_vp]),
+    "awt_encoder_base_grad_count": (_sz, [_vp]),
+    "awt_encoder_base_grad_params": (_i, [_vp]),
+    "awt_encoder_base_grad_param": (_i, [_vp, _i, C.POINTER(C.c_char_p), C.POINTER(_sz), C.POINTER(_i64), C.POINTER(_i)]),
     "awt_encoder_forward_train": (_i, [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "awt_encoder_backward": (_i, [_vp, _vp, _i, _vp, _sz, _vp, _sz, _vp]),
     "awt_encoder_backward_ex": (_i, [_vp, _vp, _i, _vp, _sz, _vp, _sz, C.c_uint32, _vp]),
@@ -100,6 +105,8 @@ _SIGNATURES = {
     "awt_op_param_grad_workspace_bytes": (_sz, [_i, _i]),
     "awt_op_layernorm_param_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _sz, _vp]),
     "awt_op_column_sums": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "awt_op_weight_grad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "awt_op_weight_grad": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _i64, _i64, _vp, _sz, _vp]),
     "awt_op_cross_entropy": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "awt_op_attention_small": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "awt_op_attention_small_backward": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -194,7 +201,7 @@ def prof_enable(on, classes=None) -> None:
     """Event-time the given kernel classes (names from PROF_CLASSES; default all) or switch timing off."""
     mask = 0
     if on:
-        for k in (classes or PROF_CLASSES):
+        for k in (classes or [c for c in PROF_CLASSES if c != "wgrad"]):
             mask |= 1 << PROF_CLASSES[k]
     check(lib().awt_prof_enable(ctx(), mask))
 

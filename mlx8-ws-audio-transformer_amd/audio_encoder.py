@@ -24,7 +24,13 @@ class WhisperAudioEncoder(nn.Module):
         super().__init__()
         cfg = model_name if isinstance(model_name, EncoderConfig) else named_config(str(model_name).split("whisper-")[-1])
         self.processor = WhisperProcessor()
-        self.encoder = NativeWhisperEncoder(cfg, precision=precision, device=device)
+        self.freeze_encoder = freeze_encoder
+        if freeze_encoder:
+            self.encoder = NativeWhisperEncoder(cfg, precision=precision, device=device)
+        else:
+            # model.py:28-38 with freeze_encoder=False: every encoder parameter trains (the sinusoid table excepted, as in HF); the forward
+            # then keeps its activations and the native backward produces the base-weight gradients (train_base)
+            self.encoder = NativeWhisperEncoder(cfg, precision=precision or "bf16x3", device=device, trainable=True, train_base=True)
         if state_dict is not None:
             self.encoder.load_state_dict(state_dict)
         if freeze_encoder:
@@ -53,6 +59,12 @@ class WhisperAudioEncoder(nn.Module):
             waveforms = waveforms.mean(dim=-1)  # model.py:82-84
         n = min(waveforms.shape[1], 480000)
         pcm = waveforms[:, :n].to(self.encoder.device, torch.float32).contiguous()
-        with torch.no_grad():
-            hidden = self.encoder.encode_pcm(pcm)
+        if not self.freeze_encoder and torch.is_grad_enabled():     # model.py:108: `torch.set_grad_enabled(not self.freeze_encoder)`
+            from .feature_extraction import logmel_whisper_device
+            with torch.no_grad():
+                feats = logmel_whisper_device(pcm, max_valid=n, n_frames=self.encoder.cfg.n_frames, n_mels=self.encoder.cfg.n_mels)
+            hidden = self.encoder(feats).last_hidden_state
+        else:
+            with torch.no_grad():
+                hidden = self.encoder.encode_pcm(pcm)
         return hidden.to(dtype=next(self.encoder.parameters()).dtype)  # model.py:113-121

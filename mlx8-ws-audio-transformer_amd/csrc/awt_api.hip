@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "comm.h"
+#include "wgrad.h"
 
 // ------------------------------------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -232,6 +233,12 @@ struct awt_encoder {
   bool mlp_f8 = false;             // cfg.backward_terms == 5: the MLP's backward GEMMs in f16f8 (the others in split-bf16)
   float* wt_tmp = nullptr;         // [ffn_dim * d_model] fp32: W^T of the matrix being uploaded (packed into fc1T8 / fc2T8)
   int grad_scale_log2 = 0;         // awt_encoder_set_grad_scale_log2: the backward pass carries 2^k x the gradient (fp16 planes), adapter gradients leave unscaled
+  // cfg.train_base: the backward pass produces the gradient of every base parameter but the position table (no adapters in this mode)
+  bool train_base = false;
+  Planes conv2T[3];                // per tap dt: [d, d] = conv2.weight[:, :, dt]^T (weight of d h1 = d pre2 W2)
+  struct GradEntry { std::string name; size_t offset; int64_t shape[3]; int rank; };
+  std::vector<GradEntry> glayout;  // the flat gradient buffer: the non-layer parameters, then one contiguous block per layer, layers in order
+  size_t g_head = 0, g_per_layer = 0;
 };
 
 namespace {
@@ -402,6 +409,7 @@ struct LayerBufs {
 struct TrainWs {   // carved from the caller's `saved` buffer
   std::vector<LayerBufs> layer;
   bf16_t *a1[2], *h1[2], *ff[2];          // conv-phase scratch, MLP hidden (not needed by the q/k/v-adapter backward)
+  bf16_t* pre1[2];                        // train_base: conv1's pre-activation [B * T, d] (a1 and h1 then outlive the forward as well)
   float* x_final;
   // backward scratch
   float *dx_a, *dx_b, *dln, *delta, *partial;
@@ -431,19 +439,29 @@ TrainWs carve_train(const awt_encoder* e, char* base, int B) {
     if (has_o) planes(L.uo, M * 128); else { L.uo[0] = L.u[0]; L.uo[1] = L.u[1]; }
     if (has_1) planes(L.u1, M * 128); else { L.u1[0] = L.u[0]; L.u1[1] = L.u[1]; }
     if (has_2) { planes(L.u2, M * 128); planes(L.ff, M * f); } else { L.u2[0] = L.u[0]; L.u2[1] = L.u[1]; L.ff[0] = L.ff[1] = nullptr; }
+    if (e->train_base) planes(L.ff, M * f);   // fc2's weight gradient contracts d(x_out) with the fc2 input of this layer
     L.lse = (float*)take((size_t)B * H * S * 4);
   }
   w.x_final = x;
-  planes(w.ff, M * f);
-  // conv-phase scratch aliases the backward scratch (disjoint in time)
+  if (e->train_base) w.ff[0] = w.ff[1] = nullptr;   // every layer keeps its own fc2 input in this mode
+  else planes(w.ff, M * f);
+  // conv-phase scratch aliases the backward scratch (disjoint in time); train_base: the conv stem's backward reads it, so it is kept
+  w.pre1[0] = w.pre1[1] = nullptr;
+  if (e->train_base) { planes(w.a1, Mt * conv1_k(e->cfg.n_mels)); planes(w.h1, Mt * d); planes(w.pre1, Mt * d); }
   const size_t mark = off;
-  planes(w.a1, Mt * conv1_k(e->cfg.n_mels)); planes(w.h1, Mt * d);
+  if (!e->train_base) { planes(w.a1, Mt * conv1_k(e->cfg.n_mels)); planes(w.h1, Mt * d); }
   const size_t conv_end = off;
   off = mark;
   w.dx_a = (float*)take(M * d * 4); w.dx_b = (float*)take(M * d * 4); w.dln = (float*)take(M * d * 4);
   w.delta = (float*)take((size_t)B * H * S * 4);
   planes(w.dxp, M * d); planes(w.dpre, M * f); planes(w.datt, M * d); planes(w.dqkv, 3 * M * d); planes(w.du, M * 128);
   w.partial_bytes = outer_reduce_partial_bytes((int)M, c.lora_rank > 0 ? c.lora_rank : 1, 1024);   // Y blocks are reduced in chunks of <= 1024 columns
+  if (e->train_base) {   // slab partials of the weight-gradient GEMMs (qkv, out_proj, fc1, fc2, a conv2 tap, a conv1 tap) and of the bias / LayerNorm reductions
+    const int Mi = (int)M, Mti = (int)Mt, di = (int)d, fi = (int)f;
+    size_t pb = std::max({wgrad_partial_bytes(Mi, 3 * di, di), wgrad_partial_bytes(Mi, di, di), wgrad_partial_bytes(Mi, fi, di), wgrad_partial_bytes(Mi, di, fi),
+                          wgrad_partial_bytes(Mti, di, c.n_mels), param_grad_partial_bytes(Mti, di)});
+    w.partial_bytes = std::max(w.partial_bytes, pb);
+  }
   w.partial = (float*)take(w.partial_bytes);
   w.bytes = std::max(off, conv_end);
   for (int li = 0; li < c.n_layers; ++li) for (int p = 0; p < 2; ++p) if (!w.layer[li].ff[p]) w.layer[li].ff[p] = w.ff[p];   // kept per layer only under an fc2 adapter
@@ -451,7 +469,7 @@ TrainWs carve_train(const awt_encoder* e, char* base, int B) {
 }
 
 // conv stem (K5-K7): mel [Bc, n_mels, T] -> residual stream x [Bc * S, d] fp32
-int conv_stem(awt_encoder* e, const float* mel, int Bc, bf16_t* const a1[2], bf16_t* const h1[2], float* x, hipStream_t s) {
+int conv_stem(awt_encoder* e, const float* mel, int Bc, bf16_t* const a1[2], bf16_t* const h1[2], float* x, hipStream_t s, bf16_t* const* pre1 = nullptr) {
   const awt_encoder_cfg& c = e->cfg;
   const int S = c.n_ctx, T = 2 * S, d = c.d_model, terms = e->prec;
   const int M = Bc * S, Mt = Bc * T;
@@ -461,7 +479,8 @@ int conv_stem(awt_encoder* e, const float* mel, int Bc, bf16_t* const a1[2], bf1
   {
     GemmSeg sg = seg_plain(aa1, k1, e->conv1.w, 0, k1, Mt);
     GemmOut o{}; set_out(o, ah1); o.ldo = d; o.bias = e->conv1.bias; o.n_valid = d;
-    rc = launch_gemm(e->ctx, Mt, d, &sg, 1, terms, EPI_BF16_GELU, o, s); if (rc) return rc;
+    if (pre1) { o.hi2 = pre1[0]; o.lo2 = pre1[1]; }   // train_base: conv1's pre-activation is kept for its GELU' in the backward pass
+    rc = launch_gemm(e->ctx, Mt, d, &sg, 1, terms, pre1 ? EPI_BF16_GELU_SAVE : EPI_BF16_GELU, o, s); if (rc) return rc;
   }
   GemmSeg sg[3];
   for (int dt = 0; dt < 3; ++dt) {
@@ -581,6 +600,50 @@ int copy_f32(float* dst, const float* src, size_t n, hipStream_t s) {
 
 }  // namespace
 
+namespace {
+// The flat gradient buffer of cfg.train_base: head = the non-layer parameters, then one contiguous block per layer (the in-backward exchange
+// reduces whole layer groups; the head goes with the lowest group, which is reduced last).  q | k | v weights are adjacent: one [3 d, d] product.
+void build_grad_layout(awt_encoder* e) {
+  const awt_encoder_cfg& c = e->cfg;
+  const int64_t d = c.d_model, f = c.ffn_dim;
+  size_t off = 0;
+  auto add = [&](const std::string& name, std::initializer_list<int64_t> shape) {
+    awt_encoder::GradEntry g{name, off, {1, 1, 1}, (int)shape.size()};
+    int i = 0; size_t n = 1;
+    for (int64_t v : shape) { g.shape[i++] = v; n *= (size_t)v; }
+    e->glayout.push_back(g);
+    off += n;
+  };
+  add("conv1.weight", {d, c.n_mels, 3}); add("conv1.bias", {d}); add("conv2.weight", {d, d, 3}); add("conv2.bias", {d});
+  add("layer_norm.weight", {d}); add("layer_norm.bias", {d});
+  e->g_head = off;
+  for (int li = 0; li < c.n_layers; ++li) {
+    const std::string p = "layers." + std::to_string(li) + ".";
+    add(p + "self_attn.q_proj.weight", {d, d}); add(p + "self_attn.k_proj.weight", {d, d}); add(p + "self_attn.v_proj.weight", {d, d});
+    add(p + "self_attn.q_proj.bias", {d}); add(p + "self_attn.v_proj.bias", {d});
+    add(p + "self_attn.out_proj.weight", {d, d}); add(p + "self_attn.out_proj.bias", {d});
+    add(p + "self_attn_layer_norm.weight", {d}); add(p + "self_attn_layer_norm.bias", {d});
+    add(p + "fc1.weight", {f, d}); add(p + "fc1.bias", {f}); add(p + "fc2.weight", {d, f}); add(p + "fc2.bias", {d});
+    add(p + "final_layer_norm.weight", {d}); add(p + "final_layer_norm.bias", {d});
+    if (li == 0) e->g_per_layer = off - e->g_head;
+  }
+}
+}  // namespace
+
+extern "C" size_t awt_encoder_base_grad_count(const awt_encoder* e) {
+  if (!e || !e->train_base) return 0;
+  return e->g_head + (size_t)e->cfg.n_layers * e->g_per_layer;
+}
+extern "C" int awt_encoder_base_grad_params(const awt_encoder* e) { return (e && e->train_base) ? (int)e->glayout.size() : 0; }
+extern "C" int awt_encoder_base_grad_param(const awt_encoder* e, int index, const char** name, size_t* offset, int64_t* shape, int* rank) {
+  AWT_REQUIRE(e && e->train_base, AWT_ERR_STATE, "encoder_base_grad_param: encoder was not created with cfg.train_base");
+  AWT_REQUIRE(index >= 0 && index < (int)e->glayout.size() && name && offset && shape && rank, AWT_ERR_INVALID, "encoder_base_grad_param: bad argument");
+  const awt_encoder::GradEntry& g = e->glayout[index];
+  *name = g.name.c_str(); *offset = g.offset; *rank = g.rank;
+  for (int i = 0; i < 3; ++i) shape[i] = g.shape[i];
+  return AWT_OK;
+}
+
 extern "C" int awt_encoder_create(awt_ctx* c, const awt_encoder_cfg* cfg, awt_encoder** out) {
   AWT_REQUIRE(c && cfg && out, AWT_ERR_INVALID, "encoder_create: null argument");
   AWT_REQUIRE(cfg->d_model > 0 && cfg->d_model % 128 == 0 && cfg->d_model <= 1280, AWT_ERR_INVALID, "encoder_create: d_model must be a multiple of 128, <= 1280");
@@ -598,14 +661,21 @@ extern "C" int awt_encoder_create(awt_ctx* c, const awt_encoder_cfg* cfg, awt_en
               "encoder_create: backward_terms = 5 runs the MLP's backward GEMMs in f16f8: training mode, and no adapters on fc1 / fc2");
   AWT_REQUIRE(cfg->lora_rank >= 0 && cfg->lora_rank <= 32, AWT_ERR_INVALID, "encoder_create: lora_rank must be in 0..32");
   AWT_REQUIRE(cfg->lora_rank == 0 || cfg->lora_targets != 0, AWT_ERR_INVALID, "encoder_create: lora_rank > 0 needs lora_targets");
-  AWT_REQUIRE(!cfg->training || cfg->lora_rank > 0, AWT_ERR_INVALID, "encoder_create: training mode needs adapters (lora_rank > 0)");
+  AWT_REQUIRE(!cfg->training || cfg->lora_rank > 0 || cfg->train_base, AWT_ERR_INVALID, "encoder_create: training mode needs adapters (lora_rank > 0) or train_base");
+  AWT_REQUIRE(!cfg->train_base || cfg->training, AWT_ERR_INVALID, "encoder_create: train_base needs training mode");
+  AWT_REQUIRE(!cfg->train_base || cfg->lora_rank == 0, AWT_ERR_INVALID, "encoder_create: train_base trains the base weights themselves: no adapters in this mode (lora_rank must be 0)");
+  AWT_REQUIRE(!cfg->train_base || cfg->backward_terms != PREC_F16F8, AWT_ERR_INVALID,
+              "encoder_create: train_base forms its weight gradients from bf16 planes: backward_terms = 5 (f16f8 MLP backward) is not available in this mode");
   awt_encoder* e = new awt_encoder();
   e->ctx = c; e->cfg = *cfg; e->prec = cfg->mfma_terms; e->planes = (cfg->mfma_terms == PREC_BF16 || cfg->mfma_terms == PREC_F16) ? 1 : 2;
   e->chunk = cfg->chunk_clips > 0 ? cfg->chunk_clips : 64;
   e->mlp_f8 = cfg->backward_terms == PREC_F16F8;
+  e->train_base = cfg->train_base != 0;
   const int d = cfg->d_model, f = cfg->ffn_dim;
   int rc = alloc_linear(e, &e->conv1, d, conv1_k(cfg->n_mels));
   if (!rc && e->mlp_f8) rc = dev_alloc(e, (void**)&e->wt_tmp, (size_t)f * d * 4);
+  if (!rc && e->train_base) rc = dev_alloc(e, (void**)&e->wt_tmp, (size_t)d * d * 4);
+  for (int dt = 0; dt < 3 && !rc && e->train_base; ++dt) rc = alloc_planes(e, &e->conv2T[dt], d, d);
   if (!rc) rc = alloc_linear(e, &e->conv2, d, 3 * d);
   if (!rc) rc = dev_alloc(e, (void**)&e->pos, (size_t)cfg->n_ctx * d * 4);
   if (!rc) rc = dev_alloc(e, (void**)&e->lnf_g, (size_t)d * 4);
@@ -641,6 +711,7 @@ extern "C" int awt_encoder_create(awt_ctx* c, const awt_encoder_cfg* cfg, awt_en
     if (lora && !rc && (cfg->lora_targets & AWT_LORA_FC2)) rc = alloc_lora(e, &L.l2, 1, f, d);
   }
   if (rc) { awt_encoder_destroy(e); return rc; }
+  if (e->train_base) build_grad_layout(e);
   *out = e;
   return AWT_OK;
 }
@@ -664,7 +735,13 @@ extern "C" int awt_encoder_set_weight(awt_encoder* e, const char* name, const fl
   std::string nm(name);
   if (nm == "conv1.weight") { rc = check_shape(name, shape, rank, {d, c.n_mels, 3}); if (!rc) rc = pack(e->conv1.w, d, c.n_mels, 3, 0, 0); }
   else if (nm == "conv1.bias") { rc = check_shape(name, shape, rank, {d}); if (!rc) rc = copy_f32(e->conv1.bias, data, d, s); }
-  else if (nm == "conv2.weight") { rc = check_shape(name, shape, rank, {d, d, 3}); if (!rc) rc = pack(e->conv2.w, d, d, 3, 0, 0); }
+  else if (nm == "conv2.weight") {
+    rc = check_shape(name, shape, rank, {d, d, 3}); if (!rc) rc = pack(e->conv2.w, d, d, 3, 0, 0);
+    for (int dt = 0; dt < 3 && !rc && e->train_base; ++dt) {   // per tap: W[:, :, dt]^T, the weight of d h1 = d pre2 W2
+      rc = launch_conv_tap(e->ctx, data, d, d, dt, e->wt_tmp, s);
+      if (!rc) rc = launch_pack_weight_t(e->ctx, e->wt_tmp, d, d, e->conv2T[dt].ld, 0, 0, 1.0f, e->conv2T[dt].hi, e->conv2T[dt].lo, s);
+    }
+  }
   else if (nm == "conv2.bias") { rc = check_shape(name, shape, rank, {d}); if (!rc) rc = copy_f32(e->conv2.bias, data, d, s); }
   else if (nm == "embed_positions.weight") { rc = check_shape(name, shape, rank, {c.n_ctx, d}); if (!rc) rc = copy_f32(e->pos, data, (size_t)c.n_ctx * d, s); }
   else if (nm == "layer_norm.weight") { rc = check_shape(name, shape, rank, {d}); if (!rc) rc = copy_f32(e->lnf_g, data, d, s); }
@@ -945,7 +1022,7 @@ extern "C" int awt_encoder_forward_train(awt_encoder* e, const float* mel, int B
   AWT_REQUIRE(((uintptr_t)saved & 255) == 0, AWT_ERR_INVALID, "encoder_forward_train: saved buffer must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   TrainWs w = carve_train(e, (char*)saved, B);
-  rc = conv_stem(e, mel, B, w.a1, w.h1, w.layer[0].x_in, s); if (rc) return rc;
+  rc = conv_stem(e, mel, B, w.a1, w.h1, w.layer[0].x_in, s, e->train_base ? w.pre1 : nullptr); if (rc) return rc;
   for (int li = 0; li < e->cfg.n_layers; ++li) { rc = encoder_layer(e, e->layers[li], w.layer[li], B, true, s); if (rc) return rc; }
   return launch_layernorm(e->ctx, w.x_final, e->lnf_g, e->lnf_b, B * e->cfg.n_ctx, e->cfg.d_model, 1e-5f, hidden, Act{}, e->prec, s);
 }
@@ -973,7 +1050,8 @@ extern "C" int awt_encoder_backward_ex(awt_encoder* e, const float* d_hidden, in
   const bool exchange = (flags & AWT_BWD_ALLREDUCE) != 0;
   AWT_REQUIRE(e->cfg.training, AWT_ERR_STATE, "encoder_backward: encoder was not created with cfg.training");
   AWT_REQUIRE(saved_bytes >= awt_encoder_train_workspace_bytes(e, B), AWT_ERR_WORKSPACE, "encoder_backward: saved buffer too small");
-  AWT_REQUIRE(n_grads == awt_encoder_lora_grad_count(e), AWT_ERR_INVALID, "encoder_backward: lora_grads has the wrong element count");
+  const bool tb = e->train_base;
+  AWT_REQUIRE(n_grads == (tb ? awt_encoder_base_grad_count(e) : awt_encoder_lora_grad_count(e)), AWT_ERR_INVALID, "encoder_backward: the gradient buffer has the wrong element count");
   hipStream_t s = (hipStream_t)stream;
   const awt_encoder_cfg& c = e->cfg;
   const int S = c.n_ctx, d = c.d_model, f = c.ffn_dim, H = c.n_heads, terms = c.mfma_terms, r = c.lora_rank;
@@ -985,10 +1063,37 @@ extern "C" int awt_encoder_backward_ex(awt_encoder* e, const float* d_hidden, in
   const float gscale = ldexpf(1.0f, e->grad_scale_log2), inv_gscale = ldexpf(1.0f, -e->grad_scale_log2);
   const int M = B * S;
   const int64_t plane = (int64_t)M * d;
-  const float lscale = c.lora_alpha / (float)r;
+  const float lscale = r > 0 ? c.lora_alpha / (float)r : 0.f;
   TrainWs w = carve_train(e, (char*)saved, B);
-  const size_t per_layer = lora_grads_per_layer(c);
+  const size_t per_layer = tb ? e->g_per_layer : lora_grads_per_layer(c);
+  float* const layer_grads = lora_grads + (tb ? e->g_head : 0);     // train_base: the non-layer parameters come first (build_grad_layout)
   int rc;
+
+  // ---- cfg.train_base: gradients of the base parameters, each formed where its dY is live.  dW = dY^T X on the weight-gradient GEMM (wgrad.hip), bias and
+  //      LayerNorm gradients on the column-reduction row kernels; all of them leave divided by the pass' gradient scale.
+  const int wterms = (gterms == PREC_BF16 || e->planes == 1) ? 1 : 3;   // three products need the lo planes of the saved activations
+  float* const partial = w.partial;
+  auto dW = [&](const bf16_t* y0, const bf16_t* y1, int64_t ldy, int ycol, int N, bf16_t* const x[2], int64_t ldx, int xcol, int K, int rows, const WgradRowMap* map,
+                float* out, int64_t sn, int64_t sk) -> int {
+    const WgradOperand yo{y0, wterms == 3 ? y1 : nullptr, ldy, ycol}, xo{x[0], wterms == 3 ? x[1] : nullptr, ldx, xcol};
+    return launch_wgrad(e->ctx, yo, N, xo, K, rows, map, wterms, inv_gscale, out, sn, sk, accumulate, partial, w.partial_bytes, s);
+  };
+  auto dBias = [&](const bf16_t* y0, const bf16_t* y1, int64_t ldy, int ycol, int N, int rows, float* out) -> int {   // column sums of dY, <= 1024 columns per launch
+    for (int c0 = 0; c0 < N; c0 += 1024) {
+      const int n = std::min(1024, N - c0);
+      int rc2 = launch_param_grad(e->ctx, nullptr, y0 + ycol + c0, y1 ? y1 + ycol + c0 : nullptr, ldy, nullptr, rows, n, 0.f, inv_gscale, accumulate, nullptr, out + c0,
+                                  partial, s);
+      if (rc2) return rc2;
+    }
+    return AWT_OK;
+  };
+  auto dLN = [&](const float* dy, const float* x, float scale, float* dgamma) -> int {   // dgamma [d] then dbeta [d]
+    return launch_param_grad(e->ctx, dy, nullptr, nullptr, 0, x, M, d, 1e-5f, scale, accumulate, dgamma, dgamma + d, partial, s);
+  };
+  // offsets inside a layer's block (build_grad_layout)
+  const size_t dd = (size_t)d * d, o_qkvw = 0, o_qb = 3 * dd, o_vb = o_qb + d, o_ow = o_vb + d, o_ob = o_ow + dd, o_ln1 = o_ob + d, o_f1w = o_ln1 + 2 * d,
+               o_f1b = o_f1w + (size_t)f * d, o_f2w = o_f1b + f, o_f2b = o_f2w + (size_t)d * f, o_ln2 = o_f2b + d;
+  if (tb) { rc = dLN(d_hidden, w.x_final, 1.0f, lora_grads + e->g_head - 2 * d); if (rc) return rc; }   // the final layer_norm sees the unscaled gradient
 
   // One adapter group (adapters that share an input): du = dy B into w.du, then per adapter dA = lscale du^T x_in and dB = dy^T u at
   // `gp` (advanced).  Forward: u = lscale x_in A^T (saved), y = x_in W^T + b + u B^T.  The group's du stays in w.du for the caller's
@@ -1031,7 +1136,8 @@ extern "C" int awt_encoder_backward_ex(awt_encoder* e, const float* d_hidden, in
     Layer& L = e->layers[li];
     const LayerBufs& b = w.layer[li];
     // gradient layout of the layer: q, k, v, out, fc1, fc2 (enabled ones); the groups are visited fc2, fc1, out, qkv
-    float* g_qkv = lora_grads + (size_t)li * per_layer;
+    float* g_qkv = layer_grads + (size_t)li * per_layer;
+    float* const gl = g_qkv;   // train_base: the layer's block
     size_t n_qkv = 0;
     for (const Slot& sl : qkv_slots) if (c.lora_targets & sl.bit) n_qkv += (size_t)2 * r * d;
     float* g_out = g_qkv + n_qkv;
@@ -1039,6 +1145,10 @@ extern "C" int awt_encoder_backward_ex(awt_encoder* e, const float* d_hidden, in
     float* g_fc2 = g_fc1 + ((c.lora_targets & AWT_LORA_FC1) ? (size_t)r * d + (size_t)f * r : 0);
     // ---- MLP: dpre = ([dx | du2] [W2 | lscale A2]) * gelu'(pre) ; dln = [dpre | du1] [W1 | lscale A1] ; dx_mid = dx + LN2_bwd(dln)
     rc = group_backward(L.l2, w.dxp[0], w.dxp[1], d, d, fc2_slot, 1, b.ff, f, b.u2, g_fc2); if (rc) return rc;
+    if (tb) {
+      rc = dW(w.dxp[0], w.dxp[1], d, 0, d, b.ff, f, 0, f, M, nullptr, gl + o_f2w, f, 1); if (rc) return rc;
+      rc = dBias(w.dxp[0], w.dxp[1], d, 0, d, M, gl + o_f2b); if (rc) return rc;
+    }
     if (mlp8) {   // no fc1 / fc2 adapters in this mode (encoder_create): one K segment each
       GemmSeg s8 = seg_plain(dxp8, d, L.fc2T8, 0, d, M);
       GemmOut o{}; set_out(o, dpre8); o.ldo = f; o.n_valid = f; o.pre_hi = b.pre[0]; o.pre_lo = b.pre[1]; o.scale = 1.0f;
@@ -1055,6 +1165,10 @@ extern "C" int awt_encoder_backward_ex(awt_encoder* e, const float* d_hidden, in
       rc = launch_gemm(e->ctx, M, f, sg, L.l2.active ? 2 : 1, gterms, EPI_BF16_DGELU, o, s); if (rc) return rc;
     }
     rc = group_backward(L.l1, w.dpre[0], w.dpre[1], f, f, fc1_slot, 1, b.ln2, d, b.u1, g_fc1); if (rc) return rc;
+    if (tb) {
+      rc = dW(w.dpre[0], w.dpre[1], f, 0, f, b.ln2, d, 0, d, M, nullptr, gl + o_f1w, d, 1); if (rc) return rc;
+      rc = dBias(w.dpre[0], w.dpre[1], f, 0, f, M, gl + o_f1b); if (rc) return rc;
+    }
     {
       GemmSeg sg[2];
       sg[0] = seg_plain(w.dpre[0], w.dpre[1], f, L.fc1T, 0, f, M);
@@ -1063,10 +1177,15 @@ extern "C" int awt_encoder_backward_ex(awt_encoder* e, const float* d_hidden, in
       rc = launch_gemm(e->ctx, M, d, sg, L.l1.active ? 2 : 1, gterms, EPI_F32, o, s); if (rc) return rc;
     }
     }
+    if (tb) { rc = dLN(w.dln, b.x_mid, inv_gscale, gl + o_ln2); if (rc) return rc; }
     rc = launch_layernorm_bwd(e->ctx, w.dln, b.x_mid, L.ln2_g, dx, M, d, 1e-5f, dx_other, w.dxp[0], w.dxp[1], s); if (rc) return rc;
     std::swap(dx, dx_other);   // dx = d(loss)/d(x_mid)
     // ---- attention: datt = [dx_mid | duo] [Wo | lscale Ao] ; (dq, dk, dv) = attention_bwd
     rc = group_backward(L.lo_, w.dxp[0], w.dxp[1], d, d, out_slot, 1, b.att, d, b.uo, g_out); if (rc) return rc;
+    if (tb) {
+      rc = dW(w.dxp[0], w.dxp[1], d, 0, d, b.att, d, 0, d, M, nullptr, gl + o_ow, d, 1); if (rc) return rc;
+      rc = dBias(w.dxp[0], w.dxp[1], d, 0, d, M, gl + o_ob); if (rc) return rc;
+    }
     {
       GemmSeg sg[2];
       sg[0] = seg_plain(w.dxp[0], w.dxp[1], d, L.outT, 0, d, M);
@@ -1079,19 +1198,24 @@ extern "C" int awt_encoder_backward_ex(awt_encoder* e, const float* d_hidden, in
                               w.dqkv[0], w.dqkv[1], B, H, S, 0.125f, terms, gterms, s);
     if (rc) return rc;
     rc = group_backward(L.lq, w.dqkv[0], w.dqkv[1], 3 * d, 3 * d, qkv_slots, 3, b.ln1, d, b.u, g_qkv); if (rc) return rc;
+    if (tb) {   // q | k | v weights are adjacent in the block: one [3 d, d] product; k_proj has no bias
+      rc = dW(w.dqkv[0], w.dqkv[1], 3 * d, 0, 3 * d, b.ln1, d, 0, d, M, nullptr, gl + o_qkvw, d, 1); if (rc) return rc;
+      rc = dBias(w.dqkv[0], w.dqkv[1], 3 * d, 0, d, M, gl + o_qb); if (rc) return rc;
+      rc = dBias(w.dqkv[0], w.dqkv[1], 3 * d, 2 * d, d, M, gl + o_vb); if (rc) return rc;
+    }
     // ---- gradient exchange: layers [li, group_hi) are final -- average them over the ranks on the side stream while the
     //      lower layers' backward continues on `s`
     if (exchange) {
       const int G = e->comm_groups, Lr = c.n_layers;
       const int grp = (int)((int64_t)li * G / Lr);                       // layer li belongs to group grp (0 = lowest layers)
       const int lo_layer = (int)(((int64_t)grp * Lr + G - 1) / G);       // first layer of that group
-      if (li == lo_layer) {
+      if (li == lo_layer && !(tb && li == 0)) {   // train_base: the lowest group waits for the conv stem's gradients and takes the head with it
         const int hi_layer = (int)(((int64_t)(grp + 1) * Lr + G - 1) / G);
-        rc = comm_reduce_async(e->comm, lora_grads + (size_t)li * per_layer, (size_t)(hi_layer - li) * per_layer, s);
+        rc = comm_reduce_async(e->comm, layer_grads + (size_t)li * per_layer, (size_t)(hi_layer - li) * per_layer, s);
         if (rc) return rc;
       }
     }
-    if (li == 0) break;   // nothing below the first adapter needs a gradient
+    if (li == 0 && !tb) break;   // nothing below the first adapter needs a gradient
     // ---- dln = [dqkv | du] [Wqkv | lscale A]  ; dx_in = dx_mid + LN1_bwd(dln)
     {
       GemmSeg sg[2];
@@ -1100,10 +1224,55 @@ extern "C" int awt_encoder_backward_ex(awt_encoder* e, const float* d_hidden, in
       GemmOut o{}; o.f32 = w.dln; o.ldo = d; o.n_valid = d;
       rc = launch_gemm(e->ctx, M, d, sg, L.lq.active ? 2 : 1, gterms, EPI_F32, o, s); if (rc) return rc;
     }
+    if (tb) { rc = dLN(w.dln, b.x_in, inv_gscale, gl + o_ln1); if (rc) return rc; }
     rc = mlp8 ? launch_layernorm_bwd(e->ctx, w.dln, b.x_in, L.ln1_g, dx, M, d, 1e-5f, dx_other, nullptr, nullptr, s, 1.0f, &dxp8)     // feeds the layer below's fc2 backward GEMM
               : launch_layernorm_bwd(e->ctx, w.dln, b.x_in, L.ln1_g, dx, M, d, 1e-5f, dx_other, w.dxp[0], w.dxp[1], s);
     if (rc) return rc;
     std::swap(dx, dx_other);
+  }
+  if (tb) {
+    // ---- conv stem.  dx = d(loss)/d(x_0) (the position table gets no gradient).  conv2: x_0 = gelu(pre2) + pos, pre2 recomputed in fp32 by the forward's own GEMM;
+    //      conv1: h1 = gelu(pre1), pre1 kept by the forward.  Tap dt of conv2 reads h1 row 2 s + dt - 1 (zero outside the clip).
+    const int T = 2 * S, Mt = B * T, nm = c.n_mels, k1 = conv1_k(nm);
+    {
+      GemmSeg sg[3];
+      for (int dt = 0; dt < 3; ++dt) {
+        sg[dt] = seg_plain(w.h1[0], w.h1[1], d, e->conv2.w, (int64_t)dt * d, d, M);
+        sg[dt].rows_out = S; sg[dt].rows_in = T; sg[dt].row_mul = 2; sg[dt].row_add = dt - 1;
+      }
+      GemmOut o{}; o.f32 = w.dln; o.ldo = d; o.bias = e->conv2.bias; o.n_valid = d;
+      rc = launch_gemm(e->ctx, M, d, sg, 3, terms, EPI_F32, o, s); if (rc) return rc;
+    }
+    rc = launch_dgelu_planes(e->ctx, dx, w.dln, (int64_t)M * d, w.datt[0], w.datt[1], s); if (rc) return rc;     // d pre2
+    float* const g_c1w = lora_grads, *g_c1b = g_c1w + (size_t)d * nm * 3, *g_c2w = g_c1b + d, *g_c2b = g_c2w + 3 * dd;
+    for (int dt = 0; dt < 3; ++dt) {   // conv2.weight[n, c, dt]
+      const WgradRowMap map{S, T, 2, dt - 1};
+      rc = dW(w.datt[0], w.datt[1], d, 0, d, w.h1, d, 0, d, M, &map, g_c2w + dt, 3 * (int64_t)d, 3); if (rc) return rc;
+    }
+    rc = dBias(w.datt[0], w.datt[1], d, 0, d, M, g_c2b); if (rc) return rc;
+    // d pre1 [B T, d] viewed as [B S, 2 d]: even frames t = 2 j take tap 1 of row j; odd frames t = 2 j + 1 take tap 0 of row j + 1 and tap 2 of row j
+    bf16_t* const dh1[2] = {w.dqkv[0], w.dqkv[1]};
+    {
+      GemmSeg sg = seg_plain(w.datt[0], w.datt[1], d, e->conv2T[1], 0, d, M);
+      GemmOut o{}; o.hi = dh1[0]; o.lo = dh1[1]; o.ldo = 2 * d; o.n_valid = d; o.pre_hi = w.pre1[0]; o.pre_lo = w.pre1[1];
+      rc = launch_gemm(e->ctx, M, d, &sg, 1, gterms, EPI_BF16_DGELU, o, s); if (rc) return rc;
+      GemmSeg so[2];
+      so[0] = seg_plain(w.datt[0], w.datt[1], d, e->conv2T[0], 0, d, M);
+      so[0].rows_out = S; so[0].rows_in = S; so[0].row_mul = 1; so[0].row_add = 1;
+      so[1] = seg_plain(w.datt[0], w.datt[1], d, e->conv2T[2], 0, d, M);
+      GemmOut oo{}; oo.hi = dh1[0] + d; oo.lo = dh1[1] ? dh1[1] + d : nullptr; oo.ldo = 2 * d; oo.n_valid = d;
+      oo.pre_hi = w.pre1[0] + d; oo.pre_lo = w.pre1[1] ? w.pre1[1] + d : nullptr;
+      rc = launch_gemm(e->ctx, M, d, so, 2, gterms, EPI_BF16_DGELU, oo, s); if (rc) return rc;
+    }
+    for (int dt = 0; dt < 3; ++dt) {   // conv1.weight[n, c, dt]: the im2col row holds tap dt at columns dt n_mels ..
+      rc = dW(dh1[0], dh1[1], d, 0, d, w.a1, k1, dt * nm, nm, Mt, nullptr, g_c1w + dt, 3 * (int64_t)nm, 3); if (rc) return rc;
+    }
+    rc = dBias(dh1[0], dh1[1], d, 0, d, Mt, g_c1b); if (rc) return rc;
+    if (exchange) {   // the lowest layer group together with the non-layer parameters in front of it
+      const int G = e->comm_groups, Lr = c.n_layers;
+      const int hi_layer = (int)(((int64_t)Lr + G - 1) / G);
+      rc = comm_reduce_async(e->comm, lora_grads, e->g_head + (size_t)hi_layer * per_layer, s); if (rc) return rc;
+    }
   }
   if (exchange) { rc = comm_join(e->comm, s); if (rc) return rc; }
   return AWT_OK;

@@ -14,6 +14,7 @@
 // Everything is deterministic (no atomics).
 #include <vector>
 #include "common.h"
+#include "wgrad.h"
 
 // ------------------------------------------------------------------------------------------------ packed frozen weights
 struct awt_weight {
@@ -240,8 +241,10 @@ __device__ __forceinline__ float wave_sum(float x) {
 // lane + 64 j.  Partials land in [slab][2][d] and a second kernel adds the slabs in a fixed order (deterministic, no atomics).
 constexpr int kSlabRows = 256;
 constexpr int kColMaxChunks = 20;          // d <= 1280
+// The gradient rows come as fp32 `dy` [M, d] or, when dy_hi is given, as a bf16 plane pair of pitch ld (the backward pass' operand planes: bias gradients).
 __global__ __launch_bounds__(256) void ln_param_grad_kernel(const float* __restrict__ dy, const float* __restrict__ x, int M, int d, float eps,
-                                                            float* __restrict__ partial) {
+                                                            float* __restrict__ partial, const bf16_t* __restrict__ dy_hi = nullptr,
+                                                            const bf16_t* __restrict__ dy_lo = nullptr, int64_t ld = 0) {
   __shared__ float red[2][4][64 * 4];      // reused per chunk group of 4
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nch = (d + 63) / 64;
   const int r0 = blockIdx.x * kSlabRows, r1 = min(M, r0 + kSlabRows);
@@ -250,7 +253,9 @@ __global__ __launch_bounds__(256) void ln_param_grad_kernel(const float* __restr
   for (int j = 0; j < kColMaxChunks; ++j) dg[j] = db[j] = 0.f;
   for (int m = r0 + wave; m < r1; m += 4) {
     const float* xr = x ? x + (int64_t)m * d : nullptr;
-    const float* gr = dy + (int64_t)m * d;
+    const float* gr = dy_hi ? nullptr : dy + (int64_t)m * d;
+    const bf16_t* gh = dy_hi ? dy_hi + (int64_t)m * ld : nullptr;
+    const bf16_t* gl = dy_lo ? dy_lo + (int64_t)m * ld : nullptr;
     float mean = 0.f, rstd = 1.f;
     float xv[kColMaxChunks];
     if (xr) {
@@ -266,7 +271,7 @@ __global__ __launch_bounds__(256) void ln_param_grad_kernel(const float* __restr
 #pragma unroll
     for (int j = 0; j < kColMaxChunks; ++j) {
       const int c = lane + 64 * j;
-      if (j < nch && c < d) { const float g = gr[c]; db[j] += g; if (xr) dg[j] += g * (xv[j] - mean) * rstd; }
+      if (j < nch && c < d) { const float g = gh ? bf16_to_f32(gh[c]) + (gl ? bf16_to_f32(gl[c]) : 0.f) : gr[c]; db[j] += g; if (xr) dg[j] += g * (xv[j] - mean) * rstd; }
     }
   }
   // waves -> one partial row per slab
@@ -288,13 +293,15 @@ __global__ __launch_bounds__(256) void ln_param_grad_kernel(const float* __restr
     }
   }
 }
-__global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__ partial, int nslab, int d, float* out0, float* out1) {
+__global__ __launch_bounds__(256) void slab_sum_kernel(const float* __restrict__ partial, int nslab, int d, float* out0, float* out1, float scale = 1.0f,
+                                                       int accumulate = 0) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= d) return;
   float a = 0.f, b = 0.f;
   for (int s = 0; s < nslab; ++s) { a += partial[((int64_t)s * 2 + 0) * d + c]; b += partial[((int64_t)s * 2 + 1) * d + c]; }
-  if (out0) out0[c] = a;
-  if (out1) out1[c] = b;
+  a *= scale; b *= scale;
+  if (out0) out0[c] = accumulate ? out0[c] + a : a;
+  if (out1) out1[c] = accumulate ? out1[c] + b : b;
 }
 
 // Forward.  A workgroup owns QB = 16 query rows of one (batch, head) so that K and V are read once per 16 queries; its four waves
@@ -557,6 +564,16 @@ extern "C" int awt_op_layernorm_backward(awt_ctx* c, const float* dy, const floa
                                          int d, float eps, void* stream) {
   return launch_layernorm_bwd(c, dy, x, gamma, dres, M, d, eps, dx, nullptr, nullptr, (hipStream_t)stream);
 }
+size_t param_grad_partial_bytes(int M, int d) { return (size_t)((M + kSlabRows - 1) / kSlabRows) * 2 * (size_t)d * 4; }
+int launch_param_grad(awt_ctx* c, const float* dy, const bf16_t* dy_hi, const bf16_t* dy_lo, int64_t ld, const float* x, int M, int d, float eps,
+                      float scale, int accumulate, float* dgamma, float* dbeta, float* partial, hipStream_t s) {
+  AWT_REQUIRE(c && (dy || dy_hi) && partial && M > 0 && d > 0 && d <= 64 * kColMaxChunks, AWT_ERR_INVALID, "param_grad: bad argument (d <= 1280)");
+  const int nslab = (M + kSlabRows - 1) / kSlabRows;
+  hipLaunchKernelGGL(ln_param_grad_kernel, dim3(nslab), dim3(256), 0, s, dy, x, M, d, eps, partial, dy_hi, dy_lo, ld);
+  hipLaunchKernelGGL(slab_sum_kernel, dim3((d + 255) / 256), dim3(256), 0, s, (const float*)partial, nslab, d, dgamma, dbeta, scale, accumulate);
+  AWT_HIP_CHECK(hipGetLastError());
+  return AWT_OK;
+}
 extern "C" size_t awt_op_param_grad_workspace_bytes(int M, int d) { return (size_t)((M + kSlabRows - 1) / kSlabRows) * 2 * (size_t)d * 4; }
 extern "C" int awt_op_layernorm_param_grad(awt_ctx* c, const float* dy, const float* x, float* dgamma, float* dbeta, int M, int d, float eps,
                                            void* workspace, size_t ws_bytes, void* stream) {
@@ -564,8 +581,8 @@ extern "C" int awt_op_layernorm_param_grad(awt_ctx* c, const float* dy, const fl
               "op_layernorm_param_grad: bad argument (d <= 1280)");
   AWT_REQUIRE(ws_bytes >= awt_op_param_grad_workspace_bytes(M, d), AWT_ERR_WORKSPACE, "op_layernorm_param_grad: workspace too small");
   const int nslab = (M + kSlabRows - 1) / kSlabRows;
-  hipLaunchKernelGGL(ln_param_grad_kernel, dim3(nslab), dim3(256), 0, (hipStream_t)stream, dy, x, M, d, eps, (float*)workspace);
-  hipLaunchKernelGGL(slab_sum_kernel, dim3((d + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, nslab, d, dgamma, dbeta);
+  hipLaunchKernelGGL(ln_param_grad_kernel, dim3(nslab), dim3(256), 0, (hipStream_t)stream, dy, x, M, d, eps, (float*)workspace, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (int64_t)0);
+  hipLaunchKernelGGL(slab_sum_kernel, dim3((d + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, nslab, d, dgamma, dbeta, 1.0f, 0);
   AWT_HIP_CHECK(hipGetLastError());
   return AWT_OK;
 }
@@ -573,8 +590,8 @@ extern "C" int awt_op_column_sums(awt_ctx* c, const float* a, float* sums, int M
   AWT_REQUIRE(c && a && sums && workspace && M > 0 && d > 0 && d <= 64 * kColMaxChunks, AWT_ERR_INVALID, "op_column_sums: bad argument (d <= 1280)");
   AWT_REQUIRE(ws_bytes >= awt_op_param_grad_workspace_bytes(M, d), AWT_ERR_WORKSPACE, "op_column_sums: workspace too small");
   const int nslab = (M + kSlabRows - 1) / kSlabRows;
-  hipLaunchKernelGGL(ln_param_grad_kernel, dim3(nslab), dim3(256), 0, (hipStream_t)stream, a, (const float*)nullptr, M, d, 0.f, (float*)workspace);
-  hipLaunchKernelGGL(slab_sum_kernel, dim3((d + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, nslab, d, (float*)nullptr, sums);
+  hipLaunchKernelGGL(ln_param_grad_kernel, dim3(nslab), dim3(256), 0, (hipStream_t)stream, a, (const float*)nullptr, M, d, 0.f, (float*)workspace, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (int64_t)0);
+  hipLaunchKernelGGL(slab_sum_kernel, dim3((d + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, nslab, d, (float*)nullptr, sums, 1.0f, 0);
   AWT_HIP_CHECK(hipGetLastError());
   return AWT_OK;
 }

@@ -46,12 +46,13 @@ class BaseModelOutput:
         return (self.last_hidden_state,)[i]
 
 
-class _EncoderLoRAFunction(torch.autograd.Function):
-    """Native forward (activations kept in a library-owned layout) and native backward to the LoRA parameters.
-    The frozen base weights and the input features get no gradient (nothing below the first adapter needs one)."""
+class _EncoderTrainFunction(torch.autograd.Function):
+    """Native forward (activations kept in a library-owned layout) and native backward to the trainable parameters `params` -- the LoRA
+    adapters, or with `train_base` every base parameter but the position table -- given in the order of the library's flat gradient
+    buffer (NativeWhisperEncoder.grad_layout).  The input features get no gradient; in the adapter mode neither do the frozen base weights."""
 
     @staticmethod
-    def forward(ctx, enc, x, *lora_params):
+    def forward(ctx, enc, x, *params):
         L = _lib.lib()
         B, _, T = x.shape
         nbytes = L.awt_encoder_train_workspace_bytes(enc._handle, B)
@@ -60,48 +61,41 @@ class _EncoderLoRAFunction(torch.autograd.Function):
         with torch.cuda.device(x.device):
             _lib.check(L.awt_encoder_forward_train(enc._handle, _lib.ptr(x), B, T, _lib.ptr(out), _lib.ptr(saved), saved.numel(),
                                                    _lib.stream_handle()))
-        ctx.enc, ctx.saved, ctx.B = enc, saved, B
-        ctx.shapes = [tuple(p.shape) for p in lora_params]
+        ctx.enc, ctx.saved, ctx.B, ctx.n_params = enc, saved, B, len(params)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         enc, L = ctx.enc, _lib.lib()
         d_out = d_out.to(torch.float32).contiguous()
-        n = L.awt_encoder_lora_grad_count(enc._handle)
+        n = enc.grad_count()
         if enc.backward_precision == "f16f8":
             # fp16 planes want gradients of order one: the pass carries 2^k x the gradient (largest |d loss / d hidden| -> ~2^6) and the library divides
             # the adapter gradients by 2^k on the way out.  One scalar read-back per step; a zero or non-finite gradient keeps k = 0.
             amax = float(d_out.abs().max())
             k = 0 if not (amax > 0.0 and math.isfinite(amax)) else max(-60, min(60, 6 - math.frexp(amax)[1]))
             _lib.check(L.awt_encoder_set_grad_scale_log2(enc._handle, k))
-        if enc._grad_flat is not None:
-            # bound gradient buffer (bind_grad_buffer): the library writes / accumulates the adapter gradients straight into
-            # the flat buffer the parameters' .grad tensors are views of, and -- when asked -- averages them over the ranks
-            # inside the same call; autograd gets no tensors for them
+        bound = enc._grad_flat is not None
+        flat = enc._grad_flat if bound else torch.empty(n, dtype=torch.float32, device=d_out.device)
+        flags = 0
+        if bound:
+            # bound gradient buffer (bind_grad_buffer): the library writes / accumulates the gradients straight into the flat buffer the
+            # parameters' .grad tensors are views of, and -- when asked -- averages them over the ranks inside the same call; autograd
+            # gets no tensors for them
             flags = 0 if (enc._grad_fresh or enc._grad_params[0].grad is None) else _lib.BWD_ACCUMULATE
             if enc.grad_sync and enc._comm is not None:
                 flags |= _lib.BWD_ALLREDUCE
-            with torch.cuda.device(d_out.device):
-                _lib.check(L.awt_encoder_backward_ex(enc._handle, _lib.ptr(d_out), ctx.B, _lib.ptr(ctx.saved), ctx.saved.numel(),
-                                                     _lib.ptr(enc._grad_flat), n, flags, _lib.stream_handle()))
-            ctx.saved = None
+        with torch.cuda.device(d_out.device):
+            _lib.check(L.awt_encoder_backward_ex(enc._handle, _lib.ptr(d_out), ctx.B, _lib.ptr(ctx.saved), ctx.saved.numel(), _lib.ptr(flat), n, flags,
+                                                 _lib.stream_handle()))
+        ctx.saved = None
+        if bound:
             enc._grad_fresh = False
             for p, v in zip(enc._grad_params, enc._grad_views):
                 if p.grad is not v:
                     p.grad = v
-            return (None, None, *([None] * len(ctx.shapes)))
-        flat = torch.empty(n, dtype=torch.float32, device=d_out.device)
-        with torch.cuda.device(d_out.device):
-            _lib.check(L.awt_encoder_backward(enc._handle, _lib.ptr(d_out), ctx.B, _lib.ptr(ctx.saved), ctx.saved.numel(), _lib.ptr(flat), n,
-                                              _lib.stream_handle()))
-        ctx.saved = None
-        grads, off = [], 0
-        for shp in ctx.shapes:          # library order == lora_param order: per layer, per target (q, k, v): A then B
-            k = shp[0] * shp[1]
-            grads.append(flat[off: off + k].view(shp))
-            off += k
-        return (None, None, *grads)
+            return (None, None, *([None] * ctx.n_params))
+        return (None, None, *[flat[off: off + math.prod(shape)].view(shape) for _, off, shape in enc.grad_layout()])
 
 
 class _Leaf(nn.Module):
@@ -140,7 +134,7 @@ def _attach(root: nn.Module, dotted: str, p: nn.Parameter, epoch=None) -> None:
 class NativeWhisperEncoder(nn.Module):
     def __init__(self, cfg: EncoderConfig, precision: Optional[str] = None, lora: Optional[LoraSpec] = None,
                  device: str = "cuda", chunk_clips: int = 0, seed: Optional[int] = 0, init_profile: str = "hf",
-                 trainable: bool = False, backward_precision: Optional[str] = None, probe_clips=None):
+                 trainable: bool = False, backward_precision: Optional[str] = None, probe_clips=None, train_base: bool = False):
         super().__init__()
         # probe_clips (precision=None only): the caller's own audio -- 1-D float arrays / tensors at 16 kHz, e.g. a few clips of the data to be encoded --
         # joins the two synthetic clips of the load-time precision probe, so that the measured decision sees what the checkpoint does on real input
@@ -162,12 +156,20 @@ class NativeWhisperEncoder(nn.Module):
             raise ValueError("the native attention kernel is specialised for head_dim 64 (every Whisper size)")
         if trainable and precision not in ("bf16", "bf16x3"):
             raise ValueError("trainable=True keeps its activations as bf16 planes: precision must be 'bf16x3' or 'bf16'")
-        if trainable and lora is None:
+        if train_base and not trainable:
+            raise ValueError("train_base=True needs trainable=True")
+        if train_base and lora is not None:
+            raise ValueError("train_base=True trains the base weights themselves: no LoRA adapters in this mode")
+        if train_base and backward_precision == "f16f8":
+            raise ValueError("train_base=True forms its weight gradients from bf16 planes: backward_precision='f16f8' is not available in this mode")
+        if trainable and lora is None and not train_base:
             raise ValueError("trainable=True needs LoRA adapters")
         self.cfg = cfg
         self.precision = precision
         self.lora = lora
         self.trainable = trainable
+        self.train_base = train_base
+        self._base_layout = None
         self.config = SimpleNamespace(d_model=cfg.d_model, encoder_layers=cfg.layers, encoder_attention_heads=cfg.heads,
                                       encoder_ffn_dim=cfg.ffn, num_mel_bins=cfg.n_mels,
                                       max_source_positions=cfg.max_source_positions)
@@ -176,7 +178,8 @@ class NativeWhisperEncoder(nn.Module):
         base = init_encoder_weights(cfg, seed or 0, init_profile) if seed is not None else None
         for name, shape in encoder_param_shapes(cfg):
             t = torch.from_numpy(base[name]) if base is not None else torch.zeros(shape)
-            _attach(self, name, nn.Parameter(t.to(dev), requires_grad=False), self._epoch)
+            # full-parameter mode: every base parameter trains except the sinusoid table (HF: embed_positions.requires_grad_(False))
+            _attach(self, name, nn.Parameter(t.to(dev), requires_grad=train_base and name != "embed_positions.weight"), self._epoch)
         if lora is not None:
             lw = init_lora_weights(cfg, lora, seed or 0) if seed is not None else None
             for name, shape in lora_param_shapes(cfg, lora):
@@ -326,7 +329,8 @@ class NativeWhisperEncoder(nn.Module):
         cfg = _lib.EncoderCfg(self.cfg.d_model, self.cfg.layers, self.cfg.heads, self.cfg.ffn, self.cfg.n_mels,
                               self.cfg.max_source_positions, PRECISIONS[self.precision],
                               self.lora.r if self.lora else 0, float(self.lora.alpha) if self.lora else 0.0, bits, self._chunk,
-                              1 if self.trainable else 0, PRECISIONS[self.backward_precision] if self.backward_precision else 0)
+                              1 if self.trainable else 0, PRECISIONS[self.backward_precision] if self.backward_precision else 0,
+                              1 if self.train_base else 0)
         out = C.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(L.awt_encoder_create(_lib.ctx(self.device), C.byref(cfg), C.byref(out)))
@@ -390,6 +394,47 @@ class NativeWhisperEncoder(nn.Module):
                 params += [leaf.lora_A, leaf.lora_B]
         return params
 
+    def base_grad_layout(self) -> list:
+        """Full-parameter mode: [(state-dict key, element offset, shape)] of the flat gradient buffer, as the library reports it
+        (include/awt.h: awt_encoder_base_grad_param) -- the non-layer parameters, then one contiguous block per layer."""
+        if not self.train_base:
+            raise ValueError("base_grad_layout needs train_base=True")
+        if self._base_layout is None:
+            self._ensure_handle()
+            L = _lib.lib()
+            out = []
+            for i in range(L.awt_encoder_base_grad_params(self._handle)):
+                name, off, shape, rank = C.c_char_p(), C.c_size_t(), (C.c_int64 * 3)(), C.c_int()
+                _lib.check(L.awt_encoder_base_grad_param(self._handle, i, C.byref(name), C.byref(off), shape, C.byref(rank)))
+                out.append((name.value.decode(), int(off.value), tuple(int(shape[j]) for j in range(rank.value))))
+            self._base_layout = out
+        return self._base_layout
+
+    def base_grad_count(self) -> int:
+        self._ensure_handle()
+        return int(_lib.lib().awt_encoder_base_grad_count(self._handle))
+
+    def trainable_parameters_library_order(self) -> list:
+        """The parameters whose gradients the native backward produces, in the order of its flat gradient buffer."""
+        if not self.train_base:
+            return self.lora_parameters_library_order()
+        return [self.get_parameter(name) for name, _, _ in self.base_grad_layout()]
+
+    def grad_layout(self) -> list:
+        """[(state-dict key, element offset, shape)] of the flat gradient buffer the native backward writes, in buffer order: the library's
+        own report in the full-parameter mode; for adapters include/awt.h's documented order (per layer, per target: lora_A then lora_B)."""
+        if self.train_base:
+            return self.base_grad_layout()
+        ids = {id(p): n for n, p in self.named_parameters()}
+        out, off = [], 0
+        for p in self.lora_parameters_library_order():
+            out.append((ids[id(p)], off, tuple(p.shape)))
+            off += p.numel()
+        return out
+
+    def grad_count(self) -> int:
+        return self.base_grad_count() if self.train_base else self.lora_grad_count()
+
     def lora_grad_count(self) -> int:
         self._ensure_handle()
         return int(_lib.lib().awt_encoder_lora_grad_count(self._handle))
@@ -400,19 +445,17 @@ class NativeWhisperEncoder(nn.Module):
         `zero_adapter_grads()`), and the data-parallel exchange reduces it in place (dist.FlatGradBucket / set_comm)."""
         if not self.trainable:
             raise ValueError("bind_grad_buffer needs trainable=True")
-        n = self.lora_grad_count()
+        n = self.grad_count()
         if flat is None:
             flat = torch.zeros(n, dtype=torch.float32, device=self.device)
         if flat.numel() != n or flat.dtype != torch.float32 or not flat.is_contiguous() or flat.device != self.device:
             raise ValueError(f"flat must be a contiguous float32 tensor of {n} elements on {self.device}")
         self._grad_flat = flat
-        self._grad_params = self.lora_parameters_library_order()
-        self._grad_views, off = [], 0
-        for p in self._grad_params:
-            k = p.numel()
-            self._grad_views.append(flat[off: off + k].view_as(p))
+        self._grad_params = self.trainable_parameters_library_order()
+        self._grad_views = []
+        for p, (_, off, shape) in zip(self._grad_params, self.grad_layout()):      # offsets and shapes as the library lays the buffer out
+            self._grad_views.append(flat[off: off + p.numel()].view(shape))
             p.grad = self._grad_views[-1]
-            off += k
         self._grad_fresh = True
         return flat
 
@@ -466,8 +509,7 @@ class NativeWhisperEncoder(nn.Module):
         self.sync_weights()
         L = _lib.lib()
         if self.trainable and torch.is_grad_enabled():
-            params = self.lora_parameters_library_order()
-            return BaseModelOutput(last_hidden_state=_EncoderLoRAFunction.apply(self, x, *params))
+            return BaseModelOutput(last_hidden_state=_EncoderTrainFunction.apply(self, x, *self.trainable_parameters_library_order()))
         ws = self._workspace(L.awt_encoder_workspace_bytes(self._handle, B))
         out = torch.empty((B, self.cfg.max_source_positions, self.cfg.d_model), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):

@@ -157,15 +157,21 @@ class WhisperLoRAModel(nn.Module):
     def __init__(self, cfg: EncoderConfig, lora: Optional[LoraSpec], precision: Optional[str] = "bf16x3", device: str = "cuda", decoder_layers: Optional[int] = None,
                  seed: int = 0, vocab: int = WHISPER_VOCAB, decoder_autocast: Optional[torch.dtype] = None, native_cross_kv: bool = True,
                  max_target_positions: int = 448, backward_precision: Optional[str] = None, native_decoder: bool = True,
-                 decoder_heads: Optional[int] = None, decoder_ffn: Optional[int] = None, decoder_lora: Optional[LoraSpec] = None):
+                 decoder_heads: Optional[int] = None, decoder_ffn: Optional[int] = None, decoder_lora: Optional[LoraSpec] = None,
+                 train_encoder: bool = False):
         super().__init__()
+        # train_encoder: full-parameter fine-tuning of the encoder, as the reference's fineTune.py trains it (every encoder parameter but the
+        # sinusoid table; encoder.NativeWhisperEncoder train_base=True) -- no encoder adapters then; the decoder stays frozen or takes decoder_lora
+        if train_encoder and lora is not None:
+            raise ValueError("train_encoder=True trains the encoder's base weights: pass lora=None (decoder_lora is still available)")
+        self.train_encoder = train_encoder
         # decoder_lora: adapters on the decoder's self- / cross-attention q_proj, v_proj as well (scope row f1: "+ LoRA on decoder"; the
         # reference fine-tunes every decoder parameter, AB/fineTune.py:131,186-199) -- native decoder only
         if decoder_lora is not None and (not native_decoder or decoder_autocast is not None):
             raise ValueError("decoder_lora needs the native decoder (native_decoder=True, no decoder_autocast)")
         # lora=None: inference only (the reference's wavToWhisper.py / fineTuneMidiTester.py use): the encoder is not trainable and may
         # run any inference precision (precision=None picks it from the checkpoint, encoder.NativeWhisperEncoder)
-        trainable = lora is not None
+        trainable = lora is not None or train_encoder
         # native_decoder=True (default): decoder, tied projection and cross-entropy run on libawt as well (native_decoder.NativeWhisperDecoder,
         # scope row f1); False keeps the stock-PyTorch decoder (the restatement pinned to HF by tests/golden/decoder.npz) around the
         # native encoder -- kept as the A/B reference of the native one (tests/test_gpu_native_decoder.py)
@@ -177,7 +183,7 @@ class WhisperLoRAModel(nn.Module):
         self.decoder_autocast = decoder_autocast
         self.native_cross_kv = native_cross_kv   # False: every decoder matmul on torch (the pre-fusion path, kept for A/B tests)
         self.encoder = NativeWhisperEncoder(cfg, precision=precision, lora=lora, device=device, seed=seed, trainable=trainable,
-                                            backward_precision=backward_precision)
+                                            backward_precision=backward_precision, train_base=train_encoder)
         self.precision = self.encoder.precision if precision is None else precision
         dheads, dffn = decoder_heads or cfg.heads, decoder_ffn or cfg.ffn
         torch.manual_seed(seed)
@@ -201,6 +207,11 @@ class WhisperLoRAModel(nn.Module):
         """Every trainable parameter: the encoder's adapters, then the decoder's (if any)."""
         return [p for n, p in self.encoder.named_parameters() if "lora_" in n] + [p for n, p in self.decoder.named_parameters() if "lora_" in n]
 
+    def trainable_parameters(self) -> List[nn.Parameter]:
+        """What the optimizer updates: the encoder's trainable parameters (its adapters, or with train_encoder every base parameter but the
+        position table), then the decoder's adapters (if any)."""
+        return [p for p in self.encoder.parameters() if p.requires_grad] + [p for n, p in self.decoder.named_parameters() if "lora_" in n]
+
     @classmethod
     def from_pretrained(cls, path, lora: Optional[LoraSpec] = None, precision: Optional[str] = None, device: str = "cuda", **kw) -> "WhisperLoRAModel":
         """`WhisperForConditionalGeneration.from_pretrained(model_path)` for a LOCAL checkpoint directory, as the reference's inference
@@ -211,7 +222,7 @@ class WhisperLoRAModel(nn.Module):
         from .checkpoint import encoder_config_from_hf, load_checkpoint_dir
         hf, enc_sd, dec_sd = load_checkpoint_dir(path)
         cfg = encoder_config_from_hf(hf, os.path.basename(os.path.normpath(os.fspath(path))))
-        if precision is None and lora is not None:
+        if precision is None and (lora is not None or kw.get("train_encoder")):
             precision = "bf16x3"
         model = cls(cfg, lora, precision=precision, device=device, decoder_layers=int(hf.get("decoder_layers", cfg.layers)),
                     vocab=int(hf.get("vocab_size", WHISPER_VOCAB)), max_target_positions=int(hf.get("max_target_positions", 448)),
@@ -564,7 +575,7 @@ class Seq2SeqTrainer:
         self.args, self.model = args, model
         self.train_dataset, self.eval_dataset = train_dataset, eval_dataset
         self.data_collator, self.compute_metrics, self.tokenizer = data_collator, compute_metrics, tokenizer
-        params = model.lora_parameters()
+        params = model.trainable_parameters() if hasattr(model, "trainable_parameters") else model.lora_parameters()
         self.optimizer = torch.optim.AdamW(params, lr=args.learning_rate, betas=(args.adam_beta1, args.adam_beta2),
                                            eps=args.adam_epsilon, weight_decay=args.weight_decay)
         self.scheduler = torch.optim.lr_scheduler.LambdaLR(self.optimizer, lambda s: linear_schedule(s, args.warmup_steps, args.max_steps))
@@ -573,7 +584,7 @@ class Seq2SeqTrainer:
         enc = getattr(model, "encoder", None)
         self.native = enc if hasattr(enc, "bind_grad_buffer") and getattr(enc, "trainable", False) else None
         if self.native is not None:
-            first = self.native.lora_parameters_library_order()
+            first = self.native.trainable_parameters_library_order()   # adapters, or the base parameters of the full-parameter mode
             ids = {id(p) for p in first}
             rest = [p for p in params if id(p) not in ids]
             self.n_native = sum(p.numel() for p in first)
@@ -728,7 +739,8 @@ class Seq2SeqTrainer:
                 better = best is None or (score > best if self.args.greater_is_better and key in m else score < best)
                 if better:
                     best = score
-                    best_state = ({k: v.detach().clone() for k, v in self.model.encoder.state_dict().items() if "lora_" in k},
+                    full_enc = getattr(self.model, "train_encoder", False)       # full-parameter mode: the trained state is the encoder itself
+                    best_state = ({k: v.detach().clone() for k, v in self.model.encoder.state_dict().items() if full_enc or "lora_" in k},
                                   {k: v.detach().clone() for k, v in self.model.decoder.state_dict().items() if "lora_" in k})
             if self.args.save_steps and self.global_step % self.args.save_steps == 0:
                 self.save_model()
@@ -746,6 +758,14 @@ class Seq2SeqTrainer:
         adapters merged into the base) that `WhisperLoRAModel.from_pretrained` -- and the reference's wavToWhisper.py:47 -- load by path."""
         out = output_dir or self.args.output_dir
         os.makedirs(out, exist_ok=True)
+        if getattr(self.model, "train_encoder", False):
+            # full-parameter mode: the base weights themselves changed, so the checkpoint is the whole directory (what the reference's
+            # trainer.save_model() writes); there is no adapter-only file to claim, except the decoder's adapters if it has any
+            self.model.save_pretrained(out)
+            dsd = {"decoder." + k: v.detach().cpu() for k, v in self.model.decoder.state_dict().items() if "lora_" in k}
+            if dsd:
+                torch.save({"lora": dsd, "encoder": "full"}, os.path.join(out, "decoder_lora_adapters.pt"))
+            return out
         if full:
             self.model.save_pretrained(out)
         sd = {k: v.detach().cpu() for k, v in self.model.encoder.state_dict().items() if "lora_" in k}

@@ -57,3 +57,32 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, precision: str 
         _lib.check(L.awt_op_attention(_lib.ctx(q.device), _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), B, H, S,
                                       terms, _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
     return o
+
+
+def weight_grad(dy: torch.Tensor, x: torch.Tensor, n: Optional[int] = None, k: Optional[int] = None, ycol: int = 0, xcol: int = 0,
+                precision: str = "bf16x3", scale: float = 1.0, out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                row_map: Optional[tuple] = None) -> torch.Tensor:
+    """dW[n, k] = scale * sum_m dy[m, ycol + n] x[row(m), xcol + k] on the MFMA weight-gradient GEMM (include/awt.h: awt_op_weight_grad).
+    dy [M, ldy], x [rows, ldx] fp32 device tensors; n / k default to the full widths.  row_map = (rows_out, rows_in, row_mul, row_add): the
+    conv-stem row map (rows outside [0, rows_in) of their group read as zero).  `out` [n, k] (any strides) is written, or added to with `accumulate`."""
+    if precision not in ("bf16", "bf16x3"):
+        raise ValueError("weight_grad: precision must be 'bf16' or 'bf16x3'")
+    dy, x = dy.float().contiguous(), x.float().contiguous()
+    M, ldy = dy.shape
+    rows_x, ldx = x.shape
+    n = ldy - ycol if n is None else n
+    k = ldx - xcol if k is None else k
+    if out is None:
+        if accumulate:
+            raise ValueError("weight_grad: accumulate needs out")
+        out = torch.empty((n, k), dtype=torch.float32, device=dy.device)
+    if out.shape != (n, k) or out.dtype != torch.float32 or out.device != dy.device:
+        raise ValueError(f"weight_grad: out must be a float32 [{n}, {k}] tensor on {dy.device}")
+    ro, ri, rm, ra = row_map if row_map is not None else (0, 0, 1, 0)
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_op_weight_grad_workspace_bytes(M, rows_x, ldy, ldx, n, k), dy.device)
+    with torch.cuda.device(dy.device):
+        _lib.check(L.awt_op_weight_grad(_lib.ctx(dy.device), _lib.ptr(dy), ldy, ycol, n, _lib.ptr(x), rows_x, ldx, xcol, k, M, ro, ri, rm, ra,
+                                        1 if precision == "bf16" else 3, float(scale), int(accumulate), out.data_ptr(), out.stride(0), out.stride(1),
+                                        _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
+    return out
