@@ -123,7 +123,7 @@ typedef struct awt_encoder_cfg {
                                5 f16f8: fp16 plane + two e4m3 planes, the two cross terms on the block-scaled fp8 MFMA: two
                                  MFMA-equivalents per fragment pair (2^-16 per operand); inference only.  Its attention keeps
                                  the cross terms of q k^T and runs P V as one fp16 product           */
-  int32_t lora_rank;        /* 0 = no adapters; else 1..64                                                 */
+  int32_t lora_rank;        /* 0 = no adapters; else 1..32 (the adapter-gradient kernels' width)           */
   float lora_alpha;         /* adapter scale = lora_alpha / lora_rank                                      */
   uint32_t lora_targets;    /* bit mask of AWT_LORA_*                                                      */
   int32_t chunk_clips;      /* clips processed per kernel wave (0 = library default)                       */
@@ -311,7 +311,9 @@ int awt_bmm_kmajor(awt_ctx* c, const float* a1, const float* a2, int K1, int64_t
  * ds[r, :] = scale * p[r, :] * (dp[r, :] - sum_c p[r, c] dp[r, c]) (ds may alias dp)                      HF:modeling_whisper.py:226-231 */
 int awt_op_softmax_rows(awt_ctx* c, const float* s, float* p, int rows, int cols, int64_t ld, float scale, void* stream);
 int awt_op_softmax_rows_backward(awt_ctx* c, const float* p, const float* dp, float* ds, int rows, int cols, int64_t ld, float scale, void* stream);
-/* x[m, :] = embed_tokens[ids[m], :] + embed_positions[pos0 + m % L, :]     HF:modeling_whisper.py:756-770 */
+/* x[m, :] = embed_tokens[ids[m], :] + embed_positions[pos0 + m % L, :]     HF:modeling_whisper.py:756-770
+ * One fp32 add per element.  d % 4 == 0.  An id outside [0, vocab) is clamped to the nearest valid row (0 or vocab - 1): the call cannot
+ * fail without a synchronisation, and it never reads outside the table.  pos must hold pos0 + L rows. */
 int awt_op_embed(awt_ctx* c, const int64_t* ids, const float* tok, const float* pos, float* x, int M, int L, int d, int pos0, int vocab,
                  void* stream);
 int awt_op_gelu(awt_ctx* c, const float* x, float* y, int64_t n, void* stream);                          /* exact erf GELU */
@@ -441,6 +443,10 @@ int awt_op_dtw(awt_ctx* c, const float* matrix, int clips, int T, int frames, co
  * (training; 8 waves when the grid has at least 256 eight-wave workgroups, else 4); 4 / 5 = every cross term, the e4m3 cross terms of
  * P V included, on 4 / 8 waves; 6 = P V as one fp16 product on 4 waves (what 0 selects for inference).  Other values are refused.
  * Only dropping P V's cross terms changes results (within the tolerances of DESIGN.md section 3); the number of waves is bit-neutral.
+ * "attn_qt": query tiles per wave of the bf16 / fp16 / bf16x3 / fp16x3 attention kernel, so that tests can drive both instantiations on
+ * small shapes: 0 = chosen from the grid size (default: one tile, 128 queries per workgroup, on grids that two tiles would leave under
+ * or unevenly filling the device; else two, 256 queries), 1 / 2 = force that instantiation.  Other values are refused.  The f16f8
+ * kernel ("attn_shape") is not affected.
  * "gemm_pp": the persistent 256 x 256 eight-wave "ping-pong" f16f8 GEMM (csrc/gemm_pp.h: both operands by LDS-DMA, split-line
  * activations, 16 x 16 MFMAs, one workgroup per CU walking its tiles): 0 = off, 1 = automatic (default: inference launches of at
  * least one tile per CU whose tile count fills its rounds of persistent workgroups to 5/6 or better, on weights that are not fp16-exact), 2 = wherever it applies (N % 256 == 0, K % 64 == 0, K >= 128, no adapter; also

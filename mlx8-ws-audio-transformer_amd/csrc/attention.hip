@@ -287,6 +287,9 @@ int launch_t(const AttnArgs& a, hipStream_t s) {
 
 }  // namespace
 
+static int g_attn_qt = 0;   // awt_tuning_set("attn_qt"): 0 = the grid rule below, 1 / 2 = that many query tiles per wave
+void awt_attn_force_qt(int v) { g_attn_qt = v; }
+
 int launch_attention(awt_ctx* c, const bf16_t* q_hi, const bf16_t* q_lo, const bf16_t* k_hi, const bf16_t* k_lo,
                      const bf16_t* v_hi, const bf16_t* v_lo, bf16_t* o_hi, bf16_t* o_lo, float* o_f32, float* lse, int B, int H,
                      int S, int prec, hipStream_t s) {
@@ -302,8 +305,9 @@ int launch_attention(awt_ctx* c, const bf16_t* q_hi, const bf16_t* q_lo, const b
   // grids under one round, and grids whose last round would be mostly empty (Whisper-tiny at B = 32: 3 rounds vs 2.75).
   const int64_t wg2 = (int64_t)((S + 255) / 256) * B * H, wg1 = (int64_t)((S + 127) / 128) * B * H;
   const double cost2 = (double)((wg2 + 511) / 512), cost1 = 0.55 * (double)((wg1 + 511) / 512);
-  if (prec == PREC_F16X3) return cost1 < cost2 ? launch_t<3, 1, true>(a, s) : launch_t<3, 2, true>(a, s);
-  if (prec == PREC_F16) return cost1 < cost2 ? launch_t<1, 1, true>(a, s) : launch_t<1, 2, true>(a, s);
-  if (cost1 < cost2) return terms == 3 ? launch_t<3, 1>(a, s) : launch_t<1, 1>(a, s);
+  const bool qt1 = g_attn_qt ? g_attn_qt == 1 : cost1 < cost2;
+  if (prec == PREC_F16X3) return qt1 ? launch_t<3, 1, true>(a, s) : launch_t<3, 2, true>(a, s);
+  if (prec == PREC_F16) return qt1 ? launch_t<1, 1, true>(a, s) : launch_t<1, 2, true>(a, s);
+  if (qt1) return terms == 3 ? launch_t<3, 1>(a, s) : launch_t<1, 1>(a, s);
   return terms == 3 ? launch_t<3, 2>(a, s) : launch_t<1, 2>(a, s);
 }

@@ -72,6 +72,11 @@ extern "C" int awt_tuning_set(const char* key, int value) {
     awt_attn_force_shape(value);
     return AWT_OK;
   }
+  if (!strcmp(key, "attn_qt")) {
+    AWT_REQUIRE(value >= 0 && value <= 2, AWT_ERR_INVALID, "tuning_set: attn_qt must be 0 (auto), 1 or 2");
+    awt_attn_force_qt(value);
+    return AWT_OK;
+  }
   AWT_REQUIRE(false, AWT_ERR_INVALID, "tuning_set: unknown key");
 }
 

@@ -412,6 +412,7 @@ int logmel_prepare_impl(awt_ctx* c, int n_fft, int n_mels, double f_min, double 
 int resample_prepare_impl(awt_ctx* c, int sr_in, int sr_out);
 void awt_free_tables(awt_ctx* c);
 void awt_attn_force_shape(int v);   // f16f8 attention form (tuning knob "attn_shape"): 0 auto, 4 / 5 / 6 (attention_f8.hip)
+void awt_attn_force_qt(int v);      // query tiles per wave (tuning knob "attn_qt"): 0 auto, 1 / 2 (attention.hip)
 void awt_gemm_set_gm(int v);       // row panels per tile group of the GEMM tile order (0 = default)
 bool attention_f16f8_reads_v8(bool with_lse);   // whether v's e4m3 images must be written for the f16f8 attention form selected now
 void awt_gemm_force_tile(int t);  // 0 auto, 64 / 128 / 256: tuning / tests (awt_tuning_set)

@@ -149,6 +149,31 @@ def attention_small_backward(q, ldq, k, ldk, v, ldv, o, dout, lse, dq, dk, dv, B
             float(drop_p), int(seed), _lib.stream_handle()))
 
 
+def attention_cached(q, ldq, cache, T, H, Lq):
+    """Causal attention of Lq new query rows per cache row over the first T positions of a decode cache [rows, Tmax, 2 H 64] (keys in the first
+    H * 64 columns, values in the rest; positions >= T are not read).  q: (tensor, column offset) as in attention_small; returns o [rows * Lq, H * 64]."""
+    qt, qo = q
+    rows, Tmax, width = cache.shape
+    d = H * 64
+    o = torch.empty((rows * Lq, d), dtype=torch.float32, device=qt.device)
+    with torch.cuda.device(qt.device):
+        _lib.check(_lib.lib().awt_op_attention_cached(_ctx(qt), qt.data_ptr() + 4 * qo, ldq, cache.data_ptr(), cache.data_ptr() + 4 * d, width, Tmax * width,
+                                                      _lib.ptr(o), d, rows, H, Lq, T, _lib.stream_handle()))
+    return o
+
+
+def embed(ids: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, position_offset: int = 0) -> torch.Tensor:
+    """ids [B, L] -> x [B * L, d] = tok[ids] + pos[position_offset + column] (awt_op_embed; an id outside [0, vocab) reads the nearest valid row)."""
+    B, L = ids.shape
+    vocab, d = tok.shape
+    ids = ids.to(device=tok.device, dtype=torch.int64).contiguous()
+    x = torch.empty((B * L, d), dtype=torch.float32, device=tok.device)
+    with torch.cuda.device(tok.device):
+        _lib.check(_lib.lib().awt_op_embed(_ctx(tok), _lib.ptr(ids), _lib.ptr(tok), _lib.ptr(pos), _lib.ptr(x), B * L, L, d, int(position_offset), vocab,
+                                           _lib.stream_handle()))
+    return x
+
+
 def gemm(x: torch.Tensor, w: torch.Tensor, precision: str = "bf16x3") -> torch.Tensor:
     """x [M, K] @ w [N, K]^T on libawt's MFMA GEMM (`awt_op_linear`): K zero-padded to a multiple of 64, N to a multiple of 128."""
     from . import ops
@@ -355,12 +380,7 @@ class DecodeCache:
         if T > self.Tmax:
             raise ValueError(f"decode cache holds {self.Tmax} positions, step needs {T}")
         self.buf[i, :, self.T:T].copy_(qkv.view(self.rows, L, 3 * d)[:, :, d:])
-        c = self.buf[i]
-        o = torch.empty((self.rows * L, d), dtype=torch.float32, device=qkv.device)
-        with torch.cuda.device(qkv.device):
-            _lib.check(_lib.lib().awt_op_attention_cached(_ctx(qkv), _lib.ptr(qkv), 3 * d, c.data_ptr(), c.data_ptr() + 4 * d, 2 * d, self.Tmax * 2 * d,
-                                                          _lib.ptr(o), d, self.rows, d // 64, L, T, _lib.stream_handle()))
-        return o
+        return attention_cached((qkv, 0), 3 * d, self.buf[i], T, d // 64, L)
 
     def gather(self, parent: torch.Tensor, src: Optional["DecodeCache"] = None) -> None:
         """Row r of this cache <- row parent[r] (int32, on the device) of `src` (default: this cache itself, through the spare buffer)."""
@@ -537,13 +557,7 @@ class NativeWhisperDecoder(nn.Module):
         return kv
 
     def _embed(self, ids: torch.Tensor, position_offset: int) -> torch.Tensor:
-        B, L = ids.shape
-        ids = ids.to(device=self.embed_tokens.weight.device, dtype=torch.int64).contiguous()
-        x = torch.empty((B * L, self.d), dtype=torch.float32, device=ids.device)
-        with torch.cuda.device(ids.device):
-            _lib.check(_lib.lib().awt_op_embed(_lib.ctx(ids.device), _lib.ptr(ids), _lib.ptr(self.embed_tokens.weight), _lib.ptr(self.embed_positions.weight),
-                                               _lib.ptr(x), B * L, L, self.d, int(position_offset), self.vocab, _lib.stream_handle()))
-        return x
+        return embed(ids, self.embed_tokens.weight, self.embed_positions.weight, position_offset)
 
     def _run(self, ids: torch.Tensor, kv: torch.Tensor, S: int, save: Optional[list], caches=None, position_offset: int = 0,
              cross_group: int = 1) -> torch.Tensor:

@@ -7,7 +7,7 @@ import torch
 from mlx8_ws_audio_transformer_amd import weights as wts
 from oracle import encoder as oracle_enc
 from oracle import logmel as oracle_mel
-from tests.util import piano_clips_f32, tuning
+from tests.util import MINI_LENGTHS, mini_at, piano_clips_f32, tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -29,14 +29,18 @@ ALL = ("q_proj", "k_proj", "v_proj", "out_proj", "fc1", "fc2")
                                                     ("mini", False, ("q_proj", "v_proj"), 8),
                                                     # BASELINE.json configs[2] / [3] at full size: Whisper-small (d = 768, 12 layers), parity
                                                     # mode S = 1500, adapters on q_proj, v_proj, r = 8 and r = 16 (oracle autograd: ~20 s of CPU)
-                                                    ("small", False, ("q_proj", "v_proj"), 8), ("small", False, ("q_proj", "v_proj"), 16)])
+                                                    ("small", False, ("q_proj", "v_proj"), 8), ("small", False, ("q_proj", "v_proj"), 16),
+                                                    # the largest rank awt_encoder_create accepts (last, so that the ids of the cases above stay as they were)
+                                                    ("mini", True, ("q_proj", "v_proj"), 32)])
 def test_lora_gradients_match_oracle_autograd(name, trimmed, targets, r):
+    _check_lora_gradients(wts.config(name, trimmed), targets, r)
+
+
+def _check_lora_gradients(cfg, targets, r, B=2):
     from mlx8_ws_audio_transformer_amd.encoder import NativeWhisperEncoder
-    cfg = wts.config(name, trimmed)
     spec = wts.LoraSpec(r=r, alpha=16.0, targets=targets)
     W = wts.init_encoder_weights(cfg, 0, "test")
     LW = wts.init_lora_weights(cfg, spec, 0, zero_b=False)
-    B = 2
     mel = oracle_mel.whisper_logmel(piano_clips_f32(B), n_samples=cfg.n_frames * 160)
     dout = (wts.unit_variates("dout", B * cfg.max_source_positions * cfg.d_model, 3).reshape(B, cfg.max_source_positions, cfg.d_model)
             / np.sqrt(cfg.max_source_positions)).astype(np.float32)
@@ -46,6 +50,7 @@ def test_lora_gradients_match_oracle_autograd(name, trimmed, targets, r):
     enc.load_state_dict({k: torch.from_numpy(v) for k, v in {**W, **LW}.items()})
     out = enc(torch.from_numpy(mel).cuda()).last_hidden_state
     assert out.requires_grad
+    print("forward max-abs error", float(np.abs(out.detach().cpu().numpy() - ref_out).max()))
     np.testing.assert_allclose(out.detach().cpu().numpy(), ref_out, rtol=0, atol=1e-3)
     (out * torch.from_numpy(dout).cuda()).sum().backward()
     worst = 0.0
@@ -61,6 +66,11 @@ def test_lora_gradients_match_oracle_autograd(name, trimmed, targets, r):
         assert err < 2e-3, (k, err)   # relative to the gradient's own scale
     assert all(p.grad is None for n, p in enc.named_parameters() if "lora_" not in n)
     print("worst relative gradient error", worst)
+
+
+@pytest.mark.parametrize("S,B", MINI_LENGTHS)         # tests/util.py lists the branch each length takes
+def test_lora_gradients_at_other_sequence_lengths(S, B):
+    _check_lora_gradients(mini_at(S), ALL, 8, B)
 
 
 def test_backward_is_reproducible_and_rejects_untrainable_configurations():
@@ -159,8 +169,16 @@ def test_f16f8_mlp_backward_matches_oracle_autograd(name, trimmed, targets, r, g
     """awt_encoder_cfg.backward_terms = 5 (`backward_precision="f16f8"`): the MLP's two backward GEMMs in the f16f8 operand format with a power-of-two
     gradient scale chosen from max |d loss / d hidden| (here tiny and large upstream gradients on purpose).  Same bound against the oracle's autograd as
     the split-bf16 backward, and close to it."""
+    _check_f16f8_mlp_backward(wts.config(name, trimmed), targets, r, gmag)
+
+
+@pytest.mark.parametrize("S", [128, 256])        # no tail tile; at 256 the f16f8 training attention crosses its (S + 255) / 256 boundary
+def test_f16f8_mlp_backward_at_other_sequence_lengths(S):
+    _check_f16f8_mlp_backward(mini_at(S), ("q_proj", "v_proj"), 8, 1.0)
+
+
+def _check_f16f8_mlp_backward(cfg, targets, r, gmag):
     from mlx8_ws_audio_transformer_amd.encoder import NativeWhisperEncoder
-    cfg = wts.config(name, trimmed)
     spec = wts.LoraSpec(r=r, alpha=16.0, targets=targets)
     W = wts.init_encoder_weights(cfg, 0, "test")
     LW = wts.init_lora_weights(cfg, spec, 0, zero_b=False)

@@ -6,7 +6,7 @@ import torch
 from mlx8_ws_audio_transformer_amd import weights as wts
 from oracle import encoder as oracle_enc
 from oracle import logmel as oracle_mel
-from tests.util import golden, piano_clips_f32, tuning
+from tests.util import MINI_LENGTHS, golden, mini_at, piano_clips_f32, tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -92,6 +92,26 @@ def test_encoder_other_parity_modes_vs_oracle(precision, name, trimmed, batch):
     np.testing.assert_allclose(out[:, -4:], G[f"{key}/last_tail"], rtol=0, atol=PARITY_TOL)
     if f"{key}/last_full" in G:
         np.testing.assert_allclose(out, G[f"{key}/last_full"], rtol=0, atol=PARITY_TOL)
+
+
+# Sequence lengths other than 200 and 1500 (tests/util.py lists the branch each one takes).  Bounds: those of the two tests above, and the bf16 envelope.
+@pytest.mark.parametrize("precision", ["bf16x3", "fp16x3", "f16f8", "bf16"])
+@pytest.mark.parametrize("S,batch", MINI_LENGTHS)
+def test_encoder_at_other_sequence_lengths(S, batch, precision):
+    cfg = mini_at(S)
+    W = wts.init_encoder_weights(cfg, 0, "test")
+    mel = _mel(cfg, batch)
+    assert mel.shape == (batch, 80, 2 * S)
+    out = _native(cfg, precision)(torch.from_numpy(mel).cuda()).last_hidden_state.cpu().numpy()
+    ref = oracle_enc.encoder_forward(W, mel, cfg.heads).numpy()
+    assert out.shape == ref.shape == (batch, S, 128)
+    e = oracle_enc.error_norms(out, ref)
+    print(precision, "S =", S, e)
+    assert np.isfinite(out).all()
+    if precision == "bf16":
+        assert e["max_abs"] < FAST_TOL["max_abs"] and e["rel_l2"] < FAST_TOL["rel_l2"], e
+    else:
+        assert e["max_abs"] < {"bf16x3": PARITY_TOL, "fp16x3": 2e-4, "f16f8": 5e-4}[precision], e
 
 
 # the same mode with the four linears of every layer on the persistent ping-pong GEMM ("gemm_pp" = 2: also at these small batches, where the

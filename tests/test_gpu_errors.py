@@ -38,6 +38,19 @@ def test_create_rejects_unsupported_configs():
     L.awt_encoder_destroy(h)
 
 
+def test_lora_rank_limit_is_the_one_the_header_states():
+    """awt_encoder_cfg.lora_rank is 0 or 1..32: the adapter-gradient reduction holds at most 32 adapter columns per block.  Both sides of the limit,
+    for inference and for training encoders."""
+    L = _lib.lib()
+    for training in (0, 1):
+        rc, h = _create(wts.config("mini", True), r=32, alpha=16.0, targets=_lib.LORA_BITS["q_proj"] | _lib.LORA_BITS["v_proj"], training=training)
+        assert rc == 0
+        L.awt_encoder_destroy(h)
+        for r in (33, 64, -1):
+            rc, _ = _create(wts.config("mini", True), r=r, alpha=16.0, targets=_lib.LORA_BITS["q_proj"] | _lib.LORA_BITS["v_proj"], training=training)
+            assert rc == -1 and b"lora_rank must be in 0..32" in L.awt_last_error(), (training, r)
+
+
 def test_set_weight_and_forward_state_errors():
     L = _lib.lib()
     cfg = wts.config("mini", True)

@@ -7,7 +7,7 @@ import torch
 from mlx8_ws_audio_transformer_amd import weights as wts
 from oracle import encoder as oracle_enc
 from oracle import logmel as oracle_mel
-from tests.util import piano_clips_f32
+from tests.util import MINI_LENGTHS, mini_at, piano_clips_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -67,6 +67,11 @@ def _check_against_oracle(cfg, B, dout_seed, precision="bf16x3", out_atol=1e-3, 
 @pytest.mark.parametrize("name,trimmed", [("mini", True), ("mini", False), ("tiny", True), ("small", False)])
 def test_base_gradients_match_oracle_autograd(name, trimmed):
     _check_against_oracle(wts.config(name, trimmed), 2, 3)
+
+
+@pytest.mark.parametrize("S,B", MINI_LENGTHS)         # tests/util.py lists the branch each length takes
+def test_base_gradients_at_other_sequence_lengths(S, B):
+    _check_against_oracle(mini_at(S), B, 3)
 
 
 def test_base_gradients_at_large_width():
@@ -137,8 +142,16 @@ def test_accumulate_and_gradient_scale_apply_to_base_gradients():
 
 
 def test_bf16_backward_option_of_the_full_backward():
+    _check_bf16_backward_band(wts.config("tiny", True))
+
+
+@pytest.mark.parametrize("S", [64, 128])          # the attention backward's last tile without a tail, on one product per fragment pair
+def test_bf16_backward_option_at_other_sequence_lengths(S):
+    _check_bf16_backward_band(mini_at(S))
+
+
+def _check_bf16_backward_band(cfg):
     from mlx8_ws_audio_transformer_amd.encoder import NativeWhisperEncoder
-    cfg = wts.config("tiny", True)
     mel = torch.from_numpy(oracle_mel.whisper_logmel(piano_clips_f32(2), n_samples=cfg.n_frames * 160)).cuda()
     grads, outs = {}, {}
     for bp in (None, "bf16"):

@@ -4,7 +4,7 @@ import pytest
 import torch
 
 from oracle import logmel as oracle
-from tests.util import golden, logmel_inputs, piano_clips_f32
+from tests.util import GENERIC_LOGMEL_CASES, generic_logmel_clip, golden, logmel_inputs, piano_clips_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -147,3 +147,72 @@ def test_real_recording_end_to_end(fe):
         out = enc(torch.from_numpy(feats).cuda()).last_hidden_state.cpu().numpy()
         for key, sl in (("last_head", slice(0, 4)), ("last_live", slice(196, 204)), ("last_tail", slice(-4, None))):
             assert np.abs(out[:, sl] - R["tiny/" + key]).max() <= 1e-3, (precision, key)
+
+
+@pytest.mark.parametrize("n_fft,hop,n_mels", sorted(GENERIC_LOGMEL_CASES))
+def test_generic_logmel_other_configurations(n_fft, hop, n_mels):
+    from mlx8_ws_audio_transformer_amd import urbansound
+    sr, f_min, f_max, n, batch = GENERIC_LOGMEL_CASES[(n_fft, hop, n_mels)]
+    clips = [generic_logmel_clip(n, i) for i in range(batch)]
+    out = urbansound.mel_spectrogram_log(torch.from_numpy(np.stack(clips)), sample_rate=sr, n_fft=n_fft, hop_length=hop, n_mels=n_mels, f_min=f_min,
+                                         f_max=f_max).cpu().numpy()
+    assert out.shape == (batch, n_mels, 1 + n // hop) and np.isfinite(out).all()
+    worst = 0.0
+    for i, clip in enumerate(clips):
+        ref = oracle.urbansound_logmel(clip, sample_rate=sr, n_fft=n_fft, hop=hop, n_mels=n_mels, f_min=f_min, f_max=f_max)
+        worst = max(worst, float(np.abs(out[i] - ref).max()))
+        np.testing.assert_allclose(out[i], ref, rtol=0, atol=MEL_TOL)
+    if (n_fft, n_mels, sr) == (400, 128, 16000):
+        empty = np.all(out == np.float32(np.log(1e-6)), axis=(0, 2))       # filters narrower than the FFT bin spacing
+        assert empty.any() and not empty.all()
+    print("generic log-mel", (n_fft, hop, n_mels), (sr, f_min, f_max, n, batch), "max-abs", worst)
+
+
+def _edge_clips_i16(lengths, seed):
+    """Seeded int16 clips of the given lengths (amplitude-modulated noise) with both int16 extremes among the first and the last samples."""
+    rng = np.random.default_rng(seed)
+    clips = []
+    for n in lengths:
+        t = np.arange(n)
+        x = np.clip(rng.standard_normal(n) * 6000.0 * (1.0 + 0.9 * np.sin(2 * np.pi * t / 7001.0)), -32768, 32767).astype(np.int16)
+        x[-1] = 32767
+        x[0] = -32768
+        if n > 2:
+            x[-2], x[1] = -32768, 32767
+        clips.append(x)
+    return clips
+
+
+def _whisper_edge_batch(lengths, n_frames, n_mels, seed):
+    """The ragged batch through the per-clip n_valid path as int16 and as float32 (the same samples / 32768) against the oracle."""
+    from mlx8_ws_audio_transformer_amd.feature_extraction import logmel_whisper_device
+    clips = _edge_clips_i16(lengths, seed)
+    width = max(lengths)
+    pcm = np.zeros((len(clips), width), np.int16)
+    for i, c in enumerate(clips):
+        pcm[i, : c.size] = c
+    ref = oracle.whisper_logmel([c.astype(np.float32) / 32768.0 for c in clips], n_samples=160 * n_frames, n_mels=n_mels)
+    n_valid = torch.tensor(lengths, dtype=torch.int32)
+    for name, dev in (("int16", torch.from_numpy(pcm).cuda()), ("float32", (torch.from_numpy(pcm).float() / 32768.0).cuda())):
+        junk = dev.clone()
+        for i, n in enumerate(lengths):                                    # samples at index >= n_valid[b] are never read
+            junk[i, n:] = 12345 if name == "int16" else float("nan")
+        out = logmel_whisper_device(junk, n_valid, width, n_frames, n_mels=n_mels).cpu().numpy()
+        assert out.shape == ref.shape and np.isfinite(out).all()
+        err = np.abs(out - ref).reshape(len(lengths), -1).max(axis=1)
+        print("whisper log-mel", name, n_frames, n_mels, "per-clip max-abs", dict(zip(lengths, err.tolist())))
+        np.testing.assert_allclose(out, ref, rtol=0, atol=MEL_TOL)
+
+
+def test_whisper_logmel_at_the_live_frame_boundary():
+    """live_frames() = ceil((n_valid + 200) / 160) decides which frames are computed and which are filled with the pad constant: clip lengths on and next to
+    that boundary (160 * 3 - 200 = 280), below the reflection width (200), and in (L - 200, L], where the right-hand reflection reads live samples."""
+    _whisper_edge_batch([1, 199, 200, 201, 279, 280, 281, 479799, 479800, 479801, 479999, 480000, 480001], 3000, 80, 11)
+
+
+def test_whisper_logmel_at_the_live_frame_boundary_trimmed_mode():
+    _whisper_edge_batch([1, 199, 200, 201, 279, 280, 281, 63799, 63800, 63801, 63999, 64000, 64001], 400, 80, 12)
+
+
+def test_whisper_logmel_at_the_live_frame_boundary_128_mels():
+    _whisper_edge_batch([1, 199, 200, 479999, 480000, 480001], 3000, 128, 13)

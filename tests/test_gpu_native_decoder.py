@@ -393,3 +393,173 @@ def test_absorbed_cross_attention_equals_projected_form_at_whisper_small_shape()
     gk, ga = res["kv"][2], res["absorbed"][2]
     assert float(gk.abs().max()) > 0
     assert float((gk - ga).abs().max()) < 2e-4 * float(gk.abs().max())
+
+
+# ---------------------------------------------------------------------------------------------- operator entry points against fp64, one by one
+@pytest.mark.parametrize("rows,H,Lq,T,Tmax", [(3, 2, 1, 1, 8), (2, 6, 1, 65, 448), (4, 2, 4, 4, 64), (2, 2, 3, 130, 448), (16, 6, 1, 448, 448), (1, 20, 17, 200, 256)])
+def test_cached_attention_against_fp64_and_the_packed_kernel(rows, H, Lq, T, Tmax):
+    """awt_op_attention_cached on a [rows, Tmax, 2 d] decode cache whose positions >= T hold NaN (they are not live: nothing of them may reach the
+    output): fp64 causal attention within the bound of test_small_attention_forward_and_backward (the same kernel), and the same bits as
+    awt_op_attention_small(causal, causal_off = T - Lq) on a packed copy of the live part."""
+    from mlx8_ws_audio_transformer_amd import native_decoder as nd
+    d = H * 64
+    q = _rand((rows * Lq, 3 * d), 1)                                      # the fused projection's output: q in the first d columns, ld = 3 d
+    cache = torch.full((rows, Tmax, 2 * d), float("nan"), device="cuda")
+    cache[:, :T] = _rand((rows, T, 2 * d), 2)
+    o = nd.attention_cached((q, 0), 3 * d, cache, T, H, Lq)
+    assert torch.isfinite(o).all()
+    qh = q[:, :d].double().view(rows, Lq, H, 64).transpose(1, 2)
+    kh = cache[:, :T, :d].double().view(rows, T, H, 64).transpose(1, 2)
+    vh = cache[:, :T, d:].double().view(rows, T, H, 64).transpose(1, 2)
+    s = (qh * 0.125) @ kh.transpose(2, 3)
+    i, j = torch.arange(Lq, device="cuda")[:, None], torch.arange(T, device="cuda")[None, :]
+    s = s.masked_fill(j > i + (T - Lq), float("-inf"))
+    ref = (torch.softmax(s, -1) @ vh).transpose(1, 2).reshape(rows * Lq, d)
+    err = (o.double() - ref).abs().max().item()
+    print("cached attention", (rows, H, Lq, T, Tmax), "max-abs vs fp64", err)
+    assert err < 2e-5, err
+    k2, v2 = cache[:, :T, :d].reshape(rows * T, d).contiguous(), cache[:, :T, d:].reshape(rows * T, d).contiguous()
+    o2, _ = nd.attention_small((q, 0), 3 * d, (k2, 0), d, (v2, 0), d, rows, H, Lq, T, True, T - Lq, want_lse=False)
+    assert torch.equal(o, o2)
+
+
+def test_cached_attention_rejects_bad_arguments():
+    from mlx8_ws_audio_transformer_amd import _lib, native_decoder as nd
+    H, d = 2, 128
+    q, cache = _rand((2 * 4, d), 1), _rand((2, 16, 2 * d), 2)
+    with pytest.raises(_lib.AwtError):                                     # fewer live positions than query rows
+        nd.attention_cached((q, 0), d, cache, 3, H, 4)
+    with pytest.raises(_lib.AwtError):                                     # more live positions than the batch stride holds
+        nd.attention_cached((q, 0), d, cache, 17, H, 4)
+    L = _lib.lib()
+    o = torch.empty((8, d), device="cuda")
+    args = lambda stride, ldkv: (_lib.ctx(q.device), _lib.ptr(q), d, cache.data_ptr(), cache.data_ptr() + 4 * d, ldkv, stride, _lib.ptr(o), d, 2, H, 4, 8,
+                                 _lib.stream_handle())
+    assert L.awt_op_attention_cached(*args(16 * 2 * d, 2 * d)) == 0
+    assert L.awt_op_attention_cached(*args(8 * 2 * d - 4, 2 * d)) == -1    # stride one element group short of T = 8 rows
+    assert L.awt_op_attention_cached(*args(16 * 2 * d + 2, 2 * d)) == -1   # not a multiple of 4
+    assert L.awt_op_attention_cached(*args(16 * 2 * d, 64)) == -1          # row stride narrower than H * 64
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("d", [128, 384, 1280])
+@pytest.mark.parametrize("L", [1, 12, 448])
+def test_embedding_op_is_bit_equal_to_the_fp32_sum(d, L):
+    """awt_op_embed is one fp32 add: bit equality with tok[ids] + pos[pos0 + m % L], ids 0 and vocab - 1 included, pos0 > 0.  Ids outside [0, vocab)
+    are clamped to the nearest valid row (include/awt.h): the kernel never reads outside the table."""
+    from mlx8_ws_audio_transformer_amd import native_decoder as nd
+    vocab, B, pos0 = 517, 3, 5
+    tok, pos = _rand((vocab, d), 1), _rand((pos0 + L + 3, d), 2)
+    ids = torch.randint(0, vocab, (B, L), generator=torch.Generator().manual_seed(3))
+    ids[0, 0], ids[-1, -1] = 0, vocab - 1
+    if L > 1:
+        ids[1, 0], ids[1, 1] = vocab - 1, 0
+    ids = ids.cuda()
+    x = nd.embed(ids, tok, pos, pos0)
+    m = torch.arange(B * L, device="cuda")
+    assert torch.equal(x, tok[ids.reshape(-1)] + pos[pos0 + m % L])
+    assert torch.equal(nd.embed(ids, tok, pos, 0), tok[ids.reshape(-1)] + pos[m % L])
+    wild = ids.clone()
+    wild[0, 0], wild[-1, -1] = -7, vocab + 1000
+    if L > 1:
+        wild[1, 0], wild[1, 1] = 2 ** 40, -2 ** 40
+    assert torch.equal(nd.embed(wild, tok, pos, pos0), tok[wild.clamp(0, vocab - 1).reshape(-1)] + pos[pos0 + m % L])
+
+
+# Bound of the LayerNorm backward operators: 4 x the max-abs error of torch's fp32 autograd of layer_norm on the CPU against fp64 on the same inputs,
+# relative to the largest reference element (the kernels sum in another order and use a reciprocal square root, hence the factor).
+# dx, measured on the CPU over the cases below: 5.7e-8 .. 1.615e-7 (largest at d = 1280, M = 777, no dres; with dres 4.5e-8 .. 1.438e-7); a row
+# reduction, the same for any number of CPU threads.
+LN_DX_TOL = 4 * 1.615e-7
+# dgamma / dbeta at d = 1280, per M: torch's fp32 column reduction depends on the number of CPU threads, so these are the figures with
+# torch.set_num_threads(1), which repeat exactly: M -> (dgamma, dbeta)
+LN_PARAM_FP32_ERR = {255: (3.366e-7, 4.451e-7), 256: (3.312e-7, 4.767e-7), 257: (3.495e-7, 4.984e-7), 700: (6.300e-7, 8.240e-7)}
+
+
+@pytest.mark.parametrize("with_dres", [False, True])
+@pytest.mark.parametrize("M", [1, 50, 777])
+@pytest.mark.parametrize("d", [128, 384, 768, 1024, 1280])
+def test_layernorm_backward_against_fp64(d, M, with_dres):
+    from mlx8_ws_audio_transformer_amd import native_decoder as nd
+    x, g, b, dy, dres = _rand((M, d), 3, 3.0) + 1.5, _rand((d,), 5) + 1.0, _rand((d,), 6), _rand((M, d), 4), _rand((M, d), 7)
+    xd = x.double().requires_grad_(True)
+    F.layer_norm(xd, (d,), g.double(), b.double(), 1e-5).backward(dy.double())
+    ref = xd.grad + dres.double() if with_dres else xd.grad
+    dx = nd.layernorm_backward(dy, x, g, dres=dres if with_dres else None)
+    err = (dx.double() - ref).abs().max().item() / ref.abs().max().item()
+    print("layernorm backward", (d, M, with_dres), "max-abs / max |ref|", err)
+    assert torch.isfinite(dx).all() and err < LN_DX_TOL, err
+
+
+@pytest.mark.parametrize("M", sorted(LN_PARAM_FP32_ERR))                   # on either side of the 256-row slab of the two-pass reduction
+def test_layernorm_param_grad_at_the_widest_row_against_fp64(M):
+    from mlx8_ws_audio_transformer_amd import _lib
+    d = 1280
+    x, dy = _rand((M, d), 3, 3.0) + 1.5, _rand((M, d), 4)
+    gd, bd = torch.ones(d, dtype=torch.float64, device="cuda", requires_grad=True), torch.zeros(d, dtype=torch.float64, device="cuda", requires_grad=True)
+    F.layer_norm(x.double(), (d,), gd, bd, 1e-5).backward(dy.double())
+    dg, db = torch.full((d,), 7.0, device="cuda"), torch.full((d,), 7.0, device="cuda")
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_op_param_grad_workspace_bytes(M, d), x.device)
+    _lib.check(L.awt_op_layernorm_param_grad(_lib.ctx(x.device), _lib.ptr(dy), _lib.ptr(x), _lib.ptr(dg), _lib.ptr(db), M, d, 1e-5, _lib.ptr(ws), ws.numel(),
+                                             _lib.stream_handle()))
+    eg = (dg.double() - gd.grad).abs().max().item() / gd.grad.abs().max().item()
+    eb = (db.double() - bd.grad).abs().max().item() / bd.grad.abs().max().item()
+    print("layernorm param grad d = 1280, M =", M, "dgamma", eg, "dbeta", eb)
+    assert eg < 4 * LN_PARAM_FP32_ERR[M][0] and eb < 4 * LN_PARAM_FP32_ERR[M][1], (eg, eb)
+
+
+def test_gelu_backward_over_the_whole_domain():
+    """The derivative (erf_fast plus __expf) on the forward test's grid: the fitted range, the continuation beyond it and the magnitudes where
+    the negative branch has to be exactly 0 and the positive one exactly dy."""
+    from mlx8_ws_audio_transformer_amd import native_decoder as nd
+    grid = torch.cat([torch.linspace(-12, 12, 200001), torch.tensor([0.0, -0.0, 1e-30, -1e-30, 5.94, -5.94, 6.5, -6.5, 40.0, -40.0, 1e4, -1e4, 6e4, -6e4, 3.0])]).cuda()
+    assert grid.numel() == 200016
+    got = nd.gelu_backward(grid, torch.ones_like(grid))
+    x = grid.double()
+    want = 0.5 * (1.0 + torch.erf(x * 0.5 ** 0.5)) + x * torch.exp(-0.5 * x * x) * (2 * np.pi) ** -0.5          # Phi(x) + x phi(x)
+    err = (got.double() - want).abs()
+    print("gelu backward: max-abs", err.max().item(), "at x =", grid[err.argmax()].item())
+    assert torch.isfinite(got).all() and err.max().item() < 2e-6
+    assert (got[grid < -15] == 0).all() and (got[grid > 15] == 1).all()
+    dy = _rand((200016,), 8)
+    assert torch.equal(nd.gelu_backward(grid, dy)[grid > 15], dy[grid > 15])
+
+
+def _ce_inputs(kind, M, vocab):
+    labels = torch.randint(0, vocab, (M,), generator=torch.Generator().manual_seed(2))
+    z = _rand((M, vocab), 1, 3.0).cpu()
+    rows = torch.arange(M)
+    if kind == "confident":                                                # the label's logit 30 above the rest: the sum of exponentials is 1 + O(1e-9)
+        z = _rand((M, vocab), 1, 1.0).cpu()
+        z[rows, labels] = z.max(dim=1).values + 30.0
+    if kind == "suppressed":                                               # what token suppression produces: -inf on a tenth of the non-label columns
+        mask = torch.rand((M, vocab), generator=torch.Generator().manual_seed(3)) < 0.1
+        mask[rows, labels] = False
+        z = z.masked_fill(mask, float("-inf"))
+    labels[::5] = -100
+    return z.cuda(), labels.cuda()
+
+
+# error of torch's fp32 F.cross_entropy on the CPU against fp64 on the same inputs (loss, dlogits); the bounds are 4 x these, floored at the 1e-5 / 1e-7
+# of test_cross_entropy_gelu_layernorm_and_embedding_ops
+CE_FP32_ERR = {"normal": (1.738e-6, 3.736e-8), "confident": (1.022e-10, 7.530e-12), "suppressed": (1.512e-6, 3.795e-8)}
+
+
+@pytest.mark.parametrize("kind", ["normal", "confident", "suppressed"])
+def test_cross_entropy_at_whisper_vocabulary(kind):
+    from mlx8_ws_audio_transformer_amd import native_decoder as nd
+    M, vocab, ld = 24, 51865, 51968
+    z, labels = _ce_inputs(kind, M, vocab)
+    logits = F.pad(z, (0, ld - vocab), value=50.0).contiguous()            # padding columns hold junk: they must be ignored
+    loss, dlogits = nd.cross_entropy(logits, labels, vocab)
+    zd = z.double().requires_grad_(True)
+    ref = F.cross_entropy(zd, labels, ignore_index=-100)
+    ref.backward()
+    e_loss, e_grad = abs(float(loss) - float(ref.detach())), (dlogits[:, :vocab].double() - zd.grad).abs().max().item()
+    print("cross entropy", kind, "loss", float(ref.detach()), "error", e_loss, "dlogits max-abs error", e_grad)
+    assert torch.isfinite(loss) and torch.isfinite(dlogits).all()
+    assert e_loss < max(1e-5, 4 * CE_FP32_ERR[kind][0]), e_loss
+    assert e_grad < max(1e-7, 4 * CE_FP32_ERR[kind][1]), e_grad
+    assert float(dlogits[:, vocab:].abs().max()) == 0.0
+    assert float(dlogits[labels == -100].abs().max()) == 0.0

@@ -117,6 +117,13 @@ def test_tuning_set_rejects_unknown():
     for key, value in [("attn_shape", v) for v in (1, 2, 3, 7, 8, 9)] + [("gemm_tile", 512), ("gemm_pp_stagger", 0)]:
         with pytest.raises(_lib.AwtError):
             _lib.tuning_set(key, value)
+    # "attn_qt": 0 (automatic), 1 or 2 query tiles per wave, nothing else
+    with tuning():                                                     # restores the defaults even if a call below fails
+        for value in (-1, 3, 4, 128, 256):
+            with pytest.raises(_lib.AwtError):
+                _lib.tuning_set("attn_qt", value)
+        for value in (1, 2, 0):
+            _lib.tuning_set("attn_qt", value)
 
 
 def test_linear_identity_with_asymmetric_weight():
@@ -130,13 +137,27 @@ def test_linear_identity_with_asymmetric_weight():
         assert torch.equal(ops.linear(x, w, None, precision), w.t().contiguous()), precision
 
 
+def _layernorm_vs_fp64(M, d):
+    from mlx8_ws_audio_transformer_amd import ops
+    x, g, b = _rand((M, d), 4, 3.0) + 1.5, _rand((d,), 5) + 1.0, _rand((d,), 6)
+    y = ops.layernorm(x, g, b)
+    ref = torch.nn.functional.layer_norm(x.double(), (d,), g.double(), b.double(), 1e-5)
+    err = (y.double() - ref).abs().max().item()
+    print("layernorm", (M, d), "max-abs vs fp64", err)
+    assert torch.isfinite(y).all() and err < 5e-6, err
+
+
+# against fp64: torch's own fp32 layer_norm is 1.6e-6 .. 2.1e-6 from fp64 on this input distribution for d = 128 .. 1280 (measured on the CPU)
 @pytest.mark.parametrize("d", [128, 384, 512, 768])
 def test_layernorm(d):
-    from mlx8_ws_audio_transformer_amd import ops
-    x, g, b = _rand((777, d), 4, 3.0) + 1.5, _rand((d,), 5) + 1.0, _rand((d,), 6)
-    y = ops.layernorm(x, g, b)
-    ref = torch.nn.functional.layer_norm(x, (d,), g, b, 1e-5)
-    assert (y - ref).abs().max().item() < 5e-6
+    _layernorm_vs_fp64(777, d)
+
+
+# the widest rows the kernel holds (Whisper medium / large); M = 1 and 3 leave most waves of a launch without a row
+@pytest.mark.parametrize("d", [1024, 1280])
+@pytest.mark.parametrize("M", [1, 3, 777])
+def test_layernorm_wide_rows(M, d):
+    _layernorm_vs_fp64(M, d)
 
 
 # max-abs error bound of softmax(q k^T) v vs float64 on these inputs, per operand precision
@@ -164,14 +185,20 @@ def test_attention_f16f8_workgroup_shapes(shape):
     """Every forced form of the f16f8 attention kernel (every cross term on 4 / 8 waves, P V as one fp16 product on 4 waves) on sequences
     with and without a tail tile."""
     from mlx8_ws_audio_transformer_amd import ops
-    for S in (333, 64, 100, 128, 200, 1500):          # 6 / 1 / 2 / 2 / 4 / 24 key tiles, with and without a tail tile
+    worst = 0.0
+    # 6 / 1 / 2 / 2 / 4 / 24 key tiles, with and without a tail tile; then sequences below one key tile (1, 31, 33, 63: every streamed row of the
+    # only tile clamped, a wave's 32 queries empty / partly filled / full) and on either side of the one / two / four tile boundaries
+    for S in (333, 64, 100, 128, 200, 1500, 1, 31, 33, 63, 65, 127, 255, 256):
         B, H = 2, 2
         q, k, v = _rand((B, H, S, 64), 17, 0.35), _rand((B, H, S, 64), 18), _rand((B, H, S, 64), 19)
         with tuning(attn_shape=shape):
             o = ops.attention(q, k, v, "f16f8")
         p = torch.softmax(q.double() @ k.double().transpose(2, 3), dim=-1)
         ref = (p @ v.double()).transpose(1, 2).reshape(B, S, H * 64)
-        assert (o.double() - ref).abs().max().item() < (ATT_TOL_F16F8_CROSS if shape in (4, 5) else ATT_TOL["f16f8"]), S
+        err = (o.double() - ref).abs().max().item()
+        worst = max(worst, err)
+        assert torch.isfinite(o).all() and err < (ATT_TOL_F16F8_CROSS if shape in (4, 5) else ATT_TOL["f16f8"]), (S, err)
+    print("f16f8 attention form", shape, "worst max-abs", worst)
 
 
 @pytest.mark.parametrize("precision", ["bf16x3", "fp16x3", "f16f8", "f16f8-pipe"])
@@ -191,6 +218,70 @@ def test_attention_online_softmax_rescale_branch(precision):
     ref = (p @ v.double()).transpose(1, 2).reshape(B, S, 64)
     # logits reach ~170: fp32 ulp of the exp2 argument is ~1.5e-5; f16f8 carries the logits to 2^-16 relative: 170 * 2^-16 = 2.6e-3 in the exponent
     assert (o.double() - ref).abs().max().item() < (3e-4 if precision != "f16f8" else 1.5e-2)
+
+
+# Both instantiations of the bf16 / fp16 / bf16x3 / fp16x3 kernel -- one query tile per wave (128 queries per workgroup) and two (256) -- forced with the
+# tuning knob "attn_qt" on sequences that leave the first and the second query tile of a wave empty, partly filled and full (a workgroup's 256 queries:
+# wave w holds rows 64 w .. 64 w + 31 in tile 0 and 64 w + 32 .. 64 w + 63 in tile 1), with and without a tail key tile, and below one key tile.
+# The automatic rule picks one tile for every one of these grids (2 x 2 heads), so without the knob the two-tile code never runs here.
+@pytest.mark.parametrize("qt", [1, 2])
+@pytest.mark.parametrize("precision", ["bf16x3", "bf16", "fp16", "fp16x3"])
+def test_attention_both_query_tilings(precision, qt):
+    from mlx8_ws_audio_transformer_amd import ops
+    B, H = 2, 2
+    worst = 0.0
+    for S in (1, 31, 33, 63, 65, 127, 192, 255, 256, 300, 448):
+        q, k, v = _rand((B, H, S, 64), 7, 0.35), _rand((B, H, S, 64), 8), _rand((B, H, S, 64), 9)
+        with tuning(attn_qt=qt):
+            o = ops.attention(q, k, v, precision)
+        p = torch.softmax(q.double() @ k.double().transpose(2, 3), dim=-1)
+        ref = (p @ v.double()).transpose(1, 2).reshape(B, S, H * 64)
+        err = (o.double() - ref).abs().max().item()
+        worst = max(worst, err)
+        assert torch.isfinite(o).all() and err < ATT_TOL[precision], (S, err)
+    print(precision, "attn_qt", qt, "worst max-abs over S", worst)
+
+
+# Knob at 0 on grids where the rule of launch_attention itself takes two query tiles per wave: it compares 0.55 * ceil(wg1 / 512) with ceil(wg2 / 512),
+# wg1 = ceil(S / 128) B H, wg2 = ceil(S / 256) B H.  (8, 64, 256): wg2 = 512 -> 1 round, wg1 = 1024 -> 0.55 * 2 = 1.1: two tiles, both full.
+# (8, 64, 129): wg2 = 512 -> 1, wg1 = 1024 -> 1.1: two tiles, the second workgroup half holding one query.  (4, 64, 300): wg2 = 512 -> 1, wg1 = 768 ->
+# 0.55 * 2 = 1.1: two tiles, a tail key tile and a partly filled second workgroup.
+@pytest.mark.parametrize("precision", ["bf16x3", "bf16", "fp16", "fp16x3"])
+def test_attention_on_grids_that_select_two_query_tiles(precision):
+    from mlx8_ws_audio_transformer_amd import ops
+    for B, H, S in ((8, 64, 256), (8, 64, 129), (4, 64, 300)):
+        wg1, wg2 = -(-S // 128) * B * H, -(-S // 256) * B * H
+        assert not 0.55 * -(-wg1 // 512) < -(-wg2 // 512)            # the library's rule, restated: these grids do not take one tile
+        q, k, v = _rand((B, H, S, 64), 7, 0.35), _rand((B, H, S, 64), 8), _rand((B, H, S, 64), 9)
+        o = ops.attention(q, k, v, precision)
+        with tuning(attn_qt=2):
+            assert torch.equal(o, ops.attention(q, k, v, precision))   # ... and the forced form is the same launch
+        ref = torch.empty((B, S, H * 64), dtype=torch.float64, device="cuda")
+        for b in range(B):                                            # per clip: the fp64 scores of one clip are 34 MB
+            p = torch.softmax(q[b].double() @ k[b].double().transpose(1, 2), dim=-1)
+            ref[b] = (p @ v[b].double()).transpose(0, 1).reshape(S, H * 64)
+        err = (o.double() - ref).abs().max().item()
+        print(precision, (B, H, S), "automatic rule (two tiles) max-abs", err)
+        assert torch.isfinite(o).all() and err < ATT_TOL[precision], ((B, H, S), err)
+
+
+@pytest.mark.parametrize("precision", ["bf16x3", "fp16x3"])
+def test_attention_online_softmax_rescale_branch_with_two_query_tiles(precision):
+    # test_attention_online_softmax_rescale_branch on the two-tile instantiation: query 5 sits in tile 0 of wave 0; query 37, given the same
+    # dominating keys, in its tile 1
+    from mlx8_ws_audio_transformer_amd import ops
+    B, H, S = 1, 1, 448
+    q, k, v = _rand((B, H, S, 64), 10, 0.2), _rand((B, H, S, 64), 11), _rand((B, H, S, 64), 12)
+    q[0, 0, 37] = q[0, 0, 5]
+    for t, key in enumerate([70, 150, 260, 390]):
+        k[0, 0, key] = q[0, 0, 5] * (20.0 + 15 * t)
+    with tuning(attn_qt=2):
+        o = ops.attention(q, k, v, precision)
+    p = torch.softmax(q.double() @ k.double().transpose(2, 3), dim=-1)
+    ref = (p @ v.double()).transpose(1, 2).reshape(B, S, 64)
+    err = (o.double() - ref).abs().max().item()
+    print(precision, "rescale branch, two query tiles: max-abs", err)
+    assert err < 3e-4, err
 
 
 def test_linear_output_larger_than_2g_elements():

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from oracle import logmel
-from tests.util import golden, logmel_inputs
+from tests.util import GENERIC_LOGMEL_CASES, generic_logmel_clip, golden, logmel_inputs
 
 G = golden("logmel_whisper.npz")
 
@@ -73,6 +73,27 @@ def test_urbansound_logmel(n_mels, hop):
     ref = G3[f"mels{n_mels}_hop{hop}"]
     assert out.shape == ref.shape == (n_mels, 1 + 64000 // hop)
     np.testing.assert_allclose(out, ref, rtol=0, atol=2e-4)  # ln() of small powers: fp32 stft vs fp64 oracle
+
+
+def test_urbansound_logmel_other_configurations_against_torch_stft():
+    """The configurations tests/test_gpu_logmel.py runs the HIP kernel at (n_fft 400 / 512, hop = n_fft and n_fft / 4, other sample rates, f_min > 0,
+    f_max < sr / 2, clip lengths that are not a multiple of hop, the minimum length): the oracle against torch.stft in float64 (centre, reflect,
+    periodic Hann) and torchaudio's published HTK filter-bank formula, restated here."""
+    import torch
+    for (n_fft, hop, n_mels), (sr, f_min, f_max, n, _) in sorted(GENERIC_LOGMEL_CASES.items()):
+        clip = generic_logmel_clip(n)
+        out = logmel.urbansound_logmel(clip, sample_rate=sr, n_fft=n_fft, hop=hop, n_mels=n_mels, f_min=f_min, f_max=f_max)
+        spec = torch.stft(torch.from_numpy(clip).double(), n_fft, hop_length=hop, window=torch.hann_window(n_fft, periodic=True, dtype=torch.float64),
+                          center=True, pad_mode="reflect", return_complex=True)
+        power = (spec.real ** 2 + spec.imag ** 2).numpy()
+        freqs = np.linspace(0, sr // 2, n_fft // 2 + 1)
+        m = np.linspace(2595.0 * np.log10(1.0 + f_min / 700.0), 2595.0 * np.log10(1.0 + f_max / 700.0), n_mels + 2)
+        f = 700.0 * (10.0 ** (m / 2595.0) - 1.0)
+        slopes = f[None, :] - freqs[:, None]
+        fb = np.maximum(0.0, np.minimum(-slopes[:, :-2] / np.diff(f)[:-1], slopes[:, 2:] / np.diff(f)[1:]))
+        ref = np.log(fb.T @ power + 1e-6)
+        assert out.shape == ref.shape == (n_mels, 1 + n // hop), (n_fft, hop, n_mels)
+        np.testing.assert_allclose(out, ref, rtol=0, atol=1e-5, err_msg=str((n_fft, hop, n_mels)))
 
 
 def test_urbansound_prepare_mono_pad_trim():

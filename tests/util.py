@@ -10,7 +10,7 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 # the library's defaults of the tuning knobs the tests change (include/awt.h, awt_tuning_set)
-TUNING_DEFAULTS = {"gemm_tile": 0, "gemm_pp": 1, "gemm_pp_mask": 12, "gemm_mfma16": 1, "attn_shape": 0}
+TUNING_DEFAULTS = {"gemm_tile": 0, "gemm_pp": 1, "gemm_pp_mask": 12, "gemm_mfma16": 1, "attn_shape": 0, "attn_qt": 0}
 
 
 @contextlib.contextmanager
@@ -53,3 +53,44 @@ def real_audio():
     G = golden("real_audio.npz")
     pcm = G["pcm_i16_stereo"]
     return pcm, (pcm.astype(np.float32) / 32768.0).mean(axis=1), G
+
+
+def mini_at(S):
+    """The mini shape at another sequence length: S picks the last-tile, lane-block and tile-count branches of the attention kernels."""
+    return wts.EncoderConfig(128, 2, 2, 512, 80, S, f"mini-S{S}")
+
+
+# (S, batch) of the tests that run the encoder and both backward passes away from S = 200 and 1500 (neither is a multiple of 64), on mini_at(S):
+#   S = 8    one key tile with a tail; three of a workgroup's four waves without a query; 16 GEMM rows
+#   S = 64   one tile, no tail (the attention backward's no-tail last tile)
+#   S = 128  two tiles, no tail, one full 128-row lane block
+#   S = 136  three tiles with a tail, a second, partial lane block (batch 3)
+#   S = 192  three tiles, no tail
+#   S = 256  four tiles, two full lane blocks; the f16f8 attention crosses its (S + 255) / 256 boundary
+MINI_LENGTHS = [(8, 2), (64, 2), (128, 2), (136, 3), (192, 2), (256, 2)]
+
+
+# (n_fft, hop, n_mels) -> (sample_rate, f_min, f_max, n_samples, batch): every n_fft the header promises besides 1024, hop == n_fft and n_fft / 4, one / some / the
+# most mel bins, with the other arguments off their defaults in turn: sample rates 22050 and 44100, f_min = 50, f_max below sr / 2, n_samples that are not a
+# multiple of hop, the minimum n_samples = n_fft / 2 + 1 (one reflection covers the whole clip), batches of 3.  128 bins over 201 FFT bins (n_fft = 400,
+# 16 kHz) include filters that hold no FFT bin: their value is ln(log_eps) in the oracle and in the kernel.
+GENERIC_LOGMEL_CASES = {
+    (400, 400, 1): (16000, 0.0, 8000.0, 64000, 1),
+    (400, 400, 40): (22050, 50.0, 11025.0, 30011, 1),
+    (400, 400, 128): (16000, 0.0, 8000.0, 64000, 3),
+    (400, 100, 1): (44100, 50.0, 16000.0, 201, 1),
+    (400, 100, 40): (16000, 50.0, 7600.0, 12345, 3),
+    (400, 100, 128): (44100, 0.0, 22050.0, 30011, 1),
+    (512, 512, 1): (22050, 0.0, 8000.0, 257, 1),
+    (512, 512, 40): (44100, 50.0, 16000.0, 64000, 3),
+    (512, 512, 128): (16000, 50.0, 8000.0, 40001, 1),
+    (512, 128, 1): (16000, 0.0, 8000.0, 64000, 1),
+    (512, 128, 40): (22050, 50.0, 8000.0, 257, 3),
+    (512, 128, 128): (22050, 0.0, 11025.0, 64000, 1),
+}
+
+
+def generic_logmel_clip(n, i=0):
+    """Clip i of a GENERIC_LOGMEL_CASES batch: piano notes over a tone and a noise floor -- tonal and broadband content in every frame, the first
+    n_fft / 2 + 1 samples included."""
+    return (0.5 * piano_clips_f32(1, 7 + i)[0] + 0.5 * synth.tone_noise_clip(i, tone_hz=440.0 * (i + 1)))[:n].astype(np.float32)
