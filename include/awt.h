@@ -253,6 +253,14 @@ int awt_audio_encode(awt_encoder* e, const void* pcm, int pcm_is_i16, int64_t pc
                      int max_valid, int B, float* input_features_out, float* last_hidden_state, void* workspace,
                      size_t ws_bytes, void* stream);
 
+/* Clip lengths reach the encoder through awt_audio_encode only.  The log-mel front-end pads a clip with one constant per clip from its
+ * last live frame on, so every position of the conv stem past the live frames but the last one is the same vector: awt_audio_encode
+ * computes the stem for the first awt_conv_stem_positions(n_ctx, max_valid) positions of each clip and copies the rest (bit-identical
+ * to computing all of them; tuning knob "conv_live").  The bound is log-mel's contract: max_valid >= every n_valid[b].  Returns n_ctx
+ * when every position has to be computed (clips of the full 30 s); needs no GPU.  awt_encoder_forward and awt_encoder_forward_train
+ * take a mel without lengths and compute every position. */
+int awt_conv_stem_positions(int n_ctx, int max_valid);
+
 /* ------------------------------------------------------------------------------------------------------
  * Single-operator entry points (what the encoder is made of; used by the per-kernel parity tests).
  * Row-major float32 in / out; bf16 splitting happens inside.  `terms` = 1 or 3 as in awt_encoder_cfg. */
@@ -454,7 +462,9 @@ int awt_op_dtw(awt_ctx* c, const float* matrix, int clips, int T, int frames, co
  * fc1; default 12 = the MLP pair, where it is measurably ahead).  Same products and the same accumulation order per output as the
  * 128 x 256 kernel's 16 x 16 form: bit-identical results where both apply.
  * "gemm_mfma16": 1 (default) = the 128 x 256 f16f8 GEMM issues its products as 16 x 16 MFMAs (both e4m3 cross terms in one block-scaled
- * instruction), 0 = the 32 x 32 form (results differ by the fp32 summation order only). */
+ * instruction), 0 = the 32 x 32 form (results differ by the fp32 summation order only).
+ * "conv_live": 1 (default) = awt_audio_encode's conv stem computes awt_conv_stem_positions(n_ctx, max_valid) positions per clip and
+ * copies the padded tail, 0 = it always computes every position.  Bit-identical results; the knob exists for A/B runs and tests. */
 int awt_tuning_set(const char* key, int value);
 
 /* ------------------------------------------------------------------------------------------------------

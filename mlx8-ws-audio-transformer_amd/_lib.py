@@ -78,6 +78,7 @@ _SIGNATURES = {
     "awt_encoder_set_comm": (_i, [_vp, _vp, _i]),
     "awt_audio_encode_workspace_bytes": (_sz, [_vp, _i]),
     "awt_audio_encode": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "awt_conv_stem_positions": (_i, [_i, _i]),
     "awt_op_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "awt_op_linear_workspace_bytes": (_sz, [_i, _i, _i]),
     "awt_op_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
@@ -215,3 +216,8 @@ def prof_collect(klass: str):
 def tuning_set(key: str, value: int) -> None:
     """Process-wide tuning / test hook (include/awt.h: awt_tuning_set), e.g. tuning_set("gemm_tile", 128)."""
     check(lib().awt_tuning_set(key.encode(), int(value)))
+
+
+def conv_stem_positions(n_ctx: int, max_valid: int) -> int:
+    """Positions per clip the conv stem of `awt_audio_encode` computes when no clip holds more than max_valid samples (n_ctx = all); no GPU needed."""
+    return int(lib().awt_conv_stem_positions(int(n_ctx), int(max_valid)))

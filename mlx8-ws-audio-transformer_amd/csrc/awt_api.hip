@@ -39,6 +39,7 @@ void awt_prof_end(awt_ctx* c, int klass, hipStream_t s) {
   p->spans[klass].push_back(p->open[klass]);
 }
 
+static int g_conv_live = 1;  // tuning knob "conv_live": 1 = awt_audio_encode's conv stem computes the live positions only (conv_stem), 0 = always every position
 static int g_pp_mask = 12;   // tuning knob "gemm_pp_mask": which of a layer's four projections may take the ping-pong GEMM (default: fc1 + fc2, profiles/r04_gemm_pp16_masks.txt)
 extern "C" int awt_tuning_set(const char* key, int value) {
   AWT_REQUIRE(key, AWT_ERR_INVALID, "tuning_set: null key");
@@ -65,6 +66,11 @@ extern "C" int awt_tuning_set(const char* key, int value) {
   if (!strcmp(key, "gemm_mfma16")) {
     AWT_REQUIRE(value == 0 || value == 1, AWT_ERR_INVALID, "tuning_set: gemm_mfma16 must be 1 (default: the f16f8 GEMM's 16 x 16 MFMA form where it applies) or 0 (32 x 32 only)");
     awt_gemm_set_mfma16(value);
+    return AWT_OK;
+  }
+  if (!strcmp(key, "conv_live")) {
+    AWT_REQUIRE(value == 0 || value == 1, AWT_ERR_INVALID, "tuning_set: conv_live must be 1 (default: the conv stem of awt_audio_encode computes the live positions only) or 0 (every position)");
+    g_conv_live = value;
     return AWT_OK;
   }
   if (!strcmp(key, "attn_shape")) {
@@ -228,6 +234,7 @@ struct awt_encoder {
   int prec = PREC_BF16X3;  // operand precision of the forward pass (cfg.mfma_terms: common.h PREC_*)
   Linear conv1, conv2;
   float* pos = nullptr;    // [S, d]
+  float* zero_row = nullptr;   // [d] zeros: the "positional table" of the compact conv stem's conv2 (conv_stem)
   float *lnf_g = nullptr, *lnf_b = nullptr;
   std::vector<Layer> layers;
   std::vector<void*> allocs;
@@ -474,26 +481,36 @@ TrainWs carve_train(const awt_encoder* e, char* base, int B) {
 }
 
 // conv stem (K5-K7): mel [Bc, n_mels, T] -> residual stream x [Bc * S, d] fp32
-int conv_stem(awt_encoder* e, const float* mel, int Bc, bf16_t* const a1[2], bf16_t* const h1[2], float* x, hipStream_t s, bf16_t* const* pre1 = nullptr) {
+// Sc in (0, S), inference with known clip lengths only (awt_audio_encode): frames from 2 Sc - 4 on are one constant per clip (conv_stem_positions), so the
+// stem runs on the first Tc = 2 Sc frames (same zero padding at both ends, mel row pitch still T) into g [Bc * Sc, d], and launch_expand_conv_rows spreads
+// g's last two rows over positions Sc - 1 .. S - 1 while it adds the positional table.  a1 / h1 are then planes of Bc * Tc rows.  Bit-identical to the full
+// stem: the same kernels run (GemmOut::m_pick: chosen as for the full row count), a row's dot products do not depend on the tile it lands in, conv2's
+// epilogue adds a zero row (rows_pos = 1) where the full stem adds pos -- gelu + 0 is gelu -- and the expand kernel makes that same fp32 add afterwards.
+int conv_stem(awt_encoder* e, const float* mel, int Bc, bf16_t* const a1[2], bf16_t* const h1[2], float* x, hipStream_t s, bf16_t* const* pre1 = nullptr,
+              int Sc = 0, float* g = nullptr) {
   const awt_encoder_cfg& c = e->cfg;
   const int S = c.n_ctx, T = 2 * S, d = c.d_model, terms = e->prec;
-  const int M = Bc * S, Mt = Bc * T;
+  const bool compact = Sc > 0 && Sc < S && g && !pre1;
+  const int So = compact ? Sc : S, To = 2 * So;       // positions and frames computed per clip
+  const int M = Bc * So, Mt = Bc * To;
   const int k1 = conv1_k(c.n_mels);
   const Act aa1 = make_act(a1[0], a1[1], (size_t)Mt * k1, terms), ah1 = make_act(h1[0], h1[1], (size_t)Mt * d, terms);
-  int rc = launch_im2col_conv1(e->ctx, mel, Bc, c.n_mels, T, k1, aa1, terms, s); if (rc) return rc;
+  int rc = launch_im2col_conv1(e->ctx, mel, Bc, c.n_mels, T, To, k1, aa1, terms, s); if (rc) return rc;
   {
     GemmSeg sg = seg_plain(aa1, k1, e->conv1.w, 0, k1, Mt);
-    GemmOut o{}; set_out(o, ah1); o.ldo = d; o.bias = e->conv1.bias; o.n_valid = d;
+    GemmOut o{}; set_out(o, ah1); o.ldo = d; o.bias = e->conv1.bias; o.n_valid = d; o.m_pick = Bc * T;
     if (pre1) { o.hi2 = pre1[0]; o.lo2 = pre1[1]; }   // train_base: conv1's pre-activation is kept for its GELU' in the backward pass
     rc = launch_gemm(e->ctx, Mt, d, &sg, 1, terms, pre1 ? EPI_BF16_GELU_SAVE : EPI_BF16_GELU, o, s); if (rc) return rc;
   }
   GemmSeg sg[3];
   for (int dt = 0; dt < 3; ++dt) {
     sg[dt] = seg_plain(ah1, d, e->conv2.w, (int64_t)dt * d, d, M);
-    sg[dt].rows_out = S; sg[dt].rows_in = T; sg[dt].row_mul = 2; sg[dt].row_add = dt - 1;
+    sg[dt].rows_out = So; sg[dt].rows_in = To; sg[dt].row_mul = 2; sg[dt].row_add = dt - 1;
   }
-  GemmOut o{}; o.f32 = x; o.ldo = d; o.bias = e->conv2.bias; o.n_valid = d; o.pos = e->pos; o.rows_pos = S;
-  return launch_gemm(e->ctx, M, d, sg, 3, terms, EPI_F32_GELU_POS, o, s);
+  GemmOut o{}; o.f32 = compact ? g : x; o.ldo = d; o.bias = e->conv2.bias; o.n_valid = d; o.m_pick = Bc * S;
+  if (compact) { o.pos = e->zero_row; o.rows_pos = 1; } else { o.pos = e->pos; o.rows_pos = S; }
+  rc = launch_gemm(e->ctx, M, d, sg, 3, terms, EPI_F32_GELU_POS, o, s); if (rc || !compact) return rc;
+  return launch_expand_conv_rows(e->ctx, g, e->pos, Bc, S, Sc, d, x, s);
 }
 
 // one transformer layer (K8-K13) on the given buffers; `save` also keeps the MLP pre-activation and the softmax statistics
@@ -555,14 +572,29 @@ int encoder_layer(awt_encoder* e, Layer& L, const LayerBufs& b, int Bc, bool sav
   return pp_fc2 ? linear_pp(e, b.ff[0], L.fc2, M, EPI_F32_RESID, o, s) : linear_with_lora(e, b.u2, b.ff, f, L.fc2, L.l2, M, EPI_F32_RESID, o, s);
 }
 
-int forward_chunk(awt_encoder* e, const float* mel, int Bc, float* hidden, char* ws_base, hipStream_t s) {
+// Sc: positions per clip the conv stem has to compute (conv_stem_positions; 0 or >= n_ctx: all of them)
+int forward_chunk(awt_encoder* e, const float* mel, int Bc, float* hidden, char* ws_base, hipStream_t s, int Sc = 0) {
   const awt_encoder_cfg& c = e->cfg;
   const int M = Bc * c.n_ctx, d = c.d_model;
   const bool two = e->planes == 2;
   Workspace w = carve(e, ws_base, Bc);
   bf16_t* a1[2] = {w.a1[0], two ? w.a1[1] : nullptr};
   bf16_t* h1[2] = {w.h1[0], two ? w.h1[1] : nullptr};
-  int rc = conv_stem(e, mel, Bc, a1, h1, w.x, s); if (rc) return rc;
+  float* g = nullptr;
+  if (Sc > 0 && Sc < c.n_ctx) {
+    // the compact stem's planes (Bc * 2 Sc rows) and its output g [Bc * Sc, d] share the region the full-length conv planes and the layer buffers
+    // alias; a shape whose region has no room for g beside the shorter planes (none of Whisper's) keeps the full stem
+    char* const base = (char*)w.a1[0];
+    const size_t room = (size_t)(ws_base + w.bytes - base), Mt = (size_t)Bc * 2 * Sc;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = base + off; off += align_up(bytes); return p; };
+    bf16_t *ca1[2] = {nullptr, nullptr}, *ch1[2] = {nullptr, nullptr};
+    for (int p = 0; p < e->planes; ++p) ca1[p] = (bf16_t*)take(Mt * conv1_k(c.n_mels) * 2);
+    for (int p = 0; p < e->planes; ++p) ch1[p] = (bf16_t*)take(Mt * d * 2);
+    float* cg = (float*)take((size_t)Bc * Sc * d * 4);
+    if (off <= room) { g = cg; for (int p = 0; p < 2; ++p) { a1[p] = ca1[p]; h1[p] = ch1[p]; } }
+  }
+  int rc = conv_stem(e, mel, Bc, a1, h1, w.x, s, nullptr, g ? Sc : 0, g); if (rc) return rc;
   LayerBufs b{};
   b.x_in = b.x_mid = b.x_out = w.x;
   for (int p = 0; p < 2; ++p) {
@@ -683,6 +715,7 @@ extern "C" int awt_encoder_create(awt_ctx* c, const awt_encoder_cfg* cfg, awt_en
   for (int dt = 0; dt < 3 && !rc && e->train_base; ++dt) rc = alloc_planes(e, &e->conv2T[dt], d, d);
   if (!rc) rc = alloc_linear(e, &e->conv2, d, 3 * d);
   if (!rc) rc = dev_alloc(e, (void**)&e->pos, (size_t)cfg->n_ctx * d * 4);
+  if (!rc) rc = dev_alloc(e, (void**)&e->zero_row, (size_t)d * 4);
   if (!rc) rc = dev_alloc(e, (void**)&e->lnf_g, (size_t)d * 4);
   if (!rc) rc = dev_alloc(e, (void**)&e->lnf_b, (size_t)d * 4);
   e->layers.resize(cfg->n_layers);
@@ -881,6 +914,8 @@ extern "C" int awt_audio_encode(awt_encoder* e, const void* pcm, int pcm_is_i16,
   hipStream_t s = (hipStream_t)stream;
   const int T = 2 * e->cfg.n_ctx;
   const int chunk = std::min(B, e->chunk);
+  // log-mel pads every clip with one constant from its last live frame on; the conv stem computes the positions that see live frames (plus two) and copies the rest
+  const int Sc = g_conv_live ? conv_stem_positions(e->cfg.n_ctx, max_valid) : 0;
   char* base = (char*)workspace;
   const size_t enc_bytes = carve(e, nullptr, chunk).bytes;
   float* mel_buf = (float*)(base + enc_bytes);
@@ -892,11 +927,13 @@ extern "C" int awt_audio_encode(awt_encoder* e, const void* pcm, int pcm_is_i16,
     rc = logmel_whisper_impl(e->ctx, (const char*)pcm + (size_t)b0 * pcm_stride * esz, pcm_is_i16, pcm_stride,
                              n_valid ? n_valid + b0 : nullptr, max_valid, Bc, T, e->cfg.n_mels, mel, lm_ws, awt_logmel_workspace_bytes(Bc), s);
     if (rc) return rc;
-    rc = forward_chunk(e, mel, Bc, hidden + (size_t)b0 * e->cfg.n_ctx * e->cfg.d_model, base, s);
+    rc = forward_chunk(e, mel, Bc, hidden + (size_t)b0 * e->cfg.n_ctx * e->cfg.d_model, base, s, Sc);
     if (rc) return rc;
   }
   return AWT_OK;
 }
+
+extern "C" int awt_conv_stem_positions(int n_ctx, int max_valid) { return conv_stem_positions(n_ctx, max_valid); }
 
 // ------------------------------------------------------------------------------------------------ single operators
 extern "C" size_t awt_op_linear_workspace_bytes(int M, int N, int K) {

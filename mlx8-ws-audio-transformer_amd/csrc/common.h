@@ -358,6 +358,8 @@ struct GemmOut {
   int S, H;                               // EPI_QKV: m = b * S + s ; plane stride = B*H*S*64
   int64_t plane_stride;
   int skip_v8;                            // EPI_QKV, f16f8: do not write the e4m3 images of v (the single-product P V attention reads only its fp16 plane)
+  int m_pick;                             // > 0: the kernel (tile and MFMA form) is chosen as for a launch of this many rows instead of M -- the compact conv stem
+                                          // runs the kernels of the full-length stem, whose fp32 summation order it must keep (0 = M)
 };
 
 // `prec`: PREC_* of the operands (and of plane outputs)
@@ -397,8 +399,13 @@ int launch_attention_f16f8(awt_ctx* c, const F8Planes& q, const F8Planes& k, con
 int launch_pack_weight(awt_ctx* c, const float* src, int N, int C, int taps, int64_t ld, int row_off, int col_off, float scale,
                        bf16_t* hi, bf16_t* lo, uint8_t* lo8, int prec, hipStream_t s, int* inexact = nullptr,    // inexact (PREC_F16F8, device int): set to 1 when a weight is not fp16-exact
                        bf16_t* s16 = nullptr, uint8_t* s8 = nullptr);                                            // PREC_F16F8: also the 16-row copies (w_frag_index / w8s_index) when given
-// conv1 im2col: mel f32 [B, C, T] -> A [B*T, K_dst] bf16 hi/lo, k = dt * C + c reads mel[b, c, t + dt - 1]
-int launch_im2col_conv1(awt_ctx* c, const float* mel, int B, int C, int T, int K_dst, const Act& out, int prec, hipStream_t s);
+// conv1 im2col: the first T frames of mel f32 [B, C, T_mel] -> A [B*T, K_dst] bf16 hi/lo, k = dt * C + c reads mel[b, c, t + dt - 1] (zero outside [0, T))
+int launch_im2col_conv1(awt_ctx* c, const float* mel, int B, int C, int T_mel, int T, int K_dst, const Act& out, int prec, hipStream_t s);
+// conv stem on the live positions only (awt_api.hip, conv_stem): x [B * S, d] = g[b, src(p)] + pos[p] with g [B * Sc, d] the stem of the first 2 Sc frames before
+// the positional add and src(p) = p for p < Sc - 1, Sc - 2 (the constant row) up to S - 2, Sc - 1 (the row that sees conv1's right padding) at S - 1
+int launch_expand_conv_rows(awt_ctx* c, const float* g, const float* pos, int B, int S, int Sc, int d, float* x, hipStream_t s);
+// positions of a clip the conv stem has to compute when no clip holds more than max_valid samples (n_ctx = all of them); logmel.hip
+int conv_stem_positions(int n_ctx, int max_valid);
 
 int logmel_whisper_impl(awt_ctx* c, const void* pcm, int pcm_is_i16, int64_t pcm_stride, const int32_t* n_valid,
                         int max_valid, int B, int n_frames_out, int n_mels, float* out, void* workspace, size_t ws_bytes, hipStream_t s,

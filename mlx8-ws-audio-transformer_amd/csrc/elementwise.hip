@@ -162,21 +162,21 @@ __global__ __launch_bounds__(256) void pack_weight_pp_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------ conv1 im2col
-// mel fp32 [B, C, T] -> A [B * T, K_dst] bf16 planes with A[(b, t), dt * C + c] = mel[b, c, t + dt - 1] (zero outside
-// the clip: Conv1d padding = 1, HF:modeling_whisper.py:566).  A 64-frame slab of the clip is staged in LDS with
-// reads coalesced along t; rows are written as whole 16-byte groups so each row is one contiguous K_dst * 2 B store.
+// mel fp32 [B, C, T_mel] -> A [B * T, K_dst] bf16 planes with A[(b, t), dt * C + c] = mel[b, c, t + dt - 1] (zero outside
+// [0, T): Conv1d padding = 1, HF:modeling_whisper.py:566; T < T_mel = the conv stem on the first T frames only).  A 64-frame slab of the clip is
+// staged in LDS with reads coalesced along t; rows are written as whole 16-byte groups so each row is one contiguous K_dst * 2 B store.
 constexpr int kImTile = 64;
 template <int PREC>
-__global__ __launch_bounds__(256) void im2col_conv1_kernel(const float* __restrict__ mel, int C, int T, int K_dst, Act out) {
+__global__ __launch_bounds__(256) void im2col_conv1_kernel(const float* __restrict__ mel, int C, int T_mel, int T, int K_dst, Act out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* tile = reinterpret_cast<float*>(smem);   // [C][kImTile + 2], pitch kImTile + 3 (odd: conflict-free column reads)
   const int pitch = kImTile + 3;
   const int b = blockIdx.y, t0 = blockIdx.x * kImTile;
-  const float* mb = mel + (int64_t)b * C * T;
+  const float* mb = mel + (int64_t)b * C * T_mel;
   for (int i = threadIdx.x; i < C * (kImTile + 2); i += 256) {
     const int c = i / (kImTile + 2), tt = i - c * (kImTile + 2);
     const int t = t0 + tt - 1;
-    tile[c * pitch + tt] = (t >= 0 && t < T) ? mb[(int64_t)c * T + t] : 0.f;
+    tile[c * pitch + tt] = (t >= 0 && t < T) ? mb[(int64_t)c * T_mel + t] : 0.f;
   }
   __syncthreads();
   const int groups = K_dst / 8;
@@ -192,6 +192,34 @@ __global__ __launch_bounds__(256) void im2col_conv1_kernel(const float* __restri
     const int64_t off = ((int64_t)b * T + t) * K_dst + g * 8;
     store_act4<PREC>(out, off, v[0]);
     store_act4<PREC>(out, off + 4, v[1]);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ conv stem: compact rows -> residual stream
+// x[b, p] = g[b, src(p)] + pos[p]: the conv stem computed Sc positions per clip (g, before the positional add; awt_api.hip conv_stem); positions
+// Sc - 1 .. S - 2 all equal row Sc - 2 and position S - 1 is row Sc - 1.  The fp32 add is the one conv2's epilogue makes on the full-length path.
+// Pure streaming, one wave per row as in layernorm_kernel (the row arithmetic is wave-uniform, the row's loads are issued together), 16 bytes per lane and
+// piece: x is written once; g and pos stay in the caches.
+__global__ __launch_bounds__(256) void expand_conv_rows_kernel(const float4* __restrict__ g, const float4* __restrict__ pos, int rows, int S, int Sc, int d4,
+                                                                float4* __restrict__ x) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int b = row / S, p = row - b * S;
+  const int src = p < Sc - 1 ? p : (p == S - 1 ? Sc - 1 : Sc - 2);
+  const float4* gr = g + ((int64_t)b * Sc + src) * d4;
+  const float4* pr = pos + (int64_t)p * d4;
+  float4* xr = x + (int64_t)row * d4;
+  float4 v[kLnMaxChunks], q[kLnMaxChunks];
+#pragma unroll
+  for (int i = 0; i < kLnMaxChunks; ++i) {
+    const int c = lane + 64 * i;
+    if (c < d4) { v[i] = gr[c]; q[i] = pr[c]; }
+  }
+#pragma unroll
+  for (int i = 0; i < kLnMaxChunks; ++i) {
+    const int c = lane + 64 * i;
+    if (c < d4) xr[c] = make_float4(v[i].x + q[i].x, v[i].y + q[i].y, v[i].z + q[i].z, v[i].w + q[i].w);
   }
 }
 
@@ -465,15 +493,25 @@ int launch_pack_weight(awt_ctx* c, const float* src, int N, int C, int taps, int
   return AWT_OK;
 }
 
-int launch_im2col_conv1(awt_ctx* c, const float* mel, int B, int C, int T, int K_dst, const Act& out, int prec, hipStream_t s) {
-  AWT_REQUIRE(mel && out.p16 && B > 0 && C > 0 && C % 8 == 0 && T > 0 && K_dst % 8 == 0 && K_dst >= 3 * C, AWT_ERR_INVALID, "im2col: bad shape");
+int launch_im2col_conv1(awt_ctx* c, const float* mel, int B, int C, int T_mel, int T, int K_dst, const Act& out, int prec, hipStream_t s) {
+  AWT_REQUIRE(mel && out.p16 && B > 0 && C > 0 && C % 8 == 0 && T > 0 && T <= T_mel && K_dst % 8 == 0 && K_dst >= 3 * C, AWT_ERR_INVALID, "im2col: bad shape");
   AWT_REQUIRE(prec != PREC_F16F8 || (out.hi8 && out.lo8), AWT_ERR_INVALID, "im2col: f16f8 output needs both e4m3 planes");
   ProfScope prof(c, AWT_PROF_OTHER, s, 0.0);
   const size_t lds = (size_t)C * (kImTile + 3) * sizeof(float);
   const dim3 grid((T + kImTile - 1) / kImTile, B), block(256);
-  if (prec == PREC_F16F8) hipLaunchKernelGGL(im2col_conv1_kernel<PREC_F16F8>, grid, block, lds, s, mel, C, T, K_dst, out);
-  else if (prec == PREC_F16X3 || prec == PREC_F16) hipLaunchKernelGGL(im2col_conv1_kernel<PREC_F16X3>, grid, block, lds, s, mel, C, T, K_dst, out);
-  else hipLaunchKernelGGL(im2col_conv1_kernel<PREC_BF16X3>, grid, block, lds, s, mel, C, T, K_dst, out);
+  if (prec == PREC_F16F8) hipLaunchKernelGGL(im2col_conv1_kernel<PREC_F16F8>, grid, block, lds, s, mel, C, T_mel, T, K_dst, out);
+  else if (prec == PREC_F16X3 || prec == PREC_F16) hipLaunchKernelGGL(im2col_conv1_kernel<PREC_F16X3>, grid, block, lds, s, mel, C, T_mel, T, K_dst, out);
+  else hipLaunchKernelGGL(im2col_conv1_kernel<PREC_BF16X3>, grid, block, lds, s, mel, C, T_mel, T, K_dst, out);
+  AWT_HIP_CHECK(hipGetLastError());
+  return AWT_OK;
+}
+
+int launch_expand_conv_rows(awt_ctx* c, const float* g, const float* pos, int B, int S, int Sc, int d, float* x, hipStream_t s) {
+  AWT_REQUIRE(g && pos && x && B > 0 && Sc >= 2 && Sc < S && d > 0 && d % 4 == 0 && d <= 64 * 4 * kLnMaxChunks, AWT_ERR_INVALID, "expand_conv_rows: bad shape (2 <= Sc < S, d % 4 == 0, d <= 1280)");
+  AWT_REQUIRE((int64_t)B * S < (int64_t)1 << 30, AWT_ERR_INVALID, "expand_conv_rows: more than 2^30 rows");
+  ProfScope prof(c, AWT_PROF_OTHER, s, 0.0);
+  const int rows = B * S;
+  hipLaunchKernelGGL(expand_conv_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, (const float4*)g, (const float4*)pos, rows, S, Sc, d / 4, (float4*)x);
   AWT_HIP_CHECK(hipGetLastError());
   return AWT_OK;
 }

@@ -595,7 +595,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f8_kernel(GemmArgs g) {
     nk = sg.K / BK;
     // The per-lane offsets are 32-bit and RELATIVE to the first source row of the tile, which goes into the 64-bit (SGPR) plane bases: a tile
     // spans at most 128 row_mul + 2 source rows, so the offsets stay small however large the activation planes are (a plane of 64+ clips of
-    // Whisper-large's MLP hidden exceeds 4 GiB; offsets from the plane base overflowed there).
+    // Whisper-large's MLP hidden exceeds 4 GiB; offsets from the plane base overflowed there).  The span holds however many row groups the
+    // tile crosses (the compact conv stem has groups of a few rows) because every row map has rows_in == row_mul * rows_out (launch_gemm
+    // checks it): the groups' source rows then follow each other without a gap, and a later group's rows lie above base_row.
     const int mb = am0 < g.M ? am0 : g.M - 1;
     const int grp0 = mb / sg.rows_out;
     const int sr0 = (mb - grp0 * sg.rows_out) * sg.row_mul + sg.row_add;
@@ -1253,6 +1255,7 @@ int pick_tile(int M, int N, int batch = 1) {
 
 template <int EPI>
 int launch_epi(GemmArgs a, int prec, hipStream_t s) {
+  const int Mp = a.out.m_pick > 0 ? a.out.m_pick : a.M;     // rows the kernel is chosen for (GemmOut::m_pick)
   if (prec == PREC_F16F8) {
     // the 16 x 16 MFMA form: one segment that carries its 16-row weight copies and takes no fp16-exact shortcut (multi-segment K loops keep the 32 x 32
     // kernel: their per-segment address state does not fit beside the 16 x 16 form's fragment rings).  It also takes N % 256 != 0 (Whisper-tiny: 384, 1152)
@@ -1261,14 +1264,14 @@ int launch_epi(GemmArgs a, int prec, hipStream_t s) {
     const int n256 = (a.N + 255) / 256 * 256;
     const bool f8s_ok = g_mfma16 && a.nseg == 1 && a.seg[0].ws16 && a.seg[0].ws8 && a.seg[0].a8 && !a.seg[0].w_exact16 &&
                         (a.N % 256 == 0 || (a.seg[0].ws_rows >= n256 && (int64_t)n256 * 3 <= (int64_t)a.N * 4));
-    const int64_t t256f = (int64_t)((a.M + 127) / 128) * (f8s_ok ? n256 / 256 : a.N / 256);
+    const int64_t t256f = (int64_t)((Mp + 127) / 128) * (f8s_ok ? n256 / 256 : a.N / 256);
     int tile = g_force_tile;
     if (!tile) tile = ((a.N % 256 == 0 || f8s_ok) && t256f >= kSlots) ? 256 : 128;
     if (tile == 256 && f8s_ok) return launch_f8s<EPI>(a, s);
     if (tile == 256 && a.N % 256 == 0) return launch_f8<EPI, CfgF8W4>(a, s);
     return launch_f8<EPI, CfgF8Sq>(a, s);
   }
-  const int tile = pick_tile(a.M, a.N);
+  const int tile = pick_tile(Mp, a.N);
   if (prec == PREC_F16X3) {      // fp16 hi / lo planes on the same kernels
     if (a.nseg == 1 && a.seg[0].w_exact16) {     // fp16-exact weights: two products per fragment pair
       if (tile == 256) return launch_one<3, 32, EPI, CfgW4, true, true>(a, s);
@@ -1387,7 +1390,8 @@ int launch_gemm(awt_ctx* c, int M, int N, const GemmSeg* segs, int nseg, int pre
     else AWT_REQUIRE(segs[i].a_hi && segs[i].w_hi && (terms == 1 || (segs[i].a_lo && segs[i].w_lo)), AWT_ERR_INVALID, "gemm: null operand plane");
     AWT_REQUIRE(segs[i].lda % 8 == 0 && segs[i].w_ksteps > 0 && segs[i].w_k0 >= 0 && segs[i].w_k0 + segs[i].K / 32 <= segs[i].w_ksteps, AWT_ERR_INVALID,
                 "gemm: lda must be a multiple of 8 and the segment must lie inside its fragment-major weight matrix");
-    AWT_REQUIRE(segs[i].rows_out > 0 && segs[i].rows_in > 0, AWT_ERR_INVALID, "gemm: bad row map");
+    AWT_REQUIRE(segs[i].rows_out > 0 && segs[i].rows_in > 0 && segs[i].row_mul > 0 && (int64_t)segs[i].row_mul * segs[i].rows_out == segs[i].rows_in, AWT_ERR_INVALID,
+                "gemm: bad row map (rows_in must be row_mul * rows_out)");
     ksum += segs[i].K;
   }
   ProfScope prof(c, AWT_PROF_GEMM, s, 2.0 * (double)M * (double)out.n_valid * ksum);

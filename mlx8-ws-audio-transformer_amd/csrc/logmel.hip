@@ -345,6 +345,19 @@ int host_live_frames(int n_valid, int n_fft, int hop, int T_out) {
 
 }  // namespace
 
+// Positions of a clip the conv stem has to compute when no clip of the batch holds more than max_valid samples (n_ctx = all of them): frames from
+// `live` on are one constant per clip (logmel_finalize_kernel), so from P0 = (live + 3) / 2 on -- the first position whose three conv2 taps read
+// constant conv1 outputs only -- every position but the last (conv1's right zero padding reaches it) is the same vector.  Sc = P0 + 2 rows of the
+// stem on the first 2 Sc frames hold everything: rows 0 .. Sc - 2 as they are (Sc - 2 is the constant row), row Sc - 1 is position n_ctx - 1.
+int conv_stem_positions(int n_ctx, int max_valid) {
+  if (n_ctx <= 0) return 0;
+  const int n_fft = 400, hop = 160, T = 2 * n_ctx;
+  const int64_t L = (int64_t)T * hop;
+  const int live = host_live_frames((int)(max_valid < L ? max_valid : L), n_fft, hop, T);
+  const int Sc = (live + 3) / 2 + 2;
+  return Sc < n_ctx ? Sc : n_ctx;
+}
+
 size_t awt_logmel_workspace_bytes(int B) { return (((size_t)(B > 0 ? B : 1) * sizeof(unsigned)) + 255) & ~(size_t)255; }
 
 // Builds (once per context) the device tables a front-end configuration needs: the DFT basis of n_fft and the mel filter bank.

@@ -30,6 +30,8 @@ class Lib:
         self.path = spec
         self.L = C.CDLL(os.path.abspath(path))
         for name, (res, args) in _lib._SIGNATURES.items():
+            if not hasattr(self.L, name):      # a library of an earlier commit lacks the entry points added since
+                continue
             fn = getattr(self.L, name)
             fn.restype, fn.argtypes = res, args
         out = C.c_void_p()
