@@ -82,14 +82,12 @@ __global__ __launch_bounds__(kThreads, 2) void attention_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // XCD-aware 1-D grid: the hardware deals block i to XCD i % 8; remap so that each XCD owns a contiguous run of
-  // (head, query-block) pairs -- the query blocks of one head then share that XCD's L2 copy of the head's K and V
+  // XCD-contiguous 1-D grid (common.h xcd_contiguous): each XCD owns a contiguous run of (head, query-block) pairs -- the query
+  // blocks of one head then share that XCD's L2 copy of the head's K and V
   // (without this every XCD fetched every head: 5.1 GB of HBM reads per launch against 0.9 GB algorithmic).
   const int nqb = (a.S + QB - 1) / QB;
   const int nwg = nqb * a.B * a.H;
-  const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  const int qd = nwg >> 3, rm = nwg & 7;
-  const int logical = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
+  const int logical = xcd_contiguous(blockIdx.x, nwg);
   const int bh = logical / nqb;                   // b * H + h
   const int b = bh / a.H, h = bh - b * a.H;
   const int q0 = (logical - bh * nqb) * QB + wave * QW;

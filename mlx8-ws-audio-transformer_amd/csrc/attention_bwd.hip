@@ -152,9 +152,7 @@ __global__ __launch_bounds__(kThreads, 2) void attention_bwd_kernel(BwdArgs a) {
   // XCD-aware 1-D grid (see attention.hip): the blocks of one head run on one XCD and share its L2 copy of the tiles
   const int nlb = (a.S + LB - 1) / LB;
   const int nwg = nlb * a.B * a.H;
-  const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  const int qd = nwg >> 3, rm = nwg & 7;
-  const int logical = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
+  const int logical = xcd_contiguous(blockIdx.x, nwg);
   const int bh = logical / nlb;
   const int b = bh / a.H, h = bh - b * a.H;
   const int l0 = (logical - bh * nlb) * LB + wave * LW;

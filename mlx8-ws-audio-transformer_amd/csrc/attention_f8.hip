@@ -127,9 +127,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f16f8_pipe_kernel(Attn8A
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nqb = (a.S + QB - 1) / QB;
   const int nwg = nqb * a.B * a.H;
-  const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  const int qd = nwg >> 3, rm = nwg & 7;
-  const int logical = (xcd < rm ? xcd * (qd + 1) : rm * (qd + 1) + (xcd - rm) * qd) + idx;
+  const int logical = xcd_contiguous(blockIdx.x, nwg);     // as attention.hip: the query blocks of one head share an XCD's L2 copy of its K and V
   const int bh = logical / nqb;
   const int b = bh / a.H, h = bh - b * a.H;
   const int q0 = (logical - bh * nqb) * QB + wave * 32;

@@ -218,7 +218,7 @@ __host__ __device__ __forceinline__ int64_t w8s_index(int n, int k, int ktiles64
 }
 
 // An activation matrix as MFMA operand planes: p16 (bf16 or fp16) + lo16 (split modes) or + hi8 / lo8 (f16f8).
-// ilv (PREC_F16F8 only, instead of the three planes): the SPLIT-LINE image the ping-pong GEMM (gemm_pp.h, FMT_F16F8S) stages by whole cache
+// ilv (PREC_F16F8 only, instead of the three planes): the SPLIT-LINE image the ping-pong GEMM (gemm_pp.h) stages by whole cache
 // lines -- a dense [M][K] matrix, K % 64 == 0, as [M][K / 64] pairs of 128-byte lines: the 64 elements' fp16 (the "X" line), then their hi8 x 64 | lo8 x 64
 // (the "Y" line), so that element offset `off` lives in pair off >> 6 (256 bytes) at e = off & 63: fp16 byte 2 e, hi8 byte 128 + e, lo8 byte 192 + e.
 struct Act { bf16_t* p16 = nullptr; bf16_t* lo16 = nullptr; uint8_t* hi8 = nullptr; uint8_t* lo8 = nullptr; char* ilv = nullptr; };
@@ -246,6 +246,37 @@ __device__ __forceinline__ void store_act4(const Act& o, int64_t off, const floa
     *reinterpret_cast<uint2*>(o.p16 + off) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
     if (o.lo16) *reinterpret_cast<uint2*>(o.lo16 + off) = make_uint2(pack2(l[0], l[1]), pack2(l[2], l[3]));
   }
+}
+
+// ---------------------------------------------------------------- workgroup order and row maps (device), shared by the GEMM, weight-gradient and attention kernels
+// XCD-contiguous remap of a 1-D grid of n workgroups: the hardware deals block b to XCD b % 8; the logical index returned gives each XCD a contiguous
+// run of logical indices instead (bijective for every n: the first n % 8 XCDs own one index more), so that neighbours in the logical order share an L2.
+// (I = the caller's index type -- blockIdx.x is unsigned, the persistent GEMM's tile index an int -- so that `block >> 3` stays the shift each kernel compiled to)
+template <class I>
+__device__ __forceinline__ int xcd_contiguous(I block, int n) {
+  const int xcd = block & 7, idx = block >> 3;
+  const int q = n >> 3, r = n & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+// GEMM tile order inside an XCD's run: groups of GM row panels, row panel fastest -- GM activation panels stay L2-resident and each
+// weight tile is read by GM workgroups at once.  (Groups of column tiles, which keep a weight slice L2-resident instead, cut the
+// L2 -> fabric reads by 10 - 25 % but ran 1.5 % slower end to end: DESIGN.md section 4.2, profiles/r01_gemm_tile_order.txt.)
+__device__ __forceinline__ void gemm_tile_coords(int tile, int tiles_m, int tiles_n, int GM, int& tm, int& tn) {
+  const int grp = tile / (GM * tiles_n);
+  const int gm = min(GM, tiles_m - grp * GM);
+  const int within = tile - grp * GM * tiles_n;
+  tn = within / gm; tm = grp * GM + (within - tn * gm);
+}
+// Row map of GemmSeg / WgradArgs (the four fields below): src = the source row of output row m, (m / rows_out) * rows_in + (m % rows_out) * row_mul + row_add.
+// Returns false when that row lies outside [0, rows_in) of its group and reads as zero (the conv stem's padding; src is then not a row to read).
+// (Validity is a bool beside the row, not a negative row: hipcc does not fold the sign test of a selected 64-bit value back into the two 32-bit
+// comparisons, and the GEMM kernels are on the register limit -- with a negative row every GemmArgs kernel compiled to different code.)
+__device__ __forceinline__ bool row_map_source(int m, int rows_out, int rows_in, int row_mul, int row_add, int64_t& src) {
+  const int grp = m / rows_out, r = m - grp * rows_out;
+  const int sr = r * row_mul + row_add;               // conv stem: 2 s + tap - 1
+  const bool ok = sr >= 0 && sr < rows_in;
+  src = (int64_t)grp * rows_in + sr;
+  return ok;
 }
 
 // ---------------------------------------------------------------- host-side error plumbing

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void pack_weight_kernel(const float* __restric
   if ((PREC == PREC_F16F8 || PREC == PREC_F16X3) && inexact && __builtin_amdgcn_ballot_w64(any_inexact) != 0 && (threadIdx.x & 63) == 0) atomicOr(inexact, 1);
 }
 
-// The packed weight image of the ping-pong GEMM (gemm_pp.h, FMT_F16F8S): per (256-column tile, K-tile, half) one 16 KB region in LDS image order; the K-tiles
+// The packed weight image of the ping-pong GEMM (gemm_pp.h): per (256-column tile, K-tile, half) one 16 KB region in LDS image order; the K-tiles
 // alternate between the X line (fp16 x 64) and the Y line (lo8 x 64 | hi8 x 64) of 64 consecutive k, each row's 16-byte chunks XOR-swizzled by the row.
 // One thread per four consecutive k of a row.
 __global__ __launch_bounds__(256) void pack_weight_pp_kernel(const float* __restrict__ src, int N, int K, int row_off, char* dst) {

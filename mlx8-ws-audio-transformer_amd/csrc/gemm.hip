@@ -103,10 +103,9 @@ struct Stager {
       const int row = p / T::CPR;
       const int c = (p % T::CPR) ^ swz<BK>(row);                // source chunk that lands in this slot
       int m = m0 + row; m = m < g.M ? m : g.M - 1;              // M tail: clamp (never stored)
-      const int grp = m / sg.rows_out, r = m - grp * sg.rows_out;
-      const int sr = r * sg.row_mul + sg.row_add;               // conv stem: 2 s + tap - 1
-      const bool ok = (sr >= 0) && (sr < sg.rows_in);
-      const int64_t aoff = ((int64_t)grp * sg.rows_in + sr) * sg.lda + c * 8 + za;
+      int64_t src;
+      const bool ok = row_map_source(m, sg.rows_out, sg.rows_in, sg.row_mul, sg.row_add, src);
+      const int64_t aoff = src * sg.lda + c * 8 + za;
       a_hi[it] = ok ? sg.a_hi + aoff : nullptr;
       a_lo[it] = (ok && TERMS == 3) ? sg.a_lo + aoff : nullptr;
     }
@@ -163,9 +162,9 @@ __device__ __forceinline__ float4 load_side4(const GemmOut& o, int m, int n, int
   return r;
 }
 
-// OP = precision of plane outputs (PREC_BF16X3: bf16 hi / lo; PREC_F16X3: fp16 hi / lo; PREC_F16F8: fp16 + two e4m3 planes)
+// F16 = number format of the plane outputs (hi / lo pairs): fp16, else bf16
 // FULL / b: as store_out8_f8 below (no per-row predicate inside a full tile; the lane's bias values are loaded once per tile)
-template <int EPI, int OP, bool FULL>
+template <int EPI, bool F16, bool FULL>
 __device__ __forceinline__ void store_out4(const GemmOut& o, int m, int n, float4 acc, float4 side, float4 b, int M) {
   if constexpr (!FULL) { if (m >= M || n >= o.n_valid) return; }
   float v[4] = {acc.x, acc.y, acc.z, acc.w};
@@ -183,11 +182,9 @@ __device__ __forceinline__ void store_out4(const GemmOut& o, int m, int n, float
     *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
   } else {
     int64_t off;
-    float inv8 = pow2f(-kF8Act), lim8 = 448.0f * pow2f(-kF8Act);          // PREC_F16F8: exponent of the e4m3 planes by operand role (store_out8_f8)
     if (EPI == EPI_QKV) {
       const int d = o.H * 64;
       const int which = n / d, within = n - which * d;
-      inv8 = which == 0 ? pow2f(-kF8Q) : pow2f(-kF8KV); lim8 = which == 0 ? 448.0f * pow2f(-kF8Q) : 448.0f * pow2f(-kF8KV);
       const int h = within >> 6, e = within & 63;
       const int b = m / o.S, s = m - b * o.S;
       if (which == 0) { v[0] *= o.scale; v[1] *= o.scale; v[2] *= o.scale; v[3] *= o.scale; }
@@ -212,20 +209,11 @@ __device__ __forceinline__ void store_out4(const GemmOut& o, int m, int n, float
         for (int t = 0; t < 4; ++t) v[t] = (EPI == EPI_BF16_GELU || EPI == EPI_BF16_GELU_SAVE) ? gelu_erf(v[t]) : v[t] * o.scale;
       }
     }
-    if constexpr (OP == PREC_F16F8) {
-      bf16_t h[4]; float l[4];
+    bf16_t hi[4], lo[4];
 #pragma unroll
-      for (int t = 0; t < 4; ++t) { h[t] = f32_to_f16(v[t]); l[t] = v[t] - f16_to_f32(h[t]); }
-      *reinterpret_cast<uint2*>(o.hi + off) = make_uint2(pack2(h[0], h[1]), pack2(h[2], h[3]));
-      *reinterpret_cast<unsigned*>(o.hi8 + off) = fp8x4_rt(v[0], v[1], v[2], v[3], lim8, inv8);
-      *reinterpret_cast<unsigned*>(o.lo8 + off) = fp8x4_rt(l[0], l[1], l[2], l[3], lim8 * pow2f(-kF8Lo), inv8 * pow2f(-kF8Lo));
-    } else {
-      bf16_t hi[4], lo[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) split16<OP == PREC_F16X3>(v[t], hi[t], lo[t]);
-      *reinterpret_cast<uint2*>(o.hi + off) = make_uint2(pack2(hi[0], hi[1]), pack2(hi[2], hi[3]));
-      if (o.lo) *reinterpret_cast<uint2*>(o.lo + off) = make_uint2(pack2(lo[0], lo[1]), pack2(lo[2], lo[3]));
-    }
+    for (int t = 0; t < 4; ++t) split16<F16>(v[t], hi[t], lo[t]);
+    *reinterpret_cast<uint2*>(o.hi + off) = make_uint2(pack2(hi[0], hi[1]), pack2(hi[2], hi[3]));
+    if (o.lo) *reinterpret_cast<uint2*>(o.lo + off) = make_uint2(pack2(lo[0], lo[1]), pack2(lo[2], lo[3]));
   }
 }
 
@@ -318,19 +306,9 @@ __global__ __launch_bounds__(CFG::WM * CFG::WN * 64, 2) void gemm_kernel(GemmArg
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
-  // XCD-aware bijective remap: hardware deals block b to XCD b % 8; give each XCD a contiguous run of tiles
-  const int nwg = g.tiles_m * g.tiles_n;
-  const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  const int q = nwg >> 3, r = nwg & 7;
-  const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  // Tile order inside an XCD's run: groups of GM row panels, row panel fastest -- GM activation panels stay L2-resident and each
-  // weight tile is read by GM workgroups at once.  (Groups of column tiles, which keep a weight slice L2-resident instead, cut the
-  // L2 -> fabric reads by 10 - 25 % but ran 1.5 % slower end to end: DESIGN.md section 4.2, profiles/r01_gemm_tile_order.txt.)
-  const int GM = g.gm;
-  const int grp = tile / (GM * g.tiles_n);
-  const int gm = min(GM, g.tiles_m - grp * GM);
-  const int within = tile - grp * GM * g.tiles_n;
-  const int tn = within / gm, tm = grp * GM + (within - tn * gm);
+  // tile order (common.h): each XCD a contiguous run of tiles, walked in groups of GM row panels
+  int tm, tn;
+  gemm_tile_coords(xcd_contiguous(blockIdx.x, g.tiles_m * g.tiles_n), g.tiles_m, g.tiles_n, g.gm, tm, tn);
   const int m0 = tm * T::BM, n0 = tn * T::BN;
 
   int ktiles = 0;
@@ -441,7 +419,7 @@ __global__ __launch_bounds__(CFG::WM * CFG::WN * 64, 2) void gemm_kernel(GemmArg
       for (int it = 0; it < 4; ++it) {
         const int rl = fq + 4 * it;
         const float4 v = *reinterpret_cast<const float4*>(patch + rl * PITCH + frow * 4);
-        store_out4<EPI, F16 ? PREC_F16X3 : PREC_BF16X3, FULL>(gout, em0 + i * 16 + rl, en, v, side[it], bias4, g.M);
+        store_out4<EPI, F16, FULL>(gout, em0 + i * 16 + rl, en, v, side[it], bias4, g.M);
       }
 #pragma unroll
       for (int it = 0; it < 4; ++it) side[it] = side_next[it];
@@ -556,19 +534,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f8_kernel(GemmArgs g) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int tid = wave * 64 + lane;
 
-  // tile order: as gemm_kernel (XCD-contiguous runs, groups of GM row panels)
-  const int nwg = g.tiles_m * g.tiles_n;
-  const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  const int qn = nwg >> 3, rn = nwg & 7;
-  const int tile = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx;
-  const int GM = g.gm;
-  int tm, tn;
-  {
-    const int grp = tile / (GM * g.tiles_n);
-    const int gm = min(GM, g.tiles_m - grp * GM);
-    const int within = tile - grp * GM * g.tiles_n;
-    tn = within / gm; tm = grp * GM + (within - tn * gm);
-  }
+  int tm, tn;      // tile order: as gemm_kernel
+  gemm_tile_coords(xcd_contiguous(blockIdx.x, g.tiles_m * g.tiles_n), g.tiles_m, g.tiles_n, g.gm, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
   const int wr = wave / WN, wc = wave - wr * WN;
   const int r32 = lane & 31, half = lane >> 5;
@@ -601,22 +568,21 @@ __global__ __launch_bounds__(256, 2) void gemm_f8_kernel(GemmArgs g) {
     const int mb = am0 < g.M ? am0 : g.M - 1;
     const int grp0 = mb / sg.rows_out;
     const int sr0 = (mb - grp0 * sg.rows_out) * sg.row_mul + sg.row_add;
+    // (row_map_source's map spelt out a second time, for the tile's first row with its in-group row clamped to 0 instead of read as zero)
     const int64_t base_row = (int64_t)grp0 * sg.rows_in + (sr0 > 0 ? sr0 : 0);       // wave-uniform; every valid source row of the tile is >= it
 #pragma unroll
     for (int it = 0; it < IT16; ++it) {
       const int p = it * NT + tid, row = p >> 3, c = (p & 7) ^ ((row >> 1) & 7);
       int m = am0 + row; m = m < g.M ? m : g.M - 1;
-      const int grp = m / sg.rows_out, r = m - grp * sg.rows_out;
-      const int sr = r * sg.row_mul + sg.row_add;
-      a16o[it] = (sr >= 0 && sr < sg.rows_in) ? (unsigned)((((int64_t)grp * sg.rows_in + sr - base_row) * sg.lda + c * 8) * 2) : kInvalid;
+      int64_t src;
+      a16o[it] = row_map_source(m, sg.rows_out, sg.rows_in, sg.row_mul, sg.row_add, src) ? (unsigned)(((src - base_row) * sg.lda + c * 8) * 2) : kInvalid;
     }
 #pragma unroll
     for (int it = 0; it < IT8; ++it) {
       const int p = it * NT + tid, row = p >> 2, c = (p & 3) ^ ((row >> 2) & 3);
       int m = am0 + row; m = m < g.M ? m : g.M - 1;
-      const int grp = m / sg.rows_out, r = m - grp * sg.rows_out;
-      const int sr = r * sg.row_mul + sg.row_add;
-      a8o[it] = (sr >= 0 && sr < sg.rows_in) ? (unsigned)(((int64_t)grp * sg.rows_in + sr - base_row) * sg.lda + c * 16) : kInvalid;
+      int64_t src;
+      a8o[it] = row_map_source(m, sg.rows_out, sg.rows_in, sg.row_mul, sg.row_add, src) ? (unsigned)((src - base_row) * sg.lda + c * 16) : kInvalid;
     }
     a16b = (const char*)sg.a_hi + base_row * sg.lda * 2; a8b = (const char*)sg.a8 + base_row * sg.lda; al8b = (const char*)sg.al8 + base_row * sg.lda;
     const int nt0 = (an0 >> 5) + wc * TN;
@@ -808,6 +774,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f8_kernel(GemmArgs g) {
   // ---- epilogue: each wave transposes one 32-row x 64-column strip at a time through a private LDS patch (32 x 32 C/D
   // layout: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)); a lane then owns EIGHT consecutive columns of a row
   // (8 lanes per row, 8 rows per pass): 32-byte fp32 / 16-byte fp16 / 8-byte e4m3 stores, whole 256-byte row segments per plane.
+  // (Own copy of the strip loop, as in gemm_f8s_kernel and gemm_pp_kernel: one shared template spilled more in the EPI_F32_RESID kernels, profiles/r06_gemm_refactor_isa.txt.)
   static_assert(TN == 2, "epilogue strips are 64 columns wide");
   constexpr int PITCH = 72;   // floats: 288-byte rows keep the two 16-byte reads of a lane 16-byte aligned
   float* patch = reinterpret_cast<float*>(smem) + wave * (32 * PITCH);      // 9216 B per wave
@@ -874,7 +841,8 @@ template <int N> __device__ __forceinline__ void wait_vm(bf16x8& f0, bf16x8& f1,
   asm volatile("s_waitcnt vmcnt(%4)" : "+v"(f0), "+v"(f1), "+v"(f2), "+v"(f3) : "n"(N) : "memory");
 }
 
-template <int EPI, bool MULTI>
+// One plain K segment (launch_epi); the multi-segment f16f8 GEMMs stay on gemm_f8_kernel.
+template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_f8s_kernel(GemmArgs g) {
   constexpr int TM = 8, TN = 4, KS = 2;                                  // per wave: 8 x 4 tiles of 16 x 16; two 32-deep fp16 k-steps per K-tile
   constexpr int BM = 128, BN = 256, BK = 64, NT = 256;
@@ -887,24 +855,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f8s_kernel(GemmArgs g) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int tid = wave * 64 + lane;
 
-  const int nwg = g.tiles_m * g.tiles_n;
-  const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  const int qn = nwg >> 3, rn = nwg & 7;
-  const int tile = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx;
-  const int GM = g.gm;
-  int tm, tn;
-  {
-    const int grp = tile / (GM * g.tiles_n);
-    const int gm = min(GM, g.tiles_m - grp * GM);
-    const int within = tile - grp * GM * g.tiles_n;
-    tn = within / gm; tm = grp * GM + (within - tn * gm);
-  }
+  int tm, tn;      // tile order: as gemm_kernel
+  gemm_tile_coords(xcd_contiguous(blockIdx.x, g.tiles_m * g.tiles_n), g.tiles_m, g.tiles_n, g.gm, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
   const int wc = wave;
   const int r16 = lane & 15, kq = lane >> 4;
 
-  int ktiles = 0;
-  for (int s = 0; s < (MULTI ? g.nseg : 1); ++s) ktiles += g.seg[s].K / BK;
+  const int ktiles = g.seg[0].K / BK;
 
   f32x4 acc[TM][TN];
 #pragma unroll
@@ -916,30 +873,28 @@ __global__ __launch_bounds__(256, 2) void gemm_f8s_kernel(GemmArgs g) {
   const char *a16b, *a8b, *al8b;
   const char *w16b[TN], *w8b[TN];
   const unsigned wl16 = lane * 16, wl32 = lane * 32;
-  int si = 0, kk = 0, nk = 0;
-  auto open_segment = [&](int seg) {
-    si = seg; kk = 0;
-    const GemmSeg& sg = g.seg[seg];
-    nk = sg.K / BK;
+  int kk = 0;
+  // (a lambda although it is called once, in the prologue: written as a plain block hipcc schedules the address arithmetic differently and the EPI_QKV kernel
+  // takes 256 instead of 254 VGPRs)
+  auto open_streams = [&]() {
+    const GemmSeg& sg = g.seg[0];
     const int mb = m0 < g.M ? m0 : g.M - 1;
     const int grp0 = mb / sg.rows_out;
     const int sr0 = (mb - grp0 * sg.rows_out) * sg.row_mul + sg.row_add;
-    const int64_t base_row = (int64_t)grp0 * sg.rows_in + (sr0 > 0 ? sr0 : 0);
+    const int64_t base_row = (int64_t)grp0 * sg.rows_in + (sr0 > 0 ? sr0 : 0);       // as in gemm_f8_kernel: the map of row_map_source, clamped
 #pragma unroll
     for (int it = 0; it < IT16; ++it) {
       const int p = it * NT + tid, row = p >> 3, c = (p & 7) ^ ((row >> 1) & 7);
       int m = m0 + row; m = m < g.M ? m : g.M - 1;
-      const int grp = m / sg.rows_out, r = m - grp * sg.rows_out;
-      const int sr = r * sg.row_mul + sg.row_add;
-      a16o[it] = (sr >= 0 && sr < sg.rows_in) ? (unsigned)((((int64_t)grp * sg.rows_in + sr - base_row) * sg.lda + c * 8) * 2) : kInvalid;
+      int64_t src;
+      a16o[it] = row_map_source(m, sg.rows_out, sg.rows_in, sg.row_mul, sg.row_add, src) ? (unsigned)(((src - base_row) * sg.lda + c * 8) * 2) : kInvalid;
     }
 #pragma unroll
     for (int it = 0; it < IT8; ++it) {
       const int p = it * NT + tid, row = p >> 2, c = (p & 3) ^ ((row >> 3) & 1);      // the 16-row fragment reads' swizzle (below)
       int m = m0 + row; m = m < g.M ? m : g.M - 1;
-      const int grp = m / sg.rows_out, r = m - grp * sg.rows_out;
-      const int sr = r * sg.row_mul + sg.row_add;
-      a8o[it] = (sr >= 0 && sr < sg.rows_in) ? (unsigned)(((int64_t)grp * sg.rows_in + sr - base_row) * sg.lda + c * 16) : kInvalid;
+      int64_t src;
+      a8o[it] = row_map_source(m, sg.rows_out, sg.rows_in, sg.row_mul, sg.row_add, src) ? (unsigned)((src - base_row) * sg.lda + c * 16) : kInvalid;
     }
     a16b = (const char*)sg.a_hi + base_row * sg.lda * 2; a8b = (const char*)sg.a8 + base_row * sg.lda; al8b = (const char*)sg.al8 + base_row * sg.lda;
     const int nt0 = (n0 >> 4) + wc * TN;
@@ -951,14 +906,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f8s_kernel(GemmArgs g) {
       w8b[j] = (const char*)sg.ws8 + (nt0 + j) * w8_ts + (int64_t)(sg.w_k0 / 2) * 2048;
     }
   };
+  // point the streams at the next K-tile (the last K-tile points at itself again)
   auto advance = [&]() {
-    if (kk + 1 < nk) {
+    if (kk + 1 < ktiles) {
       ++kk;
       a16b += BK * 2; a8b += BK; al8b += BK;
 #pragma unroll
       for (int j = 0; j < TN; ++j) { w16b[j] += KS * 1024; w8b[j] += 2048; }
-    } else if (MULTI && si + 1 < g.nseg) {
-      open_segment(si + 1);
     }
   };
   auto dma = [&](auto op_t, char* stage) {
@@ -988,7 +942,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f8s_kernel(GemmArgs g) {
     for (int j = 0; j < TN; ++j) { w8[j][0] = gload16<0>(wl32, w8b[j]); w8[j][1] = gload16<16>(wl32, w8b[j]); }
   };
 
-  open_segment(0);
+  open_streams();
   [&]<int... O>(std::integer_sequence<int, O...>) { (dma(std::integral_constant<int, O>{}, smem), ...); }(std::make_integer_sequence<int, NDMA>{});
   load_w16(std::integral_constant<int, 0>{}); load_w16(std::integral_constant<int, 1>{});
   load_w8();
@@ -1012,33 +966,35 @@ __global__ __launch_bounds__(256, 2) void gemm_f8s_kernel(GemmArgs g) {
     constexpr bool PF = decltype(pf_t)::value;
     char* nxt = smem + ((kt + 1) & 1) * STAGE;
     if constexpr (PF) advance();
-    // ---- fp16 part: KS x TM steps of TN MFMAs (64 matrix-pipe cycles), fragments read AD steps ahead into a ring
-    constexpr int AD = MULTI ? 1 : 3;
+    // ---- fp16 part: KS x TM steps of TN MFMAs (64 matrix-pipe cycles), fragments read AD = 3 steps ahead into a four-entry ring (gemm_f8_kernel: an LDS
+    // read under load takes longer than one step to return)
+    constexpr int AD = 3;
     bf16x8 af[AD + 1];
     auto read_a16 = [&](auto s_t) {
       constexpr int S2 = decltype(s_t)::value;
       af[S2 % (AD + 1)] = lds_read16<(S2 % TM) * 16 * 128>(a16a[S2 / TM]);
     };
     [&]<int... S>(std::integer_sequence<int, S...>) { (read_a16(std::integral_constant<int, S>{}), ...); }(std::make_integer_sequence<int, AD>{});
-    // e4m3 operand of row tile i (two 16-byte reads): row tile i + 1 is read into the other buffer before the MFMAs of row tile i
+    // e4m3 operand of row tile i (two 16-byte reads): row tile i + 1 is read into the other buffer before the MFMAs of row tile i; the first row tile's
+    // reads go out behind the last fp16 step
     bf16x8 ax[2], ay[2];
     auto read_8 = [&](auto i_t) {
       constexpr int I = decltype(i_t)::value, O = I * 16 * 64;
       if constexpr (I & 1) { ay[0] = lds_read16<O>(a8a[0]); ay[1] = lds_read16<O>(a8a[1]); }
       else { ax[0] = lds_read16<O>(a8a[0]); ax[1] = lds_read16<O>(a8a[1]); }
     };
-    constexpr bool EARLY8 = !MULTI;
     [&]<int... S>(std::integer_sequence<int, S...>) {
       ([&] {
         constexpr int ks = S / TM, i = S % TM;
         if constexpr (S + AD < KS * TM) read_a16(std::integral_constant<int, S + AD>{});
-        if constexpr (EARLY8 && S == KS * TM - 1) read_8(std::integral_constant<int, 0>{});
+        if constexpr (S == KS * TM - 1) read_8(std::integral_constant<int, 0>{});
         if constexpr (PF && ks == 0) {
           [&]<int... O>(std::integer_sequence<int, O...>) {
             ([&] { constexpr int op = i * DMA_PER_STEP + O; if constexpr (op < NDMA) dma(std::integral_constant<int, op>{}, nxt); }(), ...);
           }(std::make_integer_sequence<int, DMA_PER_STEP>{});
         }
-        constexpr int AHEAD = (KS * TM - 1 - S < AD ? KS * TM - 1 - S : AD) + (EARLY8 && S >= KS * TM - 1 ? 2 : 0);
+        // LDS operations younger than this step's fragment: the (up to) three fragments read ahead, plus the first e4m3 reads
+        constexpr int AHEAD = (KS * TM - 1 - S < AD ? KS * TM - 1 - S : AD) + (S >= KS * TM - 1 ? 2 : 0);
         lgkm_wait<AHEAD>(af[S % (AD + 1)]);
         if constexpr (i == 0) wait_vm<ORD::template w16_wait<PF>(ks)>(w16[ks][0], w16[ks][1], w16[ks][2], w16[ks][3]);
         __builtin_amdgcn_sched_barrier(0);
@@ -1050,7 +1006,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f8s_kernel(GemmArgs g) {
     }(std::make_integer_sequence<int, KS * TM>{});
     // ---- e4m3 part
     wait_vm8<ORD::template w8_wait<PF>()>(w8[0][0], w8[0][1], w8[1][0], w8[1][1], w8[2][0], w8[2][1], w8[3][0], w8[3][1]);
-    if constexpr (!EARLY8) read_8(std::integral_constant<int, 0>{});
     [&]<int... I>(std::integer_sequence<int, I...>) {
       ([&] {
         if constexpr (I + 1 < TM) read_8(std::integral_constant<int, I + 1>{});
@@ -1143,7 +1098,7 @@ int g_mfma16 = 1;   // tuning knob "gemm_mfma16": 1 = the 16 x 16 form wherever 
 // 128 x 256 tiles; with N % 256 != 0 the last column tile's weight rows exist (zero or unread garbage) and are multiplied, its stores are masked
 template <int EPI>
 int launch_f8s(GemmArgs a, hipStream_t s) {
-  return launch_tiles<gemm_f8s_kernel<EPI, false>>(a, 128, 256, 256, 2 * (128 * 64 * 2 + 2 * 128 * 64), s);
+  return launch_tiles<gemm_f8s_kernel<EPI>>(a, 128, 256, 256, 2 * (128 * 64 * 2 + 2 * 128 * 64), s);
 }
 
 template <int EPI, class CFG>
@@ -1169,7 +1124,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(pp::Args g, GemmOut out
   float* patch = reinterpret_cast<float*>(smem + pp::PATCH_BASE + wave * 8192);
   const int c8 = (lane & 7) * 8, r8 = lane >> 3;
   constexpr bool SIDE = EPI == EPI_F32_RESID;
-  pp::kloop<pp::FMT_F16F8S>(g, smem, [&](int tm, int tn, pp::Acc<pp::FMT_F16F8S>& accs) {
+  pp::kloop(g, smem, [&](int tm, int tn, pp::Acc& accs) {
     auto& acc = accs.t;
     const int m0 = tm * pp::BM, n0 = tn * pp::BN;
     const int em0 = m0 + wr * 128, en = n0 + wc * 64 + c8;
@@ -1227,16 +1182,21 @@ int launch_pp(const pp::Args& a, const GemmOut& o, int grid, hipStream_t s) {
 
 int g_force_tile = 0;  // 0 = auto, 64 / 128 / 256 = forced (tuning and tests)
 
-template <int TERMS, int BK, int EPI, class CFG, bool F16 = false, bool WX = false>
-int launch_one(GemmArgs a, hipStream_t s) {
+// BATCH (launch_gemm_batched): `batch` independent matrices of one shape, blockIdx.y = matrix
+template <int TERMS, int BK, int EPI, class CFG, bool F16, bool WX, bool BATCH>
+int launch_one(GemmArgs a, hipStream_t s, int batch) {
   using T = Tile<TERMS, BK, CFG, WX>;
-  return launch_tiles<gemm_kernel<TERMS, BK, EPI, CFG, F16, WX>>(a, T::BM, T::BN, T::THREADS, T::LDS_BYTES, s);
+  return launch_tiles<gemm_kernel<TERMS, BK, EPI, CFG, F16, WX, BATCH>>(a, T::BM, T::BN, T::THREADS, T::LDS_BYTES, s, batch);
 }
-// batched launch (launch_gemm_batched): `batch` independent matrices of one shape, blockIdx.y = matrix
-template <int TERMS, int BK, int EPI, class CFG>
-int launch_batched_one(GemmArgs a, int batch, hipStream_t s) {
-  using T = Tile<TERMS, BK, CFG, false>;
-  return launch_tiles<gemm_kernel<TERMS, BK, EPI, CFG, false, false, true>>(a, T::BM, T::BN, T::THREADS, T::LDS_BYTES, s, batch);
+// The gemm_kernel of a block tile (256: 128 x 256 on CfgW4, 128: 128 x 128, 64: 64 x 128).  K-tile depth: 64 for a single product; for the split product 32,
+// except on the 64-row tile -- few tiles per CU: the K loop is latency-bound (one barrier + one global round trip per K-tile), so the deeper
+// K-tile is used for the split product as well (its 64 + 64 weight-fragment registers fit next to 32 accumulators).
+template <int TERMS, int EPI, bool F16, bool WX = false, bool BATCH = false>
+int launch_tile(int tile, GemmArgs a, hipStream_t s, int batch = 1) {
+  constexpr int BK = TERMS == 1 ? 64 : 32;
+  if (tile == 256) return launch_one<TERMS, BK, EPI, CfgW4, F16, WX, BATCH>(a, s, batch);
+  if (tile == 128) return launch_one<TERMS, BK, EPI, Cfg128, F16, WX, BATCH>(a, s, batch);
+  return launch_one<TERMS, 64, EPI, Cfg64, F16, WX, BATCH>(a, s, batch);
 }
 
 // Tile choice by tile count: a launch should put at least one tile on each of the 512 workgroup slots (256 CUs x 2) --
@@ -1272,27 +1232,11 @@ int launch_epi(GemmArgs a, int prec, hipStream_t s) {
     return launch_f8<EPI, CfgF8Sq>(a, s);
   }
   const int tile = pick_tile(Mp, a.N);
-  if (prec == PREC_F16X3) {      // fp16 hi / lo planes on the same kernels
-    if (a.nseg == 1 && a.seg[0].w_exact16) {     // fp16-exact weights: two products per fragment pair
-      if (tile == 256) return launch_one<3, 32, EPI, CfgW4, true, true>(a, s);
-      if (tile == 128) return launch_one<3, 32, EPI, Cfg128, true, true>(a, s);
-      return launch_one<3, 64, EPI, Cfg64, true, true>(a, s);
-    }
-    if (tile == 256) return launch_one<3, 32, EPI, CfgW4, true>(a, s);
-    if (tile == 128) return launch_one<3, 32, EPI, Cfg128, true>(a, s);
-    return launch_one<3, 64, EPI, Cfg64, true>(a, s);
+  if (prec == PREC_F16X3) {      // fp16 hi / lo planes on the same kernels; fp16-exact weights: two products per fragment pair
+    return (a.nseg == 1 && a.seg[0].w_exact16) ? launch_tile<3, EPI, true, true>(tile, a, s) : launch_tile<3, EPI, true>(tile, a, s);
   }
-  if (prec == PREC_F16) {        // one fp16 product (measurement mode): the single-product kernels on fp16 planes
-    if (tile == 256) return launch_one<1, 64, EPI, CfgW4, true>(a, s);
-    if (tile == 128) return launch_one<1, 64, EPI, Cfg128, true>(a, s);
-    return launch_one<1, 64, EPI, Cfg64, true>(a, s);
-  }
-  const int terms = prec_products(prec);
-  if (tile == 256) return terms == 3 ? launch_one<3, 32, EPI, CfgW4>(a, s) : launch_one<1, 64, EPI, CfgW4>(a, s);
-  if (tile == 128) return terms == 3 ? launch_one<3, 32, EPI, Cfg128>(a, s) : launch_one<1, 64, EPI, Cfg128>(a, s);
-  // few tiles per CU: the K loop is latency-bound (one barrier + one global round trip per K-tile), so the deeper 64-wide
-  // K-tile is used for the split product as well (its 64 + 64 weight-fragment registers fit next to 32 accumulators)
-  return terms == 3 ? launch_one<3, 64, EPI, Cfg64>(a, s) : launch_one<1, 64, EPI, Cfg64>(a, s);
+  if (prec == PREC_F16) return launch_tile<1, EPI, true>(tile, a, s);        // one fp16 product (measurement mode): the single-product kernels on fp16 planes
+  return prec_products(prec) == 3 ? launch_tile<3, EPI, false>(tile, a, s) : launch_tile<1, EPI, false>(tile, a, s);
 }
 
 
@@ -1301,9 +1245,7 @@ int launch_batched_epi(GemmArgs a, int batch, hipStream_t s) {
   // tile by the rows a matrix wastes: 64-row tiles when the last 128-row tile would be at most half full, else by tile count
   const int tail = a.M % 128;
   const int tile = (!g_force_tile && tail > 0 && tail <= 64 && a.M < 1024) ? 64 : pick_tile(a.M, a.N, batch);
-  if (tile == 256) return launch_batched_one<3, 32, EPI, CfgW4>(a, batch, s);
-  if (tile == 128) return launch_batched_one<3, 32, EPI, Cfg128>(a, batch, s);
-  return launch_batched_one<3, 64, EPI, Cfg64>(a, batch, s);
+  return launch_tile<3, EPI, false, false, true>(tile, a, s, batch);
 }
 
 }  // namespace

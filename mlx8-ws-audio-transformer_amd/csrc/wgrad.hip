@@ -34,7 +34,7 @@ struct WgradArgs {
   const bf16_t *y_hi, *y_lo; int64_t ldy; int ycol, N;
   const bf16_t *x_hi, *x_lo; int64_t ldx; int xcol, K;
   int M, slab_rows;
-  int rows_out, rows_in, row_mul, row_add;        // X row of contraction row m: (m / rows_out) * rows_in + (m % rows_out) * row_mul + row_add; outside [0, rows_in): zero
+  int rows_out, rows_in, row_mul, row_add;        // X row of contraction row m (common.h row_map_source; outside [0, rows_in): zero)
   float* partial;                                 // [slabs][N][K]
 };
 
@@ -56,10 +56,10 @@ __device__ __forceinline__ void load_row(const WgradArgs& g, int m, int m_end, b
   yh = z;
   if (yok) yh = *reinterpret_cast<const uint4*>(g.y_hi + yo);
   if constexpr (NP == 2) { yl = z; if (yok) yl = *reinterpret_cast<const uint4*>(g.y_lo + yo); }
-  const int grp = m / g.rows_out, r = m - grp * g.rows_out;
-  const int sr = r * g.row_mul + g.row_add;
-  const bool xok = mok && xcol_ok && sr >= 0 && sr < g.rows_in;
-  const int64_t xo = ((int64_t)grp * g.rows_in + sr) * g.ldx + xcoff;
+  int64_t xrow;
+  const bool xin = row_map_source(m, g.rows_out, g.rows_in, g.row_mul, g.row_add, xrow);
+  const bool xok = mok && xcol_ok && xin;
+  const int64_t xo = xrow * g.ldx + xcoff;
   xh = z;
   if (xok) xh = *reinterpret_cast<const uint4*>(g.x_hi + xo);
   if constexpr (NP == 2) { xl = z; if (xok) xl = *reinterpret_cast<const uint4*>(g.x_lo + xo); }

@@ -32,7 +32,7 @@ for tag in tags:
     out[tag.split(rnd + "_", 1)[-1]] = dict(sorted(res.items(), key=lambda kv: -kv[1]["avg_us"] * kv[1]["launches"]))
 json.dump({"note": "per kernel NAME (not class) from the SQ / GRBM pass of tools/profile_round.sh (gpurun_out/<tag>/pmc_MFMA); mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x "
                    "GRBM_GUI_ACTIVE / 8), effective clock = GRBM_GUI_ACTIVE / 8 XCDs / kernel duration; profiled passes run 2-3 % slower than un-profiled ones.  fp32 weights: "
-                   "gemm_pp_kernel<3, true> = fc1 (GELU, split-line output), <1, false> = fc2 (fp32 + residual); gemm_f8s_kernel<4, false> = QKV, <1, false> = out_proj, <3, false> = conv1; "
+                   "gemm_pp_kernel<3, true> = fc1 (GELU, split-line output), <1, false> = fc2 (fp32 + residual); gemm_f8s_kernel<4> = QKV, <1> = out_proj, <3> = conv1 (profiles up to round 5: gemm_f8s_kernel<4, false> ...); "
                    "gemm_f8_kernel<5, CfgF8W4, true, false> = conv2 (three K segments, 32 x 32 form).  fp16 = fp16-exact weights: the one-cross-term 32 x 32 kernels (gemm_f8_kernel<EPI, CfgF8W4, false, true>)",
            "per_kernel": out}, open(os.path.join(ROOT, "profiles", "%s_mfma_by_kernel.json" % rnd), "w"), indent=1)
 for tag, res in out.items():
