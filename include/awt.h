@@ -281,6 +281,9 @@ size_t awt_op_attention_workspace_bytes(int B, int H, int S);
  * weights: the linears are weight-bound GEMMs on the encoder's MFMA kernel over weights packed once (`awt_weight`); attention is
  * an fp32 row kernel (causal self-attention, cross-attention over the 1500 encoder positions) that reads q / k / v in place from
  * the row-major outputs of the linears.  All float32 in / out, row-major, caller-owned device memory, deterministic.
+ * The weights are frozen by default; with NativeWhisperDecoder(train_base=True) every decoder parameter trains: the weight gradients are
+ * awt_op_weight_grad products on the operands the backward already holds, the biases awt_op_column_sums_ld, the LayerNorm affines
+ * awt_op_layernorm_param_grad, the tied embedding awt_op_embed_backward, and awt_weight_update re-packs a stepped weight into its handle.
  */
 typedef struct awt_weight awt_weight;
 /* Packs a frozen nn.Linear weight [N, K] (+ bias [N] or NULL) once: N is zero-padded to a multiple of 128 (awt_weight_padded_rows),
@@ -290,6 +293,11 @@ int awt_weight_create(awt_ctx* c, const float* w, const float* bias, int N, int 
                       awt_weight** out);
 void awt_weight_destroy(awt_weight* w);
 int awt_weight_padded_rows(const awt_weight* w);
+/* A TRAINED weight (NativeWhisperDecoder train_base, after an optimizer step): packs the changed [N, K] values (and bias [N]; given iff the handle
+ * was created with one) into the planes the handle already owns, the transposed copy included.  In place, no allocation; the planes come out
+ * bit-identical to those awt_weight_create would build from the same data.  w must have the handle's N x K elements (the caller checks: the
+ * handle cannot see a tensor's shape). */
+int awt_weight_update(awt_ctx* c, awt_weight* w, const float* weight, const float* bias, void* stream);
 size_t awt_linear_workspace_bytes(const awt_weight* w, int M, int backward);   /* backward != 0: for awt_linear_backward_input */
 /* y [M, Np] = x [M, K] W^T + bias (+ resid [M, Np], may alias y)      F.linear / the residual adds of HF:modeling_whisper.py:468-500 */
 int awt_linear_forward(awt_ctx* c, const awt_weight* w, const float* x, const float* resid, float* y, int M, void* workspace,
@@ -337,6 +345,18 @@ size_t awt_op_param_grad_workspace_bytes(int M, int d);
 int awt_op_layernorm_param_grad(awt_ctx* c, const float* dy, const float* x, float* dgamma, float* dbeta, int M, int d, float eps,
                                 void* workspace, size_t ws_bytes, void* stream);
 int awt_op_column_sums(awt_ctx* c, const float* a, float* sums, int M, int d, void* workspace, size_t ws_bytes, void* stream);
+/* Pitched form, any width: sums[c] (+)= sum_{m < M} a[m * ld + col + c], c < width (accumulate != 0 adds to sums).  width, col, ld multiples of 4,
+ * 16-byte aligned tensors.  The decoder's bias gradients: fc1's 4 d columns, the q / v blocks of the fused [M, 3 d] gradient, the value blocks of
+ * the [B S, 2 layers d] cross-attention buffer.  Deterministic: slabs of 256 rows summed top to bottom, then added in slab order. */
+size_t awt_op_column_sums_ld_workspace_bytes(int M, int width);
+int awt_op_column_sums_ld(awt_ctx* c, const float* a, int64_t ld, int col, int width, float* sums, int M, int accumulate, void* workspace,
+                          size_t ws_bytes, void* stream);
+/* Backward of awt_op_embed, ADDED to the two tables' gradients (the tied projection's gradient is already in dtok when this runs):
+ *   dtok[v, :] += sum over {m : clamp(ids[m]) = v} of dx[m, :]        dpos[pos0 + l, :] += sum_b dx[b L + l, :]
+ * ids are clamped as awt_op_embed clamps them.  No atomics: one workgroup owns a table row (the first row m naming it) and adds its terms in
+ * ascending m, so two runs give the same bits; rows of dtok that no id names are not touched.  M a multiple of L, d a multiple of 4, d <= 2048. */
+int awt_op_embed_backward(awt_ctx* c, const int64_t* ids, const float* dx, float* dtok, float* dpos, int M, int L, int d, int pos0, int vocab,
+                          void* stream);
 /* The weight-gradient GEMM of the full-parameter backward as an operator (csrc/wgrad.hip):
  *   out[n * sn + k * sk] (+)= scale * sum_{m < M} dy[m, ycol + n] * x[row(m), xcol + k]      n < N, k < K
  * dy fp32 [M, ldy], x fp32 [rows_x, ldx]; both are split into bf16 hi / lo planes inside; terms = 1 (one bf16 product) or 3 (split-bf16).

@@ -87,6 +87,10 @@ _SIGNATURES = {
     "awt_weight_create": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, C.POINTER(_vp)]),
     "awt_weight_destroy": (None, [_vp]),
     "awt_weight_padded_rows": (_i, [_vp]),
+    "awt_weight_update": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "awt_op_column_sums_ld_workspace_bytes": (_sz, [_i, _i]),
+    "awt_op_column_sums_ld": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _i, _vp, _sz, _vp]),
+    "awt_op_embed_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "awt_linear_workspace_bytes": (_sz, [_vp, _i, _i]),
     "awt_linear_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "awt_linear_backward_input": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),

@@ -69,6 +69,18 @@ extern "C" int awt_weight_create(awt_ctx* c, const float* w, const float* bias, 
 }
 extern "C" int awt_weight_padded_rows(const awt_weight* w) { return w ? w->Np : 0; }
 
+// A trained weight's new values into the planes the handle already owns.  The pack kernels write exactly the N x K region (the padding rows were
+// zeroed at creation and are never written), so the planes end up bit-identical to those of a handle created from the same data.
+extern "C" int awt_weight_update(awt_ctx* c, awt_weight* h, const float* w, const float* bias, void* stream) {
+  AWT_REQUIRE(c && h && w, AWT_ERR_INVALID, "weight_update: null argument");
+  AWT_REQUIRE((bias != nullptr) == (h->bias != nullptr), AWT_ERR_INVALID, "weight_update: the handle was created with a bias iff one must be given");
+  hipStream_t s = (hipStream_t)stream;
+  int rc = launch_pack_weight(c, w, h->N, h->K, 1, h->K, 0, 0, 1.0f, h->hi, h->lo, nullptr, h->prec, s);
+  if (!rc && h->t_hi) rc = launch_pack_weight_t(c, w, h->N, h->K, h->Np, 0, 0, 1.0f, h->t_hi, h->t_lo, s);
+  if (!rc && bias && hipMemcpyAsync(h->bias, bias, (size_t)h->N * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = awt_fail(AWT_ERR_HIP, "weight_update: bias copy failed");
+  return rc;
+}
+
 extern "C" size_t awt_linear_workspace_bytes(const awt_weight* w, int M, int backward) {
   if (!w || M <= 0) return 0;
   return 2 * align_up((size_t)M * (backward ? w->Np : w->K) * 2);     // the hi / lo planes of x [M, K] or of dy [M, Np]

@@ -158,13 +158,20 @@ class WhisperLoRAModel(nn.Module):
                  seed: int = 0, vocab: int = WHISPER_VOCAB, decoder_autocast: Optional[torch.dtype] = None, native_cross_kv: bool = True,
                  max_target_positions: int = 448, backward_precision: Optional[str] = None, native_decoder: bool = True,
                  decoder_heads: Optional[int] = None, decoder_ffn: Optional[int] = None, decoder_lora: Optional[LoraSpec] = None,
-                 train_encoder: bool = False):
+                 train_encoder: bool = False, train_decoder: bool = False):
         super().__init__()
         # train_encoder: full-parameter fine-tuning of the encoder, as the reference's fineTune.py trains it (every encoder parameter but the
         # sinusoid table; encoder.NativeWhisperEncoder train_base=True) -- no encoder adapters then; the decoder stays frozen or takes decoder_lora
         if train_encoder and lora is not None:
             raise ValueError("train_encoder=True trains the encoder's base weights: pass lora=None (decoder_lora is still available)")
         self.train_encoder = train_encoder
+        # train_decoder: full-parameter fine-tuning of the decoder as well -- every decoder parameter, the tied token table and the learned position
+        # table included (native_decoder.NativeWhisperDecoder train_base=True).  With train_encoder=True this is the reference's
+        # parameter set; it also combines with encoder adapters (lora=) or a frozen encoder.  native_decoder=False leaves the stock torch
+        # decoder's parameters trainable: the A/B reference through the same constructor
+        if train_decoder and decoder_lora is not None:
+            raise ValueError("train_decoder=True trains the decoder's base weights: pass decoder_lora=None (lora= on the encoder is still available)")
+        self.train_decoder = train_decoder
         # decoder_lora: adapters on the decoder's self- / cross-attention q_proj, v_proj as well (scope row f1: "+ LoRA on decoder"; the
         # reference fine-tunes every decoder parameter, AB/fineTune.py:131,186-199) -- native decoder only
         if decoder_lora is not None and (not native_decoder or decoder_autocast is not None):
@@ -191,11 +198,12 @@ class WhisperLoRAModel(nn.Module):
         if native_decoder:
             from .native_decoder import NativeWhisperDecoder
             nd = NativeWhisperDecoder(cfg.d_model, decoder_layers or cfg.layers, dheads, dffn, vocab, max_target_positions,
-                                      precision=precision if precision in ("bf16", "bf16x3") else "bf16x3", lora=decoder_lora, lora_seed=seed).to(device)
+                                      precision=precision if precision in ("bf16", "bf16x3") else "bf16x3", lora=decoder_lora, lora_seed=seed,
+                                      train_base=train_decoder).to(device)
             nd.load_state_dict(self.decoder.state_dict(), strict=decoder_lora is None)       # the same initial weights as the torch decoder of this seed
             self.decoder = nd
         for n, p in self.decoder.named_parameters():
-            p.requires_grad = "lora_" in n      # frozen base model: only the adapters train
+            p.requires_grad = train_decoder or "lora_" in n      # frozen base model: only the adapters train (train_decoder: every parameter)
         self.config = SimpleNamespace(decoder_start_token_id=DECODER_START, pad_token_id=PAD_ID, eos_token_id=EOS_ID, d_model=cfg.d_model,
                                       median_filter_width=7)
         self.max_target_positions = max_target_positions
@@ -209,8 +217,9 @@ class WhisperLoRAModel(nn.Module):
 
     def trainable_parameters(self) -> List[nn.Parameter]:
         """What the optimizer updates: the encoder's trainable parameters (its adapters, or with train_encoder every base parameter but the
-        position table), then the decoder's adapters (if any)."""
-        return [p for p in self.encoder.parameters() if p.requires_grad] + [p for n, p in self.decoder.named_parameters() if "lora_" in n]
+        position table), then the decoder's: its adapters (if any), or with train_decoder every base parameter."""
+        return [p for p in self.encoder.parameters() if p.requires_grad] + \
+            [p for n, p in self.decoder.named_parameters() if self.train_decoder or "lora_" in n]
 
     @classmethod
     def from_pretrained(cls, path, lora: Optional[LoraSpec] = None, precision: Optional[str] = None, device: str = "cuda", **kw) -> "WhisperLoRAModel":
@@ -222,7 +231,7 @@ class WhisperLoRAModel(nn.Module):
         from .checkpoint import encoder_config_from_hf, load_checkpoint_dir
         hf, enc_sd, dec_sd = load_checkpoint_dir(path)
         cfg = encoder_config_from_hf(hf, os.path.basename(os.path.normpath(os.fspath(path))))
-        if precision is None and (lora is not None or kw.get("train_encoder")):
+        if precision is None and (lora is not None or kw.get("train_encoder") or kw.get("train_decoder")):
             precision = "bf16x3"
         model = cls(cfg, lora, precision=precision, device=device, decoder_layers=int(hf.get("decoder_layers", cfg.layers)),
                     vocab=int(hf.get("vocab_size", WHISPER_VOCAB)), max_target_positions=int(hf.get("max_target_positions", 448)),
@@ -235,7 +244,7 @@ class WhisperLoRAModel(nn.Module):
         if [k for k in missing if "lora_" not in k] or unexpected:
             raise KeyError(f"{path}: decoder state dict mismatch: missing {[k for k in missing if 'lora_' not in k][:4]}, unexpected {list(unexpected)[:4]}")
         for n, p in model.decoder.named_parameters():
-            p.requires_grad = "lora_" in n
+            p.requires_grad = model.train_decoder or "lora_" in n
         for key, attr in (("decoder_start_token_id", "decoder_start_token_id"), ("pad_token_id", "pad_token_id"), ("eos_token_id", "eos_token_id")):
             if hf.get(key) is not None:
                 setattr(model.config, attr, int(hf[key]))
@@ -740,8 +749,9 @@ class Seq2SeqTrainer:
                 if better:
                     best = score
                     full_enc = getattr(self.model, "train_encoder", False)       # full-parameter mode: the trained state is the encoder itself
+                    full_dec = getattr(self.model, "train_decoder", False)       # ... and the decoder's base weights
                     best_state = ({k: v.detach().clone() for k, v in self.model.encoder.state_dict().items() if full_enc or "lora_" in k},
-                                  {k: v.detach().clone() for k, v in self.model.decoder.state_dict().items() if "lora_" in k})
+                                  {k: v.detach().clone() for k, v in self.model.decoder.state_dict().items() if full_dec or "lora_" in k})
             if self.args.save_steps and self.global_step % self.args.save_steps == 0:
                 self.save_model()
         if self.args.load_best_model_at_end and best_state is not None:      # fineTune.py:178-180
@@ -758,6 +768,15 @@ class Seq2SeqTrainer:
         adapters merged into the base) that `WhisperLoRAModel.from_pretrained` -- and the reference's wavToWhisper.py:47 -- load by path."""
         out = output_dir or self.args.output_dir
         os.makedirs(out, exist_ok=True)
+        if getattr(self.model, "train_decoder", False) and not getattr(self.model, "train_encoder", False):
+            # trained decoder under encoder adapters or a frozen encoder: the directory holds the decoder's new base weights, with the encoder
+            # adapters MERGED (as save_pretrained does), so it is the whole trained model and the one to resume from:
+            # `from_pretrained(out, train_decoder=True)` WITHOUT `lora=` (loading lora_adapters.pt on top of it would apply the adapters twice).
+            # lora_adapters.pt, still written below, holds the adapters alone, for the encoder's ORIGINAL base weights.
+            self.model.save_pretrained(out)
+            if self.model.encoder.lora is None:
+                return out
+            full = False                                         # the directory is written
         if getattr(self.model, "train_encoder", False):
             # full-parameter mode: the base weights themselves changed, so the checkpoint is the whole directory (what the reference's
             # trainer.save_model() writes); there is no adapter-only file to claim, except the decoder's adapters if it has any

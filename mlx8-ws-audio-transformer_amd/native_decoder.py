@@ -28,6 +28,10 @@ trainable `lora_A` [r, d] / `lora_B` [d, r] (B = 0 at init).  The base stays fro
 small GEMMs on the same MFMA kernel (`awt_op_linear`): du = dy B, dA = (alpha / r) du^T x, dB = (alpha / r) dy^T u, dx += (alpha / r) du A.
 The cross-attention VALUE adapters act on the encoder states (B x 1500 rows): all layers' u = enc A^T come from one GEMM, and their share
 of d(loss) / d(encoder states) from one more.
+
+Full-parameter fine-tuning (`train_base=True`): every base parameter requires grad, the backward also forms their gradients
+(weight-gradient GEMM, pitched column sums, LayerNorm parameter gradients, `awt_op_embed_backward` for the tied table and the positions), and
+`packed()` re-packs the stepped weights into the handles it already has (`awt_weight_update`).
 """
 from __future__ import annotations
 
@@ -79,6 +83,19 @@ class PackedLinear:
             _lib.check(L.awt_linear_backward_input(_lib.ctx(dy.device), self.handle, _lib.ptr(dy), _lib.ptr(dx), M, _lib.ptr(ws), ws.numel(),
                                                    _lib.stream_handle()))
         return dx
+
+    def update(self, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> None:
+        """Re-packs a changed weight (and bias) into this handle's planes, in place (`awt_weight_update`): what a trained decoder does after
+        an optimizer step instead of building a new handle."""
+        w = weight.detach().float().contiguous()
+        b = None if bias is None else bias.detach().float().contiguous()
+        if tuple(w.shape) != (self.N, self.K) or (b is not None and tuple(b.shape) != (self.N,)):
+            raise ValueError(f"PackedLinear.update: the handle holds a [{self.N}, {self.K}] weight, got {tuple(w.shape)}"
+                             + ("" if b is None else f" with bias {tuple(b.shape)}"))
+        if w.device != self.device:
+            raise ValueError(f"PackedLinear.update: the handle lives on {self.device}, the weight on {w.device}")
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().awt_weight_update(_lib.ctx(self.device), self.handle, _lib.ptr(w), _lib.ptr(b), _lib.stream_handle()))
 
     def __del__(self):
         try:
@@ -174,6 +191,50 @@ def embed(ids: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, position_offs
     return x
 
 
+def embed_backward(ids: torch.Tensor, dx: torch.Tensor, dtok: torch.Tensor, dpos: torch.Tensor, position_offset: int = 0) -> None:
+    """Adds the backward of `embed` to the two tables' gradients: dtok[clamp(ids[m])] += dx[m], dpos[position_offset + column] += dx[m]
+    (awt_op_embed_backward: no atomics, every table row's terms added in ascending m)."""
+    B, L = ids.shape
+    vocab, d = dtok.shape
+    ids = ids.to(device=dx.device, dtype=torch.int64).contiguous()
+    if dx.shape != (B * L, d) or dpos.shape[1] != d or dpos.shape[0] < position_offset + L:
+        raise ValueError("embed_backward: dx must be [B * L, d] and dpos must hold position_offset + L rows of d")
+    with torch.cuda.device(dx.device):
+        _lib.check(_lib.lib().awt_op_embed_backward(_ctx(dx), _lib.ptr(ids), _lib.ptr(dx), _lib.ptr(dtok), _lib.ptr(dpos), B * L, L, d, int(position_offset),
+                                                    vocab, _lib.stream_handle()))
+
+
+def column_sums_ld(a: torch.Tensor, col: int = 0, width: Optional[int] = None, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """sums[c] (+)= sum_m a[m, col + c] for c < width over a row-major [M, ld] matrix (awt_op_column_sums_ld; bias gradients)."""
+    M, ld = a.shape
+    width = ld - col if width is None else width
+    if out is None:
+        if accumulate:
+            raise ValueError("column_sums_ld: accumulate needs out")
+        out = torch.empty(width, dtype=torch.float32, device=a.device)
+    if out.shape != (width,):
+        raise ValueError(f"column_sums_ld: out must hold {width} elements")
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_op_column_sums_ld_workspace_bytes(M, width), a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(L.awt_op_column_sums_ld(_ctx(a), _lib.ptr(a), ld, int(col), int(width), _lib.ptr(out), M, int(accumulate), _lib.ptr(ws), ws.numel(),
+                                           _lib.stream_handle()))
+    return out
+
+
+def layernorm_param_grad(dy: torch.Tensor, x: torch.Tensor, eps: float = 1e-5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(dgamma, dbeta) of y = LayerNorm(x) gamma + beta for the gradient dy (awt_op_layernorm_param_grad)."""
+    M, d = x.shape
+    dg = torch.empty(d, dtype=torch.float32, device=x.device)
+    db = torch.empty_like(dg)
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_op_param_grad_workspace_bytes(M, d), x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(L.awt_op_layernorm_param_grad(_ctx(x), _lib.ptr(dy), _lib.ptr(x), _lib.ptr(dg), _lib.ptr(db), M, d, eps, _lib.ptr(ws), ws.numel(),
+                                                 _lib.stream_handle()))
+    return dg, db
+
+
 def gemm(x: torch.Tensor, w: torch.Tensor, precision: str = "bf16x3") -> torch.Tensor:
     """x [M, K] @ w [N, K]^T on libawt's MFMA GEMM (`awt_op_linear`): K zero-padded to a multiple of 64, N to a multiple of 128."""
     from . import ops
@@ -211,6 +272,15 @@ class PackedBatch:
                 p2 = None if second is None else second[0].data_ptr() + 4 * second[1]
                 _lib.check(L.awt_bmm_pack_kmajor(_lib.ctx(dev), t1.data_ptr() + 4 * o1, p2, K1, ld, stride, self.batch, self.N, self.K, _lib.ptr(self.buf),
                                                  self.buf.numel(), _lib.stream_handle()))
+
+    def update(self, b: torch.Tensor) -> None:
+        """Packs changed operands of the same [batch, N, K] shape into the existing buffer (`awt_bmm_pack` again; no allocation)."""
+        b = b.detach().float().contiguous()
+        if tuple(b.shape) != (self.batch, self.N, self.K) or b.device != self.buf.device:
+            raise ValueError(f"PackedBatch.update: the buffer holds [{self.batch}, {self.N}, {self.K}] operands on {self.buf.device}, got {tuple(b.shape)} on {b.device}")
+        with torch.cuda.device(b.device):
+            _lib.check(_lib.lib().awt_bmm_pack(_lib.ctx(b.device), _lib.ptr(b), self.K, self.N * self.K, self.batch, self.N, self.K, _lib.ptr(self.buf),
+                                               self.buf.numel(), _lib.stream_handle()))
 
 
 def bmm(a, pb: PackedBatch, M: int, out, resid=None, a_kmajor=None) -> None:
@@ -302,8 +372,10 @@ class _AbsorbedCross:
         a2 += self.dec.layers[i].encoder_attn.v_proj.bias                                       # rows of P sum to one
         return a2, (qt, P, c)
 
-    def backward(self, i: int, saved, da2: torch.Tensor, d_enc: torch.Tensor, L: int, grads: dict) -> torch.Tensor:
-        """Adds this layer's share of d(loss) / d(encoder states) to `d_enc` [B, S, d]; returns dq [B L, d]."""
+    def backward(self, i: int, saved, da2: torch.Tensor, d_enc: Optional[torch.Tensor], L: int, grads: dict, q: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Adds this layer's share of d(loss) / d(encoder states) to `d_enc` [B, S, d] (None: nobody needs it); returns dq [B L, d].
+        `q` (the saved query rows, bias applied, unscaled; decoder in train_base mode): also records d(loss) / d(k_proj.weight, v_proj.weight,
+        v_proj.bias) of this layer in `grads`: dW_k,h = q_h^T d(q~)_h, dW_v,h = da2_h^T context_h, db_v = column sums of da2."""
         B, S, Sp, d, H = self.B, self.S, self.Sp, self.d, self.dec.heads
         R, M = L * H, B * L
         qt, P, c = saved
@@ -319,15 +391,23 @@ class _AbsorbedCross:
         bmm((dS, 0, Sp, R * Sp), self.encT_p, R, (dqt, 0, d, R * d))                             # d(q~) = dS enc
         # d(enc)_b += P_b^T d(context)_b + dS_b^T q~_b : one [S, 2 R] x [2 R, d] product per clip
         # (all four matrices are read where they lie: both operands are K-major, two blocks stacked along K)
-        rhs = PackedBatch(kmajor=((dc, 0), (qt, 0), R, d, R * d, B, d, 2 * R))                   # B operand [d, 2 R] = [d(context)_b ; q~_b]^T
-        bmm(None, rhs, S, (d_enc, 0, d, S * d), resid=(d_enc, 0, d, S * d), a_kmajor=((P, 0), (dS, 0), R, Sp, R * Sp))
+        if d_enc is not None:
+            rhs = PackedBatch(kmajor=((dc, 0), (qt, 0), R, d, R * d, B, d, 2 * R))               # B operand [d, 2 R] = [d(context)_b ; q~_b]^T
+            bmm(None, rhs, S, (d_enc, 0, d, S * d), resid=(d_enc, 0, d, S * d), a_kmajor=((P, 0), (dS, 0), R, Sp, R * Sp))
         dq = torch.empty((M, d), dtype=torch.float32, device=dev)
         bmm((dqt, 0, H * d, d), hw["k"], M, (dq, 0, d, 64))                                      # dq_h = d(q~)_h W_k,h^T
         ab = self.dec._adapter(i, "encoder_attn", "v_proj")
-        if ab is not None:                                                                       # d(merged W_v)_h = da2_h^T context_h, then through W_v + s B A
-            A, Bm = ab
+        if ab is not None or q is not None:                                                      # d(W_v)_h = da2_h^T context_h (W_v: the merged weight under an adapter)
             dw = torch.empty((d, d), dtype=torch.float32, device=dev)
             bmm(None, PackedBatch(kmajor=((c, 0), None, M, H * d, d, H, d, M)), 64, (dw, 0, d, 64 * d), a_kmajor=((da2, 0), None, M, d, 64))
+        if q is not None:
+            ca = self.dec.layers[i].encoder_attn
+            dwk = torch.empty((d, d), dtype=torch.float32, device=dev)                           # d(W_k)_h = q_h^T d(q~)_h (d(q~) carries the 0.125)
+            bmm(None, PackedBatch(kmajor=((dqt, 0), None, M, H * d, d, H, d, M)), 64, (dwk, 0, d, 64 * d), a_kmajor=((q, 0), None, M, d, 64))
+            grads[id(ca.k_proj.weight)], grads[id(ca.v_proj.weight)] = dwk, dw
+            grads[id(ca.v_proj.bias)] = column_sums_ld(da2)                                      # rows of P sum to one
+        if ab is not None:                                                                       # through W_v + s B A
+            A, Bm = ab
             scale, prec = self.dec.lora.scale, self.dec.precision
             grads[id(Bm)] = gemm(dw, A.detach(), prec) * scale                                   # dB [d, r] = s dW A^T
             grads[id(A)] = gemm(Bm.detach().t().contiguous(), dw.t().contiguous(), prec) * scale  # dA [r, d] = s B^T dW
@@ -407,13 +487,18 @@ class _Leaf(nn.Module):
 
 
 class NativeWhisperDecoder(nn.Module):
-    """Pre-LN Whisper decoder with tied output projection on libawt.  HF parameter names; all parameters frozen."""
+    """Pre-LN Whisper decoder with tied output projection on libawt.  HF parameter names.  The base parameters are frozen unless
+    `train_base=True` (full-parameter fine-tuning): then every one of them requires grad -- the token table and the LEARNED
+    position table included, as in HF -- and `loss` returns their gradients; no adapters in that mode."""
 
     LORA_TARGETS = ("q_proj", "v_proj")
 
     def __init__(self, d: int, layers: int, heads: int, ffn: int, vocab: int = 51865, max_target_positions: int = 448, precision: str = "bf16x3",
-                 lora=None, lora_seed: int = 0):
+                 lora=None, lora_seed: int = 0, train_base: bool = False):
         super().__init__()
+        if train_base and lora is not None:
+            raise ValueError("train_base=True trains the decoder's base weights: pass lora=None")
+        self.train_base = bool(train_base)
         if d != heads * 64:
             raise ValueError("the native attention kernels are specialised for head_dim 64 (every Whisper size)")
         self.d, self.n_layers, self.heads, self.ffn, self.vocab, self.precision = d, layers, heads, ffn, vocab, precision
@@ -422,7 +507,7 @@ class NativeWhisperDecoder(nn.Module):
         self.lora = lora
 
         def P(*shape):
-            return nn.Parameter(torch.zeros(*shape), requires_grad=False)
+            return nn.Parameter(torch.zeros(*shape), requires_grad=self.train_base)
 
         self.embed_tokens = _Leaf(); self.embed_tokens.weight = P(vocab, d)
         self.embed_positions = _Leaf(); self.embed_positions.weight = P(max_target_positions, d)
@@ -481,6 +566,10 @@ class NativeWhisperDecoder(nn.Module):
                         out += [leaf.lora_A, leaf.lora_B]
         return out
 
+    def base_parameters(self) -> List[nn.Parameter]:
+        """Every base parameter, in `named_parameters()` order (what `train_base` trains)."""
+        return [p for n, p in self.named_parameters() if "lora_" not in n]
+
     def _adapter(self, i: int, att: str, proj: str):
         if self.lora is None or proj not in self.lora.targets:
             return None
@@ -517,33 +606,51 @@ class NativeWhisperDecoder(nn.Module):
         return super()._apply(fn, *a, **kw)
 
     def packed(self) -> Dict[str, object]:
-        """Frozen weights as `awt_weight` handles, rebuilt when a parameter changed: per layer the fused self-attention q|k|v
+        """The weights as `awt_weight` handles, brought up to date when a parameter changed: per layer the fused self-attention q|k|v
         projection, the two output projections, the cross-attention query projection, fc1, fc2; the fused cross-attention k|v
         projection of ALL layers (one GEMM over the encoder output) and the tied vocabulary projection."""
         vers = tuple((id(p), p._version) for n, p in self.named_parameters() if "lora_" not in n)     # identity too: a replaced Parameter object starts at version 0 again
         if self._packed is not None and self._versions == vers:
             return self._packed
-        pk: Dict[str, object] = {"layers": []}
         prec = self.precision
-        zeros = torch.zeros(self.d, device=self.embed_tokens.weight.device)
-        for lay in self.layers:
-            sa, ca = lay.self_attn, lay.encoder_attn
-            pk["layers"].append({
-                "qkv": PackedLinear(torch.cat([sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight]), torch.cat([sa.q_proj.bias, zeros, sa.v_proj.bias]), prec),
-                "so": PackedLinear(sa.out_proj.weight, sa.out_proj.bias, prec),
-                "cq": PackedLinear(ca.q_proj.weight, ca.q_proj.bias, prec),
-                "co": PackedLinear(ca.out_proj.weight, ca.out_proj.bias, prec),
-                "fc1": PackedLinear(lay.fc1.weight, lay.fc1.bias, prec),
-                "fc2": PackedLinear(lay.fc2.weight, lay.fc2.bias, prec)})
-        att = [l.encoder_attn for l in self.layers]
-        pk["ckv"] = PackedLinear(torch.cat([w for a in att for w in (a.k_proj.weight, a.v_proj.weight)]),
-                                 torch.cat([b for a in att for b in (zeros, a.v_proj.bias)]), prec)
-        pk["vocab"] = PackedLinear(self.embed_tokens.weight, None, prec)
         H, d = self.heads, self.d
-        pk["cross_heads"] = []                                                     # per-head blocks of W_k / W_v as batched B operands (_AbsorbedCross)
-        for a in att:
-            wk, wv = a.k_proj.weight.detach().view(H, 64, d), a.v_proj.weight.detach().view(H, 64, d)
-            pk["cross_heads"].append({"k": PackedBatch(wk), "kT": PackedBatch(wk.transpose(1, 2)), "v": PackedBatch(wv), "vT": PackedBatch(wv.transpose(1, 2))})
+        zeros = torch.zeros(d, device=self.embed_tokens.weight.device)
+        # every packed object as (where it lives in the result, the parameters it is made of, what to pack): a (weight, bias) pair becomes a
+        # PackedLinear, a [H, N, K] tensor the per-head B operands of _AbsorbedCross (a PackedBatch)
+        plan = []
+        for i, lay in enumerate(self.layers):
+            sa, ca = lay.self_attn, lay.encoder_attn
+            where = ("layers", i)
+            plan += [(where, "qkv", (sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight, sa.q_proj.bias, sa.v_proj.bias),
+                      lambda sa=sa: (torch.cat([sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight]), torch.cat([sa.q_proj.bias, zeros, sa.v_proj.bias]))),
+                     (where, "so", (sa.out_proj.weight, sa.out_proj.bias), lambda sa=sa: (sa.out_proj.weight, sa.out_proj.bias)),
+                     (where, "cq", (ca.q_proj.weight, ca.q_proj.bias), lambda ca=ca: (ca.q_proj.weight, ca.q_proj.bias)),
+                     (where, "co", (ca.out_proj.weight, ca.out_proj.bias), lambda ca=ca: (ca.out_proj.weight, ca.out_proj.bias)),
+                     (where, "fc1", (lay.fc1.weight, lay.fc1.bias), lambda lay=lay: (lay.fc1.weight, lay.fc1.bias)),
+                     (where, "fc2", (lay.fc2.weight, lay.fc2.bias), lambda lay=lay: (lay.fc2.weight, lay.fc2.bias))]
+            where = ("cross_heads", i)                                             # per-head blocks of W_k / W_v as batched B operands
+            plan += [(where, "k", (ca.k_proj.weight,), lambda ca=ca: ca.k_proj.weight.detach().view(H, 64, d)),
+                     (where, "kT", (ca.k_proj.weight,), lambda ca=ca: ca.k_proj.weight.detach().view(H, 64, d).transpose(1, 2)),
+                     (where, "v", (ca.v_proj.weight,), lambda ca=ca: ca.v_proj.weight.detach().view(H, 64, d)),
+                     (where, "vT", (ca.v_proj.weight,), lambda ca=ca: ca.v_proj.weight.detach().view(H, 64, d).transpose(1, 2))]
+        att = [l.encoder_attn for l in self.layers]
+        plan += [((), "ckv", tuple(t for a in att for t in (a.k_proj.weight, a.v_proj.weight, a.v_proj.bias)),
+                  lambda: (torch.cat([w for a in att for w in (a.k_proj.weight, a.v_proj.weight)]), torch.cat([b for a in att for b in (zeros, a.v_proj.bias)]))),
+                 ((), "vocab", (self.embed_tokens.weight,), lambda: (self.embed_tokens.weight, None))]
+        # the same Parameter objects at new versions (an optimizer step of the train_base mode): only what changed is packed again, into the
+        # handles that exist; anything else (first use, load_state_dict, .to(), a replaced Parameter) builds every handle
+        fresh = self._packed is None or tuple(i for i, _ in self._versions) != tuple(i for i, _ in vers)
+        changed = set() if fresh else {i for (i, v), (_, v0) in zip(vers, self._versions) if v != v0}
+        pk: Dict[str, object] = {"layers": [{} for _ in self.layers], "cross_heads": [{} for _ in self.layers]} if fresh else self._packed
+        with torch.no_grad():
+            for where, key, sources, make in plan:
+                slot = pk[where[0]][where[1]] if where else pk
+                if fresh:
+                    what = make()
+                    slot[key] = PackedLinear(what[0], what[1], prec) if isinstance(what, tuple) else PackedBatch(what)
+                elif any(id(p) in changed for p in sources):
+                    what = make()
+                    slot[key].update(*what) if isinstance(what, tuple) else slot[key].update(what)
         self._packed, self._versions = pk, vers
         return pk
 
@@ -636,15 +743,20 @@ class NativeWhisperDecoder(nn.Module):
             return logits.view(rows, L, -1)[:, L - 1]
 
     def loss(self, decoder_input_ids: torch.Tensor, labels: torch.Tensor, encoder_hidden_states: torch.Tensor):
-        """(loss, logits [B, L, vocab]): differentiable w.r.t. `encoder_hidden_states` only (the decoder is frozen)."""
+        """(loss, logits [B, L, vocab]): differentiable w.r.t. `encoder_hidden_states` and the decoder's trainable parameters (its adapters, or
+        with `train_base` every base parameter; none for the frozen decoder)."""
         holder: List[torch.Tensor] = []
-        loss = _DecoderLoss.apply(encoder_hidden_states, self, decoder_input_ids, labels, holder, *self.lora_parameters())
+        trained = self.base_parameters() if self.train_base else self.lora_parameters()
+        loss = _DecoderLoss.apply(encoder_hidden_states, self, decoder_input_ids, labels, holder, *trained)
         return loss, holder[0]
 
 
 class _DecoderLoss(torch.autograd.Function):
     """decoder + tied projection + cross-entropy as ONE autograd node with a hand-written native backward: d(loss) / d(encoder states) and,
-    with decoder adapters, d(loss) / d(lora_A, lora_B) in `NativeWhisperDecoder.lora_parameters()` order."""
+    with decoder adapters, d(loss) / d(lora_A, lora_B) in `NativeWhisperDecoder.lora_parameters()` order, or in the `train_base` mode the
+    gradient of every base parameter in `base_parameters()` order.  Each parameter gradient is formed where its dY is live in the backward
+    (DESIGN §4.6b): weights on the weight-gradient GEMM (`ops.weight_grad`, fused operands read in place by column offset), biases as pitched
+    column sums, LayerNorm affines by `awt_op_layernorm_param_grad`, the tied embedding as the projection's product plus `awt_op_embed_backward`."""
 
     @staticmethod
     def forward(ctx, enc, dec: NativeWhisperDecoder, ids, labels, holder, *adapters):
@@ -663,7 +775,10 @@ class _DecoderLoss(torch.autograd.Function):
         loss, dlogits = cross_entropy(logits, labels, dec.vocab)
         holder.append(logits.view(B, L, -1)[:, :, : dec.vocab])
         ctx.dec, ctx.saved, ctx.kv, ctx.x_last, ctx.dlogits, ctx.shape = dec, save, kv, x, dlogits, (B, S, L)
-        ctx.enc2d, ctx.u_cv, ctx.n_adapters = (enc2d if u_cv is not None else None), u_cv, len(adapters)
+        keep_enc = u_cv is not None or (dec.train_base and not isinstance(kv, _AbsorbedCross))     # the X of the value adapters' / the cross k | v weights' gradients
+        ctx.enc2d, ctx.u_cv, ctx.n_adapters = (enc2d if keep_enc else None), u_cv, len(adapters)
+        if dec.train_base:
+            ctx.ids, ctx.xf = ids, xf                                                       # the embedding's backward and the tied projection's X
         return loss
 
     @staticmethod
@@ -683,11 +798,34 @@ class _DecoderLoss(torch.autograd.Function):
             grads[id(Bm)] = gemm(dy.t().contiguous(), u.t().contiguous(), prec) * scale     # dB [d, r] = (alpha / r) dy^T u
             return gemm(du, A.detach().t().contiguous(), prec) * scale                      # [M, d] = (alpha / r) du A
 
+        from . import ops
+        base = dec.train_base
+        need_enc = ctx.needs_input_grad[0] or not base                                      # a frozen encoder under train_base: no d(encoder states)
+
+        def wgrad(dy, x, **kw):                                                             # dW [n, k] = dy[:, ycol: ycol + n]^T x[:, xcol: xcol + k]
+            return ops.weight_grad(dy, x, precision=prec, **kw)
+
+        def linear_grads(leaf, dy, x):
+            """Records d(weight) = dy^T x and d(bias) = column sums of dy of one nn.Linear."""
+            n = leaf.weight.shape[0]
+            grads[id(leaf.weight)] = wgrad(dy, x, n=n)
+            grads[id(leaf.bias)] = column_sums_ld(dy, 0, n)
+
+        def norm_grads(leaf, dy, x):
+            grads[id(leaf.weight)], grads[id(leaf.bias)] = layernorm_param_grad(dy, x)
+
         dlogits = ctx.dlogits * g                                                           # upstream scalar (1 / micro-batches, ...)
-        dx = layernorm_backward(pk["vocab"].backward_input(dlogits), ctx.x_last, dec.layer_norm.weight)
+        dxf = pk["vocab"].backward_input(dlogits)
+        if base:
+            norm_grads(dec.layer_norm, dxf, ctx.x_last)
+            # the tied table, projection side: dlogits^T LN(x_last) over the padded vocabulary [Np, d] (the padding columns of dlogits are zero);
+            # the parameter's gradient is its first `vocab` rows, and the lookup side is added to them after the last layer
+            d_tok = wgrad(dlogits, ctx.xf)
+        dx = layernorm_backward(dxf, ctx.x_last, dec.layer_norm.weight)
+        del dxf
         absorbed = isinstance(kv, _AbsorbedCross)
         if absorbed:
-            d_enc = torch.zeros((B, S, d), dtype=torch.float32, device=dx.device)           # every layer adds its share (one batched GEMM each)
+            d_enc = torch.zeros((B, S, d), dtype=torch.float32, device=dx.device) if need_enc else None     # every layer adds its share (one batched GEMM each)
         else:
             dkv = torch.empty_like(kv)                                                      # every layer writes its own two d-wide blocks
         for i in range(nl - 1, -1, -1):
@@ -695,27 +833,46 @@ class _DecoderLoss(torch.autograd.Function):
             x0, qkv, a, lse, x1, q, a2, lse2, x2, f, us = save[i]
             # MLP: x3 = x2 + fc2(gelu(fc1(LN3(x2))))
             df = gelu_backward(f, p["fc2"].backward_input(dx))
-            dx = layernorm_backward(p["fc1"].backward_input(df), x2, lay.final_layer_norm.weight, dres=dx)
+            dh3 = p["fc1"].backward_input(df)
+            if base:                                                                        # LayerNorm outputs and gelu(f) are recomputed: B x L rows
+                linear_grads(lay.fc2, dx, gelu(f))
+                linear_grads(lay.fc1, df, layernorm(x2, lay.final_layer_norm.weight, lay.final_layer_norm.bias))
+                norm_grads(lay.final_layer_norm, dh3, x2)
+            dx = layernorm_backward(dh3, x2, lay.final_layer_norm.weight, dres=dx)
+            del dh3
             # cross-attention: x2 = x1 + out(attn(q(LN2(x1)), K_i, V_i))
+            if base:
+                linear_grads(lay.encoder_attn.out_proj, dx, a2)
             da2 = p["co"].backward_input(dx)
             if absorbed:
-                dq = kv.backward(i, lse2, da2, d_enc, L, grads)
+                dq = kv.backward(i, lse2, da2, d_enc, L, grads, q if base else None)
             else:
                 dq = torch.empty_like(q)
                 attention_small_backward((q, 0), d, (kv, 2 * i * d), 2 * nl * d, (kv, (2 * i + 1) * d), 2 * nl * d, a2, da2, lse2,
                                          (dq, 0), (dkv, 2 * i * d), (dkv, (2 * i + 1) * d), B, H, L, S, False, 0)
             dh2 = p["cq"].backward_input(dq)
+            if base:
+                linear_grads(lay.encoder_attn.q_proj, dq, layernorm(x1, lay.encoder_attn_layer_norm.weight, lay.encoder_attn_layer_norm.bias))
+                norm_grads(lay.encoder_attn_layer_norm, dh2, x1)
             ab = dec._adapter(i, "encoder_attn", "q_proj")
             if ab is not None:
                 h2 = layernorm(x1, lay.encoder_attn_layer_norm.weight, lay.encoder_attn_layer_norm.bias)      # recomputed: B x L rows
                 dh2 = dh2 + adapter_backward(ab, h2, us["cq"], dq)
             dx = layernorm_backward(dh2, x1, lay.encoder_attn_layer_norm.weight, dres=dx)
             # self-attention: x1 = x0 + out(attn(qkv(LN1(x0))))
+            if base:
+                linear_grads(lay.self_attn.out_proj, dx, a)
             da = p["so"].backward_input(dx)
             dqkv = torch.empty_like(qkv)
             attention_small_backward((qkv, 0), 3 * d, (qkv, d), 3 * d, (qkv, 2 * d), 3 * d, a, da, lse,
                                      (dqkv, 0), (dqkv, d), (dqkv, 2 * d), B, H, L, L, True, 0)
             dh = p["qkv"].backward_input(dqkv)
+            if base:                                                                        # q | k | v: ONE [3 d, d] product, its row blocks are the three gradients
+                sa = lay.self_attn
+                dw = wgrad(dqkv, layernorm(x0, lay.self_attn_layer_norm.weight, lay.self_attn_layer_norm.bias))
+                grads[id(sa.q_proj.weight)], grads[id(sa.k_proj.weight)], grads[id(sa.v_proj.weight)] = dw[:d], dw[d: 2 * d], dw[2 * d:]
+                grads[id(sa.q_proj.bias)], grads[id(sa.v_proj.bias)] = column_sums_ld(dqkv, 0, d), column_sums_ld(dqkv, 2 * d, d)
+                norm_grads(lay.self_attn_layer_norm, dh, x0)
             if us:
                 h = None
                 for proj, col in (("q_proj", 0), ("v_proj", 2 * d)):
@@ -726,8 +883,20 @@ class _DecoderLoss(torch.autograd.Function):
                         dh = dh + adapter_backward(ab, h, us[proj], dqkv[:, col: col + d].contiguous())
             dx = layernorm_backward(dh, x0, lay.self_attn_layer_norm.weight, dres=dx)
         ctx.saved = ctx.kv = ctx.dlogits = None
+        if base:                                                                            # the lookup side of the tied table, and the position rows
+            d_pos = torch.zeros_like(dec.embed_positions.weight)
+            embed_backward(ctx.ids, dx, d_tok[: dec.vocab], d_pos)
+            grads[id(dec.embed_tokens.weight)], grads[id(dec.embed_positions.weight)] = d_tok[: dec.vocab], d_pos
+            if not absorbed:                                                                # all layers' cross k / v weights: ONE product dkv^T enc
+                dw = wgrad(dkv, ctx.enc2d)
+                for i, lay in enumerate(dec.layers):
+                    ca = lay.encoder_attn
+                    grads[id(ca.k_proj.weight)], grads[id(ca.v_proj.weight)] = dw[2 * i * d: (2 * i + 1) * d], dw[(2 * i + 1) * d: (2 * i + 2) * d]
+                    grads[id(ca.v_proj.bias)] = column_sums_ld(dkv, (2 * i + 1) * d, d)
+                ctx.enc2d = None
+            ctx.ids = ctx.xf = None
         if not absorbed:
-            d_enc = pk["ckv"].backward_input(dkv)                                           # [B S, d]
+            d_enc = pk["ckv"].backward_input(dkv) if need_enc else None                     # [B S, d]
         if ctx.u_cv is not None:
             # cross-attention value adapters: dV_i = dkv block 2 i + 1 (B x S rows); their share of d(encoder states) is ONE GEMM over all layers
             r = dec.lora.r
@@ -744,5 +913,5 @@ class _DecoderLoss(torch.autograd.Function):
             a_all_t = torch.cat([dec._adapter(i, "encoder_attn", "v_proj")[0].detach() for i in range(nl)], dim=0).t().contiguous()   # [d, layers * r]
             d_enc = d_enc + gemm(du_all, a_all_t, prec) * scale
             ctx.enc2d = ctx.u_cv = None
-        params = dec.lora_parameters() if ctx.n_adapters else []
-        return (d_enc.view(B, S, d), None, None, None, None, *[grads.get(id(p)) for p in params])
+        params = (dec.base_parameters() if base else dec.lora_parameters()) if ctx.n_adapters else []
+        return (d_enc.view(B, S, d) if d_enc is not None else None, None, None, None, None, *[grads.get(id(p)) for p in params])
