@@ -463,6 +463,38 @@ size_t awt_dtw_workspace_bytes(int clips, int T, int frames);
 int awt_op_dtw(awt_ctx* c, const float* matrix, int clips, int T, int frames, const int32_t* num_frames, int negate, int32_t* jump_frame,
                int32_t* text_idx, int32_t* time_idx, int32_t* path_start, void* workspace, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Operators of the 1-D CNN classifier (csrc/cnn_ops.hip; cnn_classifier.py).  Activations are channels-last fp32 rows [B T, C] (clip b,
+ * frame t at row b T + t), C a multiple of 4, tensors 16-byte aligned.  Deterministic: no atomics, fixed slabs of rows added in slab order.
+ *
+ * awt_op_conv1d: y[b, t, :] = bias + sum_tap x[b, t + tap - 1, :] w[:, :, tap]^T (Conv1d kernel_size 3, padding 1, stride 1; frames
+ * outside [0, T) of the SAME clip read as zero) as one GEMM launch of three row-mapped K segments.  w: the fp32 Conv1d weight
+ * [Cout, Cin, 3], packed into the workspace per call; taps must be 3; Cin % 64 == 0 (zero-pad the channels), Cout % 128 == 0; terms 1
+ * (bf16), 3 (bf16x3) or 4 (fp16x3: fp16 hi + lo planes, 22 bits per operand, for operands inside fp16's range -- the forward).  The input gradient is the same call on dy with w'[ci, co, tap] = w[co, ci, 2 - tap]; the weight gradient is
+ * awt_op_weight_grad per tap with the same row map, the bias gradient awt_op_column_sums. */
+size_t awt_op_conv1d_workspace_bytes(int B, int T, int Cin, int Cout);
+int awt_op_conv1d(awt_ctx* c, const float* x, const float* w, const float* bias, float* y, int B, int T, int Cin, int Cout, int taps, int terms,
+                  void* workspace, size_t ws_bytes, void* stream);
+/* Per-channel mean and BIASED variance of x [M, C] (training-mode BatchNorm1d's batch statistics), one read of x: per 64-row slab a
+ * two-pass mean / sum of squared deviations in registers, the slabs merged in order with the pairwise update of Chan et al. (never
+ * E[x^2] - E[x]^2).  A constant column gives var = 0 exactly. */
+size_t awt_op_batchnorm_stats_workspace_bytes(int M, int C);
+int awt_op_batchnorm_stats(awt_ctx* c, const float* x, int M, int C, float* mean, float* var, void* workspace, size_t ws_bytes, void* stream);
+/* y = pool(relu((x - mean) (var + eps)^-1/2 gamma + beta)) in one pass over x [B T, C]; mean / var are the batch statistics (train) or
+ * the running statistics (eval).  pool = 2: MaxPool1d(2, 2) along T inside each clip, y [B (T / 2), C], an odd T drops its last frame
+ * (T >= 2); pool = 0: the mean over T (AdaptiveAvgPool1d(1)), y [B, C]. */
+int awt_op_bn_relu_pool(awt_ctx* c, const float* x, const float* mean, const float* var, const float* gamma, const float* beta, float eps,
+                        float* y, int B, int T, int C, int pool, void* stream);
+/* Backward of awt_op_bn_relu_pool under BATCH statistics (mean / var = awt_op_batchnorm_stats of x, M = B T): from dy (the pooled
+ * gradient) and the saved pre-BN x, with the ReLU mask and the pooling winner recomputed (nothing else is stored),
+ *   dbeta = sum dz, dgamma = sum dz xhat, dx = gamma rstd (dz - dbeta / M - xhat dgamma / M),  dz = the gradient at the BatchNorm output
+ * (frames an odd T drops have dz = 0).  Three launches: slab partials of the two sums (reads x once), their sum in slab order
+ * ([slabs, 2 C] floats), dx (reads x once). */
+size_t awt_op_bn_relu_pool_backward_workspace_bytes(int B, int T, int C);
+int awt_op_bn_relu_pool_backward(awt_ctx* c, const float* dy, const float* x, const float* mean, const float* var, const float* gamma,
+                                 const float* beta, float eps, float* dx, float* dgamma, float* dbeta, int B, int T, int C, int pool,
+                                 void* workspace, size_t ws_bytes, void* stream);
+
 /* Process-wide tuning / test hooks.  key "gemm_tile": 0 = choose the GEMM block tile from the shape (default), 64 / 128 / 256 =
  * force the 64 x 128, 128 x 128 or 128 x 256 tile (256 falls back to 128 when N is not a multiple of 256) so that tests can
  * drive every tiling on small shapes.

@@ -7,3 +7,4 @@ There is no CPU fallback: every operator raises if the library is missing.
 """
 from .weights import (CONFIGS, EncoderConfig, LoraSpec, config, init_encoder_weights,  # noqa: F401
                       init_lora_weights, weights_digest)
+from .cnn_classifier import CNNUrbanSound8KClassifier, eval_or_test_cnn, train_cnn  # noqa: F401,E402
