@@ -481,19 +481,37 @@ int awt_op_conv1d(awt_ctx* c, const float* x, const float* w, const float* bias,
 size_t awt_op_batchnorm_stats_workspace_bytes(int M, int C);
 int awt_op_batchnorm_stats(awt_ctx* c, const float* x, int M, int C, float* mean, float* var, void* workspace, size_t ws_bytes, void* stream);
 /* y = pool(relu((x - mean) (var + eps)^-1/2 gamma + beta)) in one pass over x [B T, C]; mean / var are the batch statistics (train) or
- * the running statistics (eval).  pool = 2: MaxPool1d(2, 2) along T inside each clip, y [B (T / 2), C], an odd T drops its last frame
- * (T >= 2); pool = 0: the mean over T (AdaptiveAvgPool1d(1)), y [B, C]. */
+ * the running statistics (eval).  `pool`:
+ *   AWT_POOL_MEAN       the mean over T (AdaptiveAvgPool1d(1)), y [B, C];
+ *   AWT_POOL_MAX2       MaxPool1d(2, 2) along T inside each clip, y [B (T / 2), C], an odd T drops its last frame (T >= 2);
+ *   AWT_POOL_MAX4       MaxPool1d(4), y [B (T / 4), C], the trailing T mod 4 frames are dropped (T >= 4);
+ *   AWT_POOL_MAX4_MEAN  MaxPool1d(4) then AdaptiveAvgPool1d(1): y [B, C] = the mean over the T / 4 pooled frames, added in frame order; the
+ *                       pooled tensor is never written (T >= 4).
+ * Any other value is refused. */
+enum { AWT_POOL_MEAN = 0, AWT_POOL_MAX2 = 2, AWT_POOL_MAX4 = 4, AWT_POOL_MAX4_MEAN = 5 };
 int awt_op_bn_relu_pool(awt_ctx* c, const float* x, const float* mean, const float* var, const float* gamma, const float* beta, float eps,
                         float* y, int B, int T, int C, int pool, void* stream);
 /* Backward of awt_op_bn_relu_pool under BATCH statistics (mean / var = awt_op_batchnorm_stats of x, M = B T): from dy (the pooled
  * gradient) and the saved pre-BN x, with the ReLU mask and the pooling winner recomputed (nothing else is stored),
  *   dbeta = sum dz, dgamma = sum dz xhat, dx = gamma rstd (dz - dbeta / M - xhat dgamma / M),  dz = the gradient at the BatchNorm output
- * (frames an odd T drops have dz = 0).  Three launches: slab partials of the two sums (reads x once), their sum in slab order
+ * (frames that the max-pool drops have dz = 0; the winner of a window is the FIRST frame with its largest pre-ReLU value, torch's tie-break;
+ * AWT_POOL_MAX4_MEAN: dz at a winner is dy[b] / (T / 4)).  Three launches: slab partials of the two sums (reads x once), their sum in slab order
  * ([slabs, 2 C] floats), dx (reads x once). */
 size_t awt_op_bn_relu_pool_backward_workspace_bytes(int B, int T, int C);
 int awt_op_bn_relu_pool_backward(awt_ctx* c, const float* dy, const float* x, const float* mean, const float* var, const float* gamma,
                                  const float* beta, float eps, float* dx, float* dgamma, float* dbeta, int B, int T, int C, int pool,
                                  void* workspace, size_t ws_bytes, void* stream);
+
+/* Conv1d(1, Cout, kernel, stride) without padding on raw waveforms (CNNWaveformClassifier's first layer):
+ *   y[b, t, co] = bias[co] + sum_{k < kernel} x[b * x_pitch + t * stride + k] * w[co, 0, k],   t < T1 = (n_samples - kernel) / stride + 1,
+ * x fp32 [B, n_samples] at a clip pitch of x_pitch floats, w the fp32 nn.Conv1d weight [Cout, 1, kernel], y channels-last rows [B T1, Cout].
+ * Exact fp32: the products are formed on v_mfma_f32_16x16x4_f32, so each output is the k-ordered fmaf chain that starts at the bias.  A workgroup
+ * stages the samples of 128 consecutive frames and the weight in LDS once; no workspace, no atomics, deterministic.  Required: stride % 8 == 0,
+ * kernel % stride == 0, n_samples >= kernel, Cout % 16 == 0, (127 + kernel / stride) (stride + 4) + Cout (kernel + 4) <= 16384 (64 KiB of LDS),
+ * x_pitch >= n_samples and x_pitch % 4 == 0, B <= 65535, 16-byte aligned tensors.  Samples past the last frame are not read.  The weight gradient
+ * is awt_op_weight_grad per block of `stride` taps over the waveform viewed as rows of `stride` samples, the bias gradient awt_op_column_sums. */
+int awt_op_conv1d_framed(awt_ctx* c, const float* x, int64_t x_pitch, const float* w, const float* bias, float* y, int B, int n_samples, int kernel,
+                         int stride, int Cout, void* stream);
 
 /* Process-wide tuning / test hooks.  key "gemm_tile": 0 = choose the GEMM block tile from the shape (default), 64 / 128 / 256 =
  * force the 64 x 128, 128 x 128 or 128 x 256 tile (256 falls back to 128 when N is not a multiple of 256) so that tests can

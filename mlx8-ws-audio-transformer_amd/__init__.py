@@ -8,3 +8,4 @@ There is no CPU fallback: every operator raises if the library is missing.
 from .weights import (CONFIGS, EncoderConfig, LoraSpec, config, init_encoder_weights,  # noqa: F401
                       init_lora_weights, weights_digest)
 from .cnn_classifier import CNNUrbanSound8KClassifier, eval_or_test_cnn, train_cnn  # noqa: F401,E402
+from .waveform_classifier import CNNWaveformClassifier, UrbanSoundRawDataset, train_waveform_classifier  # noqa: F401,E402

@@ -134,6 +134,7 @@ _SIGNATURES = {
     "awt_op_bn_relu_pool": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp]),
     "awt_op_bn_relu_pool_backward_workspace_bytes": (_sz, [_i, _i, _i]),
     "awt_op_bn_relu_pool_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "awt_op_conv1d_framed": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "awt_tuning_set": (_i, [C.c_char_p, _i]),
     "awt_prof_enable": (_i, [_vp, _i]),
     "awt_prof_collect": (_i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(C.c_double)]),

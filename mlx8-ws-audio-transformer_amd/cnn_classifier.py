@@ -21,7 +21,8 @@ once to channels-last rows [B T, C], which every operator below reads and writes
 The running statistics are updated with torch ops on the [C] vectors; ReLU in the head and the five Dropouts are element-wise torch ops under
 autograd, as in the Transformer classifier.  There is no torch fallback for conv, BatchNorm or pooling: without libawt the first call raises.
 Nothing is cached between calls (the conv weights are packed per call, like `awt_op_linear`'s), so there is no state that a parameter update
-or a `copy.deepcopy` could leave stale.  `CNNWaveformClassifier` (spectrogram.py:664-697) is out of scope.
+or a `copy.deepcopy` could leave stale.  `CNNWaveformClassifier` (spectrogram.py:664-697) is built from the same operators in
+waveform_classifier.py.
 """
 from __future__ import annotations
 
@@ -40,6 +41,8 @@ CNN_CHANNELS = (128, 256, 512, 512)
 HEAD_WIDTHS = (256, 128)
 _TERMS = {"bf16": 1, "bf16x3": 3}
 _FORWARD_TERMS = {"bf16": 1, "bf16x3": 3, "fp16x3": 4}       # common.h PREC_*
+POOL_MEAN, POOL_MAX2, POOL_MAX4, POOL_MAX4_MEAN = 0, 2, 4, 5  # include/awt.h AWT_POOL_*
+_POOL_WINDOW = {POOL_MEAN: 0, POOL_MAX2: 2, POOL_MAX4: 4, POOL_MAX4_MEAN: 4}
 
 
 def _terms(precision: str) -> int:
@@ -124,9 +127,10 @@ def batchnorm_stats(x: torch.Tensor):
 
 def bn_relu_pool(x: torch.Tensor, mean: torch.Tensor, var: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, B: int, T: int,
                  pool: int) -> torch.Tensor:
-    """pool(relu(batch_norm(x))) of x [B T, C] in one pass (`awt_op_bn_relu_pool`): pool = 2 -> [B (T // 2), C], pool = 0 -> [B, C]."""
+    """pool(relu(batch_norm(x))) of x [B T, C] in one pass (`awt_op_bn_relu_pool`): POOL_MAX2 / POOL_MAX4 -> [B (T // 2), C] / [B (T // 4), C],
+    POOL_MEAN (the mean over T) and POOL_MAX4_MEAN (the mean over the T // 4 pooled frames) -> [B, C]."""
     C = _check_rows(x, B, T)
-    y = torch.empty((B * (T // 2) if pool == 2 else B, C), dtype=torch.float32, device=x.device)
+    y = torch.empty((B * (T // pool) if pool in (POOL_MAX2, POOL_MAX4) else B, C), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         _lib.check(_lib.lib().awt_op_bn_relu_pool(_lib.ctx(x.device), _lib.ptr(x), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(gamma), _lib.ptr(beta),
                                                   float(eps), _lib.ptr(y), B, T, C, pool, _lib.stream_handle()))
@@ -190,8 +194,10 @@ class _BnReluPool(torch.autograd.Function):
 def batchnorm_relu_pool(bn: nn.BatchNorm1d, x: torch.Tensor, B: int, T: int, pool: int) -> torch.Tensor:
     """`pool(relu(bn(x)))` for a `nn.BatchNorm1d` holding the parameters and buffers: in train() on the batch statistics (updating
     `running_mean`, `running_var` -- with the unbiased variance -- and `num_batches_tracked` as the module does), in eval() on the running ones."""
-    if pool == 2 and T < 2:
-        raise ValueError("MaxPool1d(2, 2) needs at least 2 frames")
+    if pool not in _POOL_WINDOW:
+        raise ValueError(f"pool must be one of {sorted(_POOL_WINDOW)} (POOL_MEAN, POOL_MAX2, POOL_MAX4, POOL_MAX4_MEAN)")
+    if T < _POOL_WINDOW[pool]:
+        raise ValueError(f"MaxPool1d({_POOL_WINDOW[pool]}) needs at least {_POOL_WINDOW[pool]} frames")
     x = x.contiguous()
     if not (bn.training or not bn.track_running_stats):
         return bn_relu_pool(x, bn.running_mean, bn.running_var, bn.weight.detach(), bn.bias.detach(), bn.eps, B, T, pool)

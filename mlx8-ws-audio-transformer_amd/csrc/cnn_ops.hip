@@ -104,18 +104,40 @@ __device__ __forceinline__ float4 relu4(const float4 z) { return max4(z, f4(0.f)
 __device__ __forceinline__ float4 gate(const float4 z, const float4 g) {           // g where z > 0: ReLU's derivative
   return make_float4(z.x > 0.f ? g.x : 0.f, z.y > 0.f ? g.y : 0.f, z.z > 0.f ? g.z : 0.f, z.w > 0.f ? g.w : 0.f);
 }
-// Gradient of max(relu(za), relu(zb)) with respect to za and zb.  The winner is the larger pre-ReLU value, the first on a tie.  After the ReLU a
-// tie between two DIFFERENT inputs can only be 0 = 0, where ReLU's derivative is zero whichever index is named, so the kernel would not have to
-// reproduce torch's first-index tie-break; `>=` costs nothing and also covers equal positive values (a constant channel ties at beta).
-__device__ __forceinline__ void pool2_grad(const float4 za, const float4 zb, const float4 g, float4& ga, float4& gb) {
-  ga = make_float4(za.x >= zb.x ? g.x : 0.f, za.y >= zb.y ? g.y : 0.f, za.z >= zb.z ? g.z : 0.f, za.w >= zb.w ? g.w : 0.f);
-  gb = gate(zb, g - ga);
-  ga = gate(za, ga);
+// Gradient of max_i relu(z_i) over a pooling window of W frames with respect to each z_i.  The winner is the FIRST frame holding the window's
+// largest pre-ReLU value: walking the frames in order, `rem` is the part of g not yet handed out, and a frame with z_i >= max takes all of it.
+// After the ReLU a tie between two DIFFERENT inputs can only be 0 = 0, where ReLU's derivative is zero whichever index is named, so the kernel
+// would not have to reproduce torch's first-index tie-break; `>=` costs nothing and also covers equal positive values (a constant channel ties
+// at beta).
+__device__ __forceinline__ float4 take_ge(const float4 z, const float4 m, const float4 g) {
+  return make_float4(z.x >= m.x ? g.x : 0.f, z.y >= m.y ? g.y : 0.f, z.z >= m.z ? g.z : 0.f, z.w >= m.w ? g.w : 0.f);
+}
+template <int W>
+__device__ __forceinline__ void pool_grad(const float4 (&z)[W], const float4 g, float4 (&gz)[W]) {
+  float4 m = z[0], rem = g;
+#pragma unroll
+  for (int i = 1; i < W; ++i) m = max4(m, z[i]);
+#pragma unroll
+  for (int i = 0; i < W; ++i) {
+    const float4 t = take_ge(z[i], m, rem);
+    rem = rem - t;
+    gz[i] = gate(z[i], t);
+  }
+}
+// max over the window's W frames of the pre-ReLU BatchNorm output, then the ReLU (relu is monotone: the same value as max of the relus)
+template <int W>
+__device__ __forceinline__ float4 bn_relu_window_max(const BnCoef& k, const float* p, int C) {
+  float4 m = bn_act(k, bn_xhat(k, ld4(p)));
+#pragma unroll
+  for (int i = 1; i < W; ++i) m = max4(m, bn_act(k, bn_xhat(k, ld4(p + (int64_t)i * C))));
+  return relu4(m);
 }
 
-// pool = 2: unit u = (clip b, pooled frame t2) reads rows b T + 2 t2 and + 1, writes row u of y [B (T / 2), C]; an odd T's last frame is not read.
+// pool = 2 / 4 (W): unit u = (clip b, pooled frame tw) reads rows b T + W tw ... + W - 1, writes row u of y [B (T / W), C]; the trailing T mod W
+// frames are not read.
+template <int W>
 __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const float* __restrict__ x, const float* mean, const float* var, const float* gamma,
-                                                              const float* beta, float eps, float* __restrict__ y, int U, int T, int T2, int C) {
+                                                              const float* beta, float eps, float* __restrict__ y, int U, int T, int TW, int C) {
   const int tx = threadIdx.x & (kCols - 1), ty = threadIdx.x / kCols;
   const int col = (blockIdx.x * kCols + tx) * 4;
   if (col >= C) return;
@@ -125,10 +147,8 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_kernel(const float* __res
   for (int j = 0; j < kPerLane; ++j) {
     const int u = u0 + kLanes * j;
     if (u >= U) break;
-    const int b = u / T2, t2 = u - b * T2;
-    const float* p = x + ((int64_t)b * T + 2 * t2) * C + col;
-    const float4 za = bn_act(k, bn_xhat(k, ld4(p))), zb = bn_act(k, bn_xhat(k, ld4(p + C)));
-    st4(y + (int64_t)u * C + col, relu4(max4(za, zb)));
+    const int b = u / TW, tw = u - b * TW;
+    st4(y + (int64_t)u * C + col, bn_relu_window_max<W>(k, x + ((int64_t)b * T + W * tw) * C + col, C));
   }
 }
 // pool = 0: y[b] = mean over the clip's T frames, added in frame order; unit = clip
@@ -144,13 +164,28 @@ __global__ __launch_bounds__(256) void bn_relu_avgpool_kernel(const float* __res
   for (int t = 0; t < T; ++t, p += C) s = s + relu4(bn_act(k, bn_xhat(k, ld4(p))));
   st4(y + (int64_t)b * C + col, s * (1.0f / (float)T));
 }
+// MaxPool1d(4) then the mean (AWT_POOL_MAX4_MEAN): y[b] = mean over the clip's TW = T / W pooled frames, added in frame order; unit = clip.  The
+// pooled tensor exists in registers only.
+template <int W>
+__global__ __launch_bounds__(256) void bn_relu_maxpool_mean_kernel(const float* __restrict__ x, const float* mean, const float* var, const float* gamma,
+                                                                   const float* beta, float eps, float* __restrict__ y, int B, int T, int TW, int C) {
+  const int tx = threadIdx.x & (kCols - 1), ty = threadIdx.x / kCols;
+  const int col = (blockIdx.x * kCols + tx) * 4;
+  const int b = blockIdx.y * kLanes + ty;
+  if (col >= C || b >= B) return;
+  const BnCoef k = bn_coef(mean, var, gamma, beta, eps, col);
+  const float* p = x + (int64_t)b * T * C + col;
+  float4 s = f4(0.f);
+  for (int tw = 0; tw < TW; ++tw, p += (int64_t)W * C) s = s + bn_relu_window_max<W>(k, p, C);
+  st4(y + (int64_t)b * C + col, s * (1.0f / (float)TW));
+}
 
 // Backward, launch 1: partial[slab][0][C] = sum dz, partial[slab][1][C] = sum dz xhat over the slab's units, dz the gradient at the BatchNorm
-// output.  POOL2: unit = a pooled frame (two rows of x, one of dy; the frame an odd T drops has dz = 0 and adds nothing); else unit = a row of x
-// with dz = relu'(z) dy[clip] / T.
-template <bool POOL2>
+// output.  W = 2 / 4: unit = a pooled frame (W rows of x; the frames that T mod W drops have dz = 0 and add nothing) whose gradient is row u of dy,
+// or with MEAN dy[clip] / TW; W = 0: unit = a row of x with dz = relu'(z) dy[clip] / T.
+template <int W, bool MEAN>
 __global__ __launch_bounds__(256) void bn_pool_bwd_reduce_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* mean, const float* var,
-                                                                 const float* gamma, const float* beta, float eps, int U, int T, int T2, int C,
+                                                                 const float* gamma, const float* beta, float eps, int U, int T, int TW, int C,
                                                                  float* __restrict__ partial) {
   __shared__ float4 s1[kLanes][kCols], s2[kLanes][kCols];
   const int tx = threadIdx.x & (kCols - 1), ty = threadIdx.x / kCols;
@@ -165,14 +200,22 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_reduce_kernel(const float* __
     for (int j = 0; j < kPerLane; ++j) {
       const int u = u0 + kLanes * j;
       if (u >= U) break;
-      if constexpr (POOL2) {
-        const int b = u / T2, t2 = u - b * T2;
-        const float* p = x + ((int64_t)b * T + 2 * t2) * C + col;
-        const float4 ha = bn_xhat(k, ld4(p)), hb = bn_xhat(k, ld4(p + C));
-        float4 ga, gb;
-        pool2_grad(bn_act(k, ha), bn_act(k, hb), ld4(dy + (int64_t)u * C + col), ga, gb);
-        a1 = a1 + ga + gb;
-        a2 = a2 + ga * ha + gb * hb;
+      if constexpr (W > 0) {
+        const int b = u / TW, tw = u - b * TW;
+        const float* p = x + ((int64_t)b * T + W * tw) * C + col;
+        float4 h[W], z[W], g[W];
+#pragma unroll
+        for (int i = 0; i < W; ++i) { h[i] = bn_xhat(k, ld4(p + (int64_t)i * C)); z[i] = bn_act(k, h[i]); }
+        float4 gy;
+        if constexpr (MEAN) gy = ld4(dy + (int64_t)b * C + col) * (1.0f / (float)TW); else gy = ld4(dy + (int64_t)u * C + col);
+        pool_grad<W>(z, gy, g);
+        if constexpr (W == 2) {
+          a1 = a1 + g[0] + g[1];
+          a2 = a2 + g[0] * h[0] + g[1] * h[1];
+        } else {
+          a1 = a1 + g[0] + g[1] + g[2] + g[3];
+          a2 = a2 + g[0] * h[0] + g[1] * h[1] + g[2] * h[2] + g[3] * h[3];
+        }
       } else {
         const float4 h = bn_xhat(k, ld4(x + (int64_t)u * C + col));
         const float4 g = gate(bn_act(k, h), ld4(dy + (int64_t)(u / T) * C + col) * inv_t);
@@ -199,36 +242,41 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_sum_kernel(const float* __res
   }
   st4(dbeta + col, a1); st4(dgamma + col, a2);
 }
-// Backward, launch 3: dx = gamma rstd (dz - dbeta / M - xhat dgamma / M) for EVERY row of x, M = B T.  POOL2: unit = (clip, frame pair p < ceil(T / 2));
-// the lone last frame of an odd T has dz = 0 but still receives the two mean terms.
-template <bool POOL2>
+// Backward, launch 3: dx = gamma rstd (dz - dbeta / M - xhat dgamma / M) for EVERY row of x, M = B T.  W = 2 / 4: unit = (clip, window p < ceil(T / W));
+// the frames of the incomplete last window have dz = 0 but still receive the two mean terms.
+template <int W, bool MEAN>
 __global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* mean, const float* var,
                                                                 const float* gamma, const float* beta, float eps, const float* dgamma, const float* dbeta,
-                                                                int U, int T, int T2, int C, float inv_m, float* __restrict__ dx) {
+                                                                int U, int T, int TW, int C, float inv_m, float* __restrict__ dx) {
   const int tx = threadIdx.x & (kCols - 1), ty = threadIdx.x / kCols;
   const int col = (blockIdx.x * kCols + tx) * 4;
   if (col >= C) return;
   const BnCoef k = bn_coef(mean, var, gamma, beta, eps, col);
   const float4 kb = ld4(dbeta + col) * inv_m, kg = ld4(dgamma + col) * inv_m, gr = k.gamma * k.rstd;
   const float inv_t = 1.0f / (float)T;
-  const int Tp = (T + 1) / 2;
   const int u0 = blockIdx.y * kSlab + ty;
 #pragma unroll 2
   for (int j = 0; j < kPerLane; ++j) {
     const int u = u0 + kLanes * j;
     if (u >= U) break;
-    if constexpr (POOL2) {
+    if constexpr (W > 0) {
+      const int Tp = (T + W - 1) / W;
       const int b = u / Tp, tp = u - b * Tp;
-      const int64_t row = (int64_t)b * T + 2 * tp;
-      const float4 ha = bn_xhat(k, ld4(x + row * C + col));
-      if (tp < T2) {
-        const float4 hb = bn_xhat(k, ld4(x + (row + 1) * C + col));
-        float4 ga, gb;
-        pool2_grad(bn_act(k, ha), bn_act(k, hb), ld4(dy + ((int64_t)b * T2 + tp) * C + col), ga, gb);
-        st4(dx + row * C + col, gr * (ga - kb - ha * kg));
-        st4(dx + (row + 1) * C + col, gr * (gb - kb - hb * kg));
+      const int64_t row = (int64_t)b * T + W * tp;
+      if (tp < TW) {
+        float4 h[W], z[W], g[W];
+#pragma unroll
+        for (int i = 0; i < W; ++i) { h[i] = bn_xhat(k, ld4(x + (row + i) * C + col)); z[i] = bn_act(k, h[i]); }
+        float4 gy;
+        if constexpr (MEAN) gy = ld4(dy + (int64_t)b * C + col) * (1.0f / (float)TW); else gy = ld4(dy + ((int64_t)b * TW + tp) * C + col);
+        pool_grad<W>(z, gy, g);
+#pragma unroll
+        for (int i = 0; i < W; ++i) st4(dx + (row + i) * C + col, gr * (g[i] - kb - h[i] * kg));
       } else {
-        st4(dx + row * C + col, gr * (f4(0.f) - kb - ha * kg));
+        for (int i = 0; W * tp + i < T; ++i) {
+          const float4 ha = bn_xhat(k, ld4(x + (row + i) * C + col));
+          st4(dx + (row + i) * C + col, gr * (f4(0.f) - kb - ha * kg));
+        }
       }
     } else {
       const float4 h = bn_xhat(k, ld4(x + (int64_t)u * C + col));
@@ -303,54 +351,172 @@ extern "C" int awt_op_batchnorm_stats(awt_ctx* c, const float* x, int M, int C, 
   return AWT_OK;
 }
 
+namespace {
+// pool codes (awt.h AWT_POOL_*): the window of the max-pool, 0 for none
+int pool_window(int pool) { return pool == AWT_POOL_MAX2 ? 2 : (pool == AWT_POOL_MAX4 || pool == AWT_POOL_MAX4_MEAN) ? 4 : 0; }
+bool pool_ok(int pool, int T) { return pool == AWT_POOL_MEAN || (pool_window(pool) > 0 && T >= pool_window(pool)); }
+}  // namespace
+
 extern "C" int awt_op_bn_relu_pool(awt_ctx* c, const float* x, const float* mean, const float* var, const float* gamma, const float* beta, float eps,
                                    float* y, int B, int T, int C, int pool, void* stream) {
   AWT_REQUIRE(C > 0 && C % 4 == 0, AWT_ERR_INVALID, "op_bn_relu_pool: C must be a positive multiple of 4");
-  AWT_REQUIRE(pool == 0 || (pool == 2 && T >= 2), AWT_ERR_INVALID, "op_bn_relu_pool: pool must be 2 (max over frame pairs, T >= 2) or 0 (mean over T)");
+  AWT_REQUIRE(pool_ok(pool, T), AWT_ERR_INVALID,
+              "op_bn_relu_pool: pool must be 0 (mean over T), 2 (max over frame pairs, T >= 2), 4 (max over 4 frames, T >= 4) or 5 (4, then the mean)");
   AWT_REQUIRE(c && x && mean && var && gamma && beta && y && shape_ok(B, T, C) && eps >= 0.f, AWT_ERR_INVALID, "op_bn_relu_pool: null or empty argument");
   AWT_REQUIRE(aligned16({x, mean, var, gamma, beta, y}), AWT_ERR_INVALID, "op_bn_relu_pool: tensors must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int gx = (C / 4 + kCols - 1) / kCols;
-  if (pool == 2) {
-    const int T2 = T / 2, U = B * T2;
-    hipLaunchKernelGGL(bn_relu_maxpool_kernel, dim3(gx, slabs(U)), dim3(256), 0, s, x, mean, var, gamma, beta, eps, y, U, T, T2, C);
+  if (pool == AWT_POOL_MAX2 || pool == AWT_POOL_MAX4) {
+    const int TW = T / pool_window(pool), U = B * TW;
+    if (pool == AWT_POOL_MAX2) hipLaunchKernelGGL(bn_relu_maxpool_kernel<2>, dim3(gx, slabs(U)), dim3(256), 0, s, x, mean, var, gamma, beta, eps, y, U, T, TW, C);
+    else hipLaunchKernelGGL(bn_relu_maxpool_kernel<4>, dim3(gx, slabs(U)), dim3(256), 0, s, x, mean, var, gamma, beta, eps, y, U, T, TW, C);
   } else {
     AWT_REQUIRE((B + kLanes - 1) / kLanes <= 65535, AWT_ERR_INVALID, "op_bn_relu_pool: too many clips");
-    hipLaunchKernelGGL(bn_relu_avgpool_kernel, dim3(gx, (B + kLanes - 1) / kLanes), dim3(256), 0, s, x, mean, var, gamma, beta, eps, y, B, T, C);
+    const dim3 grid(gx, (B + kLanes - 1) / kLanes);
+    if (pool == AWT_POOL_MEAN) hipLaunchKernelGGL(bn_relu_avgpool_kernel, grid, dim3(256), 0, s, x, mean, var, gamma, beta, eps, y, B, T, C);
+    else hipLaunchKernelGGL(bn_relu_maxpool_mean_kernel<4>, grid, dim3(256), 0, s, x, mean, var, gamma, beta, eps, y, B, T, T / 4, C);
   }
   AWT_HIP_CHECK(hipGetLastError());
   return AWT_OK;
 }
 
 extern "C" size_t awt_op_bn_relu_pool_backward_workspace_bytes(int B, int T, int C) {
-  return (B <= 0 || T <= 0 || C <= 0) ? 0 : partial_bytes((int64_t)B * T, C);       // covers both poolings (pool = 2 has half the units)
+  return (B <= 0 || T <= 0 || C <= 0) ? 0 : partial_bytes((int64_t)B * T, C);       // covers every pooling (the max-pools have fewer units)
 }
+namespace {
+template <int W, bool MEAN>
+void launch_pool_backward(hipStream_t s, const float* dy, const float* x, const float* mean, const float* var, const float* gamma, const float* beta, float eps,
+                          float* dx, float* dgamma, float* dbeta, int B, int T, int C, float* partial) {
+  const int gx = (C / 4 + kCols - 1) / kCols, gsum = (C / 4 + 255) / 256;
+  const int TW = W > 0 ? T / (W > 0 ? W : 1) : T / 2;
+  const int Ur = W > 0 ? B * TW : B * T, Ua = W > 0 ? B * ((T + W - 1) / (W > 0 ? W : 1)) : B * T;
+  const float inv_m = 1.0f / ((float)B * (float)T);
+  hipLaunchKernelGGL((bn_pool_bwd_reduce_kernel<W, MEAN>), dim3(gx, slabs(Ur)), dim3(256), 0, s, dy, x, mean, var, gamma, beta, eps, Ur, T, TW, C, partial);
+  hipLaunchKernelGGL(bn_pool_bwd_sum_kernel, dim3(gsum), dim3(256), 0, s, (const float*)partial, slabs(Ur), C, dgamma, dbeta);
+  hipLaunchKernelGGL((bn_pool_bwd_apply_kernel<W, MEAN>), dim3(gx, slabs(Ua)), dim3(256), 0, s, dy, x, mean, var, gamma, beta, eps, (const float*)dgamma,
+                     (const float*)dbeta, Ua, T, TW, C, inv_m, dx);
+}
+}  // namespace
 extern "C" int awt_op_bn_relu_pool_backward(awt_ctx* c, const float* dy, const float* x, const float* mean, const float* var, const float* gamma,
                                             const float* beta, float eps, float* dx, float* dgamma, float* dbeta, int B, int T, int C, int pool,
                                             void* workspace, size_t ws_bytes, void* stream) {
   AWT_REQUIRE(C > 0 && C % 4 == 0, AWT_ERR_INVALID, "op_bn_relu_pool_backward: C must be a positive multiple of 4");
-  AWT_REQUIRE(pool == 0 || (pool == 2 && T >= 2), AWT_ERR_INVALID, "op_bn_relu_pool_backward: pool must be 2 (T >= 2) or 0");
+  AWT_REQUIRE(pool_ok(pool, T), AWT_ERR_INVALID, "op_bn_relu_pool_backward: pool must be 0, 2 (T >= 2), 4 or 5 (T >= 4)");
   AWT_REQUIRE(c && dy && x && mean && var && gamma && beta && dx && dgamma && dbeta && workspace && shape_ok(B, T, C) && eps >= 0.f, AWT_ERR_INVALID,
               "op_bn_relu_pool_backward: null or empty argument");
   AWT_REQUIRE(aligned16({dy, x, mean, var, gamma, beta, dx, dgamma, dbeta, workspace}), AWT_ERR_INVALID, "op_bn_relu_pool_backward: tensors must be 16-byte aligned");
   AWT_REQUIRE(ws_bytes >= awt_op_bn_relu_pool_backward_workspace_bytes(B, T, C), AWT_ERR_WORKSPACE, "op_bn_relu_pool_backward: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int gx = (C / 4 + kCols - 1) / kCols, gsum = (C / 4 + 255) / 256, T2 = T / 2;
-  const float inv_m = 1.0f / ((float)B * (float)T);
   float* partial = (float*)workspace;
-  if (pool == 2) {
-    const int Ur = B * T2, Ua = B * ((T + 1) / 2);
-    hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel<true>, dim3(gx, slabs(Ur)), dim3(256), 0, s, dy, x, mean, var, gamma, beta, eps, Ur, T, T2, C, partial);
-    hipLaunchKernelGGL(bn_pool_bwd_sum_kernel, dim3(gsum), dim3(256), 0, s, (const float*)partial, slabs(Ur), C, dgamma, dbeta);
-    hipLaunchKernelGGL(bn_pool_bwd_apply_kernel<true>, dim3(gx, slabs(Ua)), dim3(256), 0, s, dy, x, mean, var, gamma, beta, eps, (const float*)dgamma,
-                       (const float*)dbeta, Ua, T, T2, C, inv_m, dx);
-  } else {
-    const int U = B * T;
-    hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel<false>, dim3(gx, slabs(U)), dim3(256), 0, s, dy, x, mean, var, gamma, beta, eps, U, T, T2, C, partial);
-    hipLaunchKernelGGL(bn_pool_bwd_sum_kernel, dim3(gsum), dim3(256), 0, s, (const float*)partial, slabs(U), C, dgamma, dbeta);
-    hipLaunchKernelGGL(bn_pool_bwd_apply_kernel<false>, dim3(gx, slabs(U)), dim3(256), 0, s, dy, x, mean, var, gamma, beta, eps, (const float*)dgamma,
-                       (const float*)dbeta, U, T, T2, C, inv_m, dx);
-  }
+  if (pool == AWT_POOL_MAX2) launch_pool_backward<2, false>(s, dy, x, mean, var, gamma, beta, eps, dx, dgamma, dbeta, B, T, C, partial);
+  else if (pool == AWT_POOL_MAX4) launch_pool_backward<4, false>(s, dy, x, mean, var, gamma, beta, eps, dx, dgamma, dbeta, B, T, C, partial);
+  else if (pool == AWT_POOL_MAX4_MEAN) launch_pool_backward<4, true>(s, dy, x, mean, var, gamma, beta, eps, dx, dgamma, dbeta, B, T, C, partial);
+  else launch_pool_backward<0, false>(s, dy, x, mean, var, gamma, beta, eps, dx, dgamma, dbeta, B, T, C, partial);
   AWT_HIP_CHECK(hipGetLastError());
   return AWT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ framed Conv1d(1, Cout, kernel, stride) on the raw waveform
+// DESIGN section 4.10.  y[b, t, co] = bias[co] + sum_k x[b, t stride + k] w[co, k] as a GEMM of frames x taps on the exact-fp32 MFMA
+// (v_mfma_f32_16x16x4_f32: a k-ordered fmaf chain that starts at the bias).  A workgroup of 4 waves owns kFramedRows consecutive frames of one
+// clip and stages, once, the samples they cover and the whole weight in LDS:
+//   samples  as rows of `stride` floats at a pitch of stride + 4: frame f, tap k = j stride + r  is  sx[(f + j) (stride + 4) + r].  The MFMA's B operand
+//            is lane (frame l & 15, k = 4 step + (l >> 4)); with pitch / 4 odd (stride % 8 == 0) the 16 frames start on the 16 different multiples
+//            of 4 banks and the 4 k fill them: 64 lanes, 64 banks.  At the natural pitch (stride = 16) frames 0, 4, 8, 12 would share a bank.
+//   weights  [Cout][kernel + 4]: the A operand is lane (channel l & 15, k = 4 step + (l >> 4)), conflict-free for the same reason.
+// A = weights, B = frames puts 4 consecutive channels of ONE frame in a lane's accumulator (D row = channel 4 (l >> 4) + reg, column = frame): a
+// float4 store per lane, 64 contiguous bytes per frame and channel tile.  A wave owns 2 frame tiles x CT channel tiles = 2 CT independent accumulators.
+namespace {
+constexpr int kFramedRows = 128;          // output frames per workgroup (waveform_classifier.FRAMED_ROWS_PER_WORKGROUP)
+constexpr int kFramedLds = 64 * 1024;     // the staging may take this much LDS
+
+size_t framed_lds_bytes(int kernel, int stride, int Cout) {
+  return ((size_t)(kFramedRows + kernel / stride - 1) * (stride + 4) + (size_t)Cout * (kernel + 4)) * 4;
+}
+
+template <int CT>
+__global__ __launch_bounds__(256) void conv1d_framed_kernel(const float* __restrict__ x, int64_t x_pitch, const float* __restrict__ w, const float* __restrict__ bias,
+                                                            float* __restrict__ y, int T1, int kernel, int stride, int Cout) {
+  extern __shared__ float4 framed_lds[];
+  const int taps = kernel / stride, P = stride + 4, WP = kernel + 4;
+  float* sx = reinterpret_cast<float*>(framed_lds);
+  float* sw = sx + (kFramedRows + taps - 1) * P;
+  const int b = blockIdx.y, f0 = blockIdx.x * kFramedRows, rows = min(kFramedRows, T1 - f0);
+  const float* xs = x + (int64_t)b * x_pitch + (int64_t)f0 * stride;
+  const int n_valid = stride * (rows - 1) + kernel;            // the samples this tile's frames cover: all inside the clip; a multiple of 4
+  for (int p = 4 * threadIdx.x; p < (kFramedRows + taps - 1) * stride; p += 4 * 256) {
+    const int r = p / stride, col = p - r * stride;
+    st4(sx + r * P + col, p < n_valid ? ld4(xs + p) : f4(0.f));
+  }
+  for (int p = 4 * threadIdx.x; p < Cout * kernel; p += 4 * 256) {
+    const int co = p / kernel, k = p - co * kernel;
+    st4(sw + co * WP + k, ld4(w + p));
+  }
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
+  const int fw = wave * 32;                                    // this wave's frames: fw + 16 ft + j
+  if (fw >= rows) return;
+  const float* bx = sx + (fw + j) * P + g;
+  for (int co0 = 0; co0 < Cout; co0 += 16 * CT) {
+    f32x4 acc[2][CT];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+      const float4 bv = ld4(bias + co0 + 16 * ct + 4 * g);
+      acc[0][ct] = acc[1][ct] = f32x4{bv.x, bv.y, bv.z, bv.w};
+    }
+    const float* aw = sw + (co0 + j) * WP + g;
+    auto k_step = [&](int k, int xo) {                            // taps k ... k + 3: 2 + CT LDS reads, 2 CT MFMAs
+      const float b0 = bx[xo], b1 = bx[16 * P + xo];
+      float a[CT];
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) a[ct] = aw[16 * ct * WP + k];
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        acc[0][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ct], b0, acc[0][ct], 0, 0, 0);
+        acc[1][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ct], b1, acc[1][ct], 0, 0, 0);
+      }
+    };
+    for (int tap = 0; tap < taps; ++tap)
+      for (int c0 = 0; c0 < stride; c0 += 8) {                    // stride % 8 == 0: two k-steps per trip, in k order
+        k_step(tap * stride + c0, tap * P + c0);
+        k_step(tap * stride + c0 + 4, tap * P + c0 + 4);
+      }
+#pragma unroll
+    for (int ft = 0; ft < 2; ++ft) {
+      const int f = fw + 16 * ft + j;
+      if (f >= rows) continue;
+      float* yo = y + ((int64_t)b * T1 + f0 + f) * Cout + co0 + 4 * g;
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) st4(yo + 16 * ct, make_float4(acc[ft][ct][0], acc[ft][ct][1], acc[ft][ct][2], acc[ft][ct][3]));
+    }
+  }
+}
+// the LDS attribute is set once per device to the LARGEST size a call may ask for: the size of a call depends on (kernel, stride, Cout)
+template <auto Kernel, class... Args>
+int launch_framed(dim3 grid, int lds, hipStream_t s, const Args&... args) {
+  AWT_ONCE_PER_DEVICE(AWT_HIP_CHECK(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kFramedLds)));
+  hipLaunchKernelGGL(Kernel, grid, dim3(256), lds, s, args...);
+  AWT_HIP_CHECK(hipGetLastError());
+  return AWT_OK;
+}
+}  // namespace
+
+extern "C" int awt_op_conv1d_framed(awt_ctx* c, const float* x, int64_t x_pitch, const float* w, const float* bias, float* y, int B, int n_samples,
+                                    int kernel, int stride, int Cout, void* stream) {
+  AWT_REQUIRE(stride > 0 && stride % 8 == 0, AWT_ERR_INVALID, "op_conv1d_framed: stride must be a positive multiple of 8");
+  AWT_REQUIRE(kernel > 0 && kernel % stride == 0, AWT_ERR_INVALID, "op_conv1d_framed: kernel must be a positive multiple of the stride");
+  AWT_REQUIRE(n_samples >= kernel, AWT_ERR_INVALID, "op_conv1d_framed: n_samples must be at least kernel (no padding)");
+  AWT_REQUIRE(Cout > 0 && Cout % 16 == 0 && framed_lds_bytes(kernel, stride, Cout) <= (size_t)kFramedLds, AWT_ERR_INVALID,
+              "op_conv1d_framed: Cout must be a positive multiple of 16, and weights and staged samples must fit 64 KiB of LDS");
+  AWT_REQUIRE(c && x && w && bias && y, AWT_ERR_INVALID, "op_conv1d_framed: null argument");
+  AWT_REQUIRE(B > 0 && B <= 65535 && x_pitch >= n_samples && x_pitch % 4 == 0, AWT_ERR_INVALID,
+              "op_conv1d_framed: 1 <= B <= 65535 and a clip pitch >= n_samples that is a multiple of 4 required");
+  AWT_REQUIRE(aligned16({x, w, bias, y}), AWT_ERR_INVALID, "op_conv1d_framed: tensors must be 16-byte aligned");
+  const int T1 = (n_samples - kernel) / stride + 1;
+  const dim3 grid((T1 + kFramedRows - 1) / kFramedRows, B);
+  const int lds = (int)framed_lds_bytes(kernel, stride, Cout);
+  hipStream_t s = (hipStream_t)stream;
+  if (Cout % 64 == 0) return launch_framed<conv1d_framed_kernel<4>>(grid, lds, s, x, x_pitch, w, bias, y, T1, kernel, stride, Cout);
+  if (Cout % 32 == 0) return launch_framed<conv1d_framed_kernel<2>>(grid, lds, s, x, x_pitch, w, bias, y, T1, kernel, stride, Cout);
+  return launch_framed<conv1d_framed_kernel<1>>(grid, lds, s, x, x_pitch, w, bias, y, T1, kernel, stride, Cout);
 }
