@@ -17,17 +17,6 @@
 
 namespace {
 
-__device__ __forceinline__ float al_wave_max(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-  return x;
-}
-__device__ __forceinline__ float al_wave_sum(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-
 // ------------------------------------------------------------------------------------------------ probabilities of the alignment heads
 constexpr int kAwRows = 8;          // token rows per workgroup
 constexpr int kAwMaxS = 1536;       // encoder positions whose scores fit the workgroup's LDS
@@ -92,10 +81,10 @@ __global__ __launch_bounds__(256) void align_weights_kernel(AlignW a) {
   for (int i = wave; i < nq; i += 4) {
     float m = -3.0e38f;
     for (int j = lane; j < a.S; j += 64) m = fmaxf(m, sc[i][j]);
-    m = al_wave_max(m);
+    m = wave_max(m);
     float l = 0.f;
     for (int j = lane; j < a.S; j += 64) { const float e = __expf(sc[i][j] - m); sc[i][j] = e; l += e; }
-    l = al_wave_sum(l);
+    l = wave_sum(l);
     float* o = a.out + (((int64_t)clip * a.n_sel + hsel) * a.T + i0 + i) * a.frames;
     for (int j = lane; j < a.frames; j += 64) o[j] = sc[i][j] / l;
   }

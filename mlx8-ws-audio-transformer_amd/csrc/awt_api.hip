@@ -222,8 +222,6 @@ struct Layer {
 
 // conv1 as a GEMM: K = 3 taps x n_mels, zero-padded to a multiple of 64 (80 mels: 256, 128 mels: 384)
 int conv1_k(int n_mels) { return (3 * n_mels + 63) / 64 * 64; }
-constexpr size_t kAlign = 256;
-size_t align_up(size_t x) { return (x + kAlign - 1) & ~(kAlign - 1); }
 
 }  // namespace
 
@@ -310,21 +308,20 @@ Workspace carve(const awt_encoder* e, char* base, int Bc) {
   const size_t P = e->planes, S = c.n_ctx, T = 2 * S, d = c.d_model, f = c.ffn_dim;
   const size_t M = (size_t)Bc * S, Mt = (size_t)Bc * T;
   Workspace w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes); return p; };
-  w.x = (float*)take(M * d * 4);
-  for (size_t p = 0; p < P; ++p) w.ln[p] = (bf16_t*)take(M * d * 2);
-  for (size_t p = 0; p < P; ++p) w.u[p] = (bf16_t*)take(M * 128 * 2);
+  Carver cv(base);
+  w.x = cv.take<float>(M * d * 4);
+  for (size_t p = 0; p < P; ++p) w.ln[p] = cv.take<bf16_t>(M * d * 2);
+  for (size_t p = 0; p < P; ++p) w.u[p] = cv.take<bf16_t>(M * 128 * 2);
   // layer-phase buffers; the conv-phase buffers (im2col rows and conv1 output) alias the same region
-  const size_t layer_start = off;
-  for (size_t p = 0; p < P; ++p) w.qkv[p] = (bf16_t*)take(3 * M * d * 2);
-  for (size_t p = 0; p < P; ++p) w.att[p] = (bf16_t*)take(M * d * 2);
-  for (size_t p = 0; p < P; ++p) w.ff[p] = (bf16_t*)take(M * f * 2);
-  const size_t layer_end = off;
-  off = layer_start;
-  for (size_t p = 0; p < P; ++p) w.a1[p] = (bf16_t*)take(Mt * conv1_k(c.n_mels) * 2);
-  for (size_t p = 0; p < P; ++p) w.h1[p] = (bf16_t*)take(Mt * d * 2);
-  w.bytes = std::max(off, layer_end);
+  const size_t layer_start = cv.off;
+  for (size_t p = 0; p < P; ++p) w.qkv[p] = cv.take<bf16_t>(3 * M * d * 2);
+  for (size_t p = 0; p < P; ++p) w.att[p] = cv.take<bf16_t>(M * d * 2);
+  for (size_t p = 0; p < P; ++p) w.ff[p] = cv.take<bf16_t>(M * f * 2);
+  const size_t layer_end = cv.off;
+  cv.off = layer_start;
+  for (size_t p = 0; p < P; ++p) w.a1[p] = cv.take<bf16_t>(Mt * conv1_k(c.n_mels) * 2);
+  for (size_t p = 0; p < P; ++p) w.h1[p] = cv.take<bf16_t>(Mt * d * 2);
+  w.bytes = std::max(cv.off, layer_end);
   // the ping-pong GEMM reads whole 256-row panels of its activation: up to 255 rows past the last buffer's end (never stored)
   if (e->prec == PREC_F16F8 && !c.training) w.bytes += align_up((size_t)256 * std::max(f, (size_t)conv1_k(c.n_mels)) * 4);
   return w;
@@ -351,11 +348,8 @@ void set_out(GemmOut& o, const Act& a) { o.hi = a.p16; o.lo = a.lo16; o.hi8 = a.
 Act make_ilv(bf16_t* p0) { Act a; a.ilv = (char*)p0; return a; }
 
 GemmSeg seg_plain(const Act& a, int64_t lda, const Planes& w, int64_t wcol, int K, int M) {
-  GemmSeg s{};
-  s.a_hi = a.p16; s.a_lo = a.lo16; s.a8 = a.hi8; s.al8 = a.lo8; s.lda = lda;
-  s.w_hi = w.hi; s.w_lo = w.lo; s.w8 = (const uint8_t*)w.lo; s.wl8 = w.x8;
-  s.w_ksteps = (int)(w.ld / 32); s.w_k0 = (int)(wcol / 32); s.K = K;
-  s.rows_out = M; s.rows_in = M; s.row_mul = 1; s.row_add = 0;
+  GemmSeg s = gemm_seg_plain(a.p16, a.lo16, lda, w.hi, w.lo, (int)(w.ld / 32), (int)(wcol / 32), K, M);
+  s.a8 = a.hi8; s.al8 = a.lo8; s.w8 = (const uint8_t*)w.lo; s.wl8 = w.x8;
   s.w_exact16 = w.exact16 ? 1 : 0;
   s.a_ilv = a.ilv; s.w_pp = w.pp;
   s.ws16 = w.s16; s.ws8 = w.s8; s.ws_rows = (int)w.s_rows;
@@ -434,16 +428,15 @@ TrainWs carve_train(const awt_encoder* e, char* base, int B) {
   const size_t P = e->planes, S = c.n_ctx, T = 2 * S, d = c.d_model, f = c.ffn_dim, H = c.n_heads;
   const size_t M = (size_t)B * S, Mt = (size_t)B * T;
   TrainWs w{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes); return p; };
-  auto planes = [&](bf16_t* (&dst)[2], size_t elems) { dst[0] = dst[1] = nullptr; for (size_t p = 0; p < P; ++p) dst[p] = (bf16_t*)take(elems * 2); };
+  Carver cv(base);
+  auto planes = [&](bf16_t* (&dst)[2], size_t elems) { dst[0] = dst[1] = nullptr; for (size_t p = 0; p < P; ++p) dst[p] = cv.take<bf16_t>(elems * 2); };
   w.layer.resize(c.n_layers);
-  float* x = (float*)take(M * d * 4);
+  float* x = cv.take<float>(M * d * 4);
   for (int li = 0; li < c.n_layers; ++li) {
     LayerBufs& L = w.layer[li];
     L.x_in = x;
-    L.x_mid = (float*)take(M * d * 4);
-    L.x_out = (float*)take(M * d * 4);
+    L.x_mid = cv.take<float>(M * d * 4);
+    L.x_out = cv.take<float>(M * d * 4);
     x = L.x_out;
     planes(L.ln1, M * d); planes(L.qkv, 3 * M * d); planes(L.att, M * d); planes(L.ln2, M * d); planes(L.pre, M * f);
     planes(L.u, M * 128);
@@ -452,7 +445,7 @@ TrainWs carve_train(const awt_encoder* e, char* base, int B) {
     if (has_1) planes(L.u1, M * 128); else { L.u1[0] = L.u[0]; L.u1[1] = L.u[1]; }
     if (has_2) { planes(L.u2, M * 128); planes(L.ff, M * f); } else { L.u2[0] = L.u[0]; L.u2[1] = L.u[1]; L.ff[0] = L.ff[1] = nullptr; }
     if (e->train_base) planes(L.ff, M * f);   // fc2's weight gradient contracts d(x_out) with the fc2 input of this layer
-    L.lse = (float*)take((size_t)B * H * S * 4);
+    L.lse = cv.take<float>((size_t)B * H * S * 4);
   }
   w.x_final = x;
   if (e->train_base) w.ff[0] = w.ff[1] = nullptr;   // every layer keeps its own fc2 input in this mode
@@ -460,12 +453,12 @@ TrainWs carve_train(const awt_encoder* e, char* base, int B) {
   // conv-phase scratch aliases the backward scratch (disjoint in time); train_base: the conv stem's backward reads it, so it is kept
   w.pre1[0] = w.pre1[1] = nullptr;
   if (e->train_base) { planes(w.a1, Mt * conv1_k(e->cfg.n_mels)); planes(w.h1, Mt * d); planes(w.pre1, Mt * d); }
-  const size_t mark = off;
+  const size_t mark = cv.off;
   if (!e->train_base) { planes(w.a1, Mt * conv1_k(e->cfg.n_mels)); planes(w.h1, Mt * d); }
-  const size_t conv_end = off;
-  off = mark;
-  w.dx_a = (float*)take(M * d * 4); w.dx_b = (float*)take(M * d * 4); w.dln = (float*)take(M * d * 4);
-  w.delta = (float*)take((size_t)B * H * S * 4);
+  const size_t conv_end = cv.off;
+  cv.off = mark;
+  w.dx_a = cv.take<float>(M * d * 4); w.dx_b = cv.take<float>(M * d * 4); w.dln = cv.take<float>(M * d * 4);
+  w.delta = cv.take<float>((size_t)B * H * S * 4);
   planes(w.dxp, M * d); planes(w.dpre, M * f); planes(w.datt, M * d); planes(w.dqkv, 3 * M * d); planes(w.du, M * 128);
   w.partial_bytes = outer_reduce_partial_bytes((int)M, c.lora_rank > 0 ? c.lora_rank : 1, 1024);   // Y blocks are reduced in chunks of <= 1024 columns
   if (e->train_base) {   // slab partials of the weight-gradient GEMMs (qkv, out_proj, fc1, fc2, a conv2 tap, a conv1 tap) and of the bias / LayerNorm reductions
@@ -474,8 +467,8 @@ TrainWs carve_train(const awt_encoder* e, char* base, int B) {
                           wgrad_partial_bytes(Mti, di, c.n_mels), param_grad_partial_bytes(Mti, di)});
     w.partial_bytes = std::max(w.partial_bytes, pb);
   }
-  w.partial = (float*)take(w.partial_bytes);
-  w.bytes = std::max(off, conv_end);
+  w.partial = cv.take<float>(w.partial_bytes);
+  w.bytes = std::max(cv.off, conv_end);
   for (int li = 0; li < c.n_layers; ++li) for (int p = 0; p < 2; ++p) if (!w.layer[li].ff[p]) w.layer[li].ff[p] = w.ff[p];   // kept per layer only under an fc2 adapter
   return w;
 }
@@ -586,13 +579,12 @@ int forward_chunk(awt_encoder* e, const float* mel, int Bc, float* hidden, char*
     // alias; a shape whose region has no room for g beside the shorter planes (none of Whisper's) keeps the full stem
     char* const base = (char*)w.a1[0];
     const size_t room = (size_t)(ws_base + w.bytes - base), Mt = (size_t)Bc * 2 * Sc;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base + off; off += align_up(bytes); return p; };
+    Carver cv(base);
     bf16_t *ca1[2] = {nullptr, nullptr}, *ch1[2] = {nullptr, nullptr};
-    for (int p = 0; p < e->planes; ++p) ca1[p] = (bf16_t*)take(Mt * conv1_k(c.n_mels) * 2);
-    for (int p = 0; p < e->planes; ++p) ch1[p] = (bf16_t*)take(Mt * d * 2);
-    float* cg = (float*)take((size_t)Bc * Sc * d * 4);
-    if (off <= room) { g = cg; for (int p = 0; p < 2; ++p) { a1[p] = ca1[p]; h1[p] = ch1[p]; } }
+    for (int p = 0; p < e->planes; ++p) ca1[p] = cv.take<bf16_t>(Mt * conv1_k(c.n_mels) * 2);
+    for (int p = 0; p < e->planes; ++p) ch1[p] = cv.take<bf16_t>(Mt * d * 2);
+    float* cg = cv.take<float>((size_t)Bc * Sc * d * 4);
+    if (cv.bytes() <= room) { g = cg; for (int p = 0; p < 2; ++p) { a1[p] = ca1[p]; h1[p] = ch1[p]; } }
   }
   int rc = conv_stem(e, mel, Bc, a1, h1, w.x, s, nullptr, g ? Sc : 0, g); if (rc) return rc;
   LayerBufs b{};
@@ -897,10 +889,17 @@ extern "C" int awt_encoder_forward(awt_encoder* e, const float* mel, int B, int 
   return AWT_OK;
 }
 
+namespace {
+// awt_audio_encode's workspace for chunks of Bc clips: the encoder's own (carve), one chunk's mel features, the log-mel workspace
+struct AudioEncodeWs { char* enc; float* mel; void* logmel; size_t bytes; };
+AudioEncodeWs audio_encode_layout(const awt_encoder* e, void* base, int Bc) {
+  Carver cv(base);
+  return {cv.take(carve(e, nullptr, Bc).bytes), cv.take<float>((size_t)Bc * e->cfg.n_mels * 2 * e->cfg.n_ctx * 4), cv.take(awt_logmel_workspace_bytes(Bc)), cv.bytes()};
+}
+}  // namespace
 extern "C" size_t awt_audio_encode_workspace_bytes(const awt_encoder* e, int B) {
   if (!e || B <= 0) return 0;
-  const int Bc = std::min(B, e->chunk);
-  return carve(e, nullptr, Bc).bytes + align_up((size_t)Bc * e->cfg.n_mels * 2 * e->cfg.n_ctx * 4) + awt_logmel_workspace_bytes(Bc);
+  return audio_encode_layout(e, nullptr, std::min(B, e->chunk)).bytes;
 }
 
 extern "C" int awt_audio_encode(awt_encoder* e, const void* pcm, int pcm_is_i16, int64_t pcm_stride, const int32_t* n_valid,
@@ -916,18 +915,15 @@ extern "C" int awt_audio_encode(awt_encoder* e, const void* pcm, int pcm_is_i16,
   const int chunk = std::min(B, e->chunk);
   // log-mel pads every clip with one constant from its last live frame on; the conv stem computes the positions that see live frames (plus two) and copies the rest
   const int Sc = g_conv_live ? conv_stem_positions(e->cfg.n_ctx, max_valid) : 0;
-  char* base = (char*)workspace;
-  const size_t enc_bytes = carve(e, nullptr, chunk).bytes;
-  float* mel_buf = (float*)(base + enc_bytes);
-  void* lm_ws = base + enc_bytes + align_up((size_t)chunk * e->cfg.n_mels * T * 4);
+  const AudioEncodeWs w = audio_encode_layout(e, workspace, chunk);
   const size_t esz = pcm_is_i16 ? 2 : 4;
   for (int b0 = 0; b0 < B; b0 += chunk) {
     const int Bc = std::min(chunk, B - b0);
-    float* mel = features_out ? features_out + (size_t)b0 * e->cfg.n_mels * T : mel_buf;
+    float* mel = features_out ? features_out + (size_t)b0 * e->cfg.n_mels * T : w.mel;
     rc = logmel_whisper_impl(e->ctx, (const char*)pcm + (size_t)b0 * pcm_stride * esz, pcm_is_i16, pcm_stride,
-                             n_valid ? n_valid + b0 : nullptr, max_valid, Bc, T, e->cfg.n_mels, mel, lm_ws, awt_logmel_workspace_bytes(Bc), s);
+                             n_valid ? n_valid + b0 : nullptr, max_valid, Bc, T, e->cfg.n_mels, mel, w.logmel, awt_logmel_workspace_bytes(Bc), s);
     if (rc) return rc;
-    rc = forward_chunk(e, mel, Bc, hidden + (size_t)b0 * e->cfg.n_ctx * e->cfg.d_model, base, s, Sc);
+    rc = forward_chunk(e, mel, Bc, hidden + (size_t)b0 * e->cfg.n_ctx * e->cfg.d_model, w.enc, s, Sc);
     if (rc) return rc;
   }
   return AWT_OK;
@@ -936,10 +932,29 @@ extern "C" int awt_audio_encode(awt_encoder* e, const void* pcm, int pcm_is_i16,
 extern "C" int awt_conv_stem_positions(int n_ctx, int max_valid) { return conv_stem_positions(n_ctx, max_valid); }
 
 // ------------------------------------------------------------------------------------------------ single operators
-extern "C" size_t awt_op_linear_workspace_bytes(int M, int N, int K) {
-  const size_t npad = ((size_t)N + 255) / 256 * 256;      // the 16-row w copies cover whole 256-column tiles
-  return 2 * align_up((size_t)M * K * 2) + 2 * align_up((size_t)N * K * 2) + 256 + 2 * align_up(npad * K * 2);     // x planes, w planes, a flag word (fp16-exact weights), the 16-row w copies (f16f8)
+namespace {
+// awt_op_linear's workspace: the x and w operand planes, a flag word ("a weight is not fp16-exact"), the 16-row w copies (f16f8); the ping-pong form
+// (tuning knob "gemm_pp" = 2) reads the same bytes as x in split lines over the two x planes and the packed weight image over the two w planes
+struct OpLinearWs {
+  PlanePair x, w; int* flag; bf16_t* s16; uint8_t* s8; size_t s_bytes, bytes;     // s_bytes: both copies, from s16 on
+  char* x_ilv() const { return (char*)x.hi; }
+  char* w_pp() const { return (char*)w.hi; }
+};
+OpLinearWs op_linear_layout(void* base, int M, int N, int K) {
+  const size_t sb = ((size_t)N + 255) / 256 * 256 * K * 2;      // the 16-row w copies cover whole 256-column tiles
+  Carver cv(base);
+  return {take_planes(cv, (size_t)M * K), take_planes(cv, (size_t)N * K), cv.take<int>(256), cv.take<bf16_t>(sb), cv.take<uint8_t>(sb), 2 * align_up(sb), cv.bytes()};
 }
+// awt_op_attention's workspace: the two 2-byte planes of q, of k and of v
+struct OpAttentionWs { PlanePair q, k, v; size_t bytes; };
+OpAttentionWs op_attention_layout(void* base, int B, int H, int S) {
+  const size_t n = (size_t)B * H * S * 64;
+  Carver cv(base);
+  return {take_planes(cv, n), take_planes(cv, n), take_planes(cv, n), cv.bytes()};
+}
+}  // namespace
+
+extern "C" size_t awt_op_linear_workspace_bytes(int M, int N, int K) { return op_linear_layout(nullptr, M, N, K).bytes; }
 extern "C" int awt_op_linear(awt_ctx* c, const float* x, const float* w, const float* bias, float* y, int M, int N, int K,
                              int terms, void* workspace, size_t ws_bytes, void* stream) {
   AWT_REQUIRE(prec_known(terms), AWT_ERR_INVALID, "op_linear: terms must be 1 (bf16), 2 (fp16), 3 (bf16x3), 4 (fp16x3) or 5 (f16f8)");
@@ -947,43 +962,38 @@ extern "C" int awt_op_linear(awt_ctx* c, const float* x, const float* w, const f
   AWT_REQUIRE(M > 0 && N > 0 && N % 128 == 0 && K > 0 && K % 64 == 0, AWT_ERR_INVALID, "op_linear: N % 128 == 0 and K % 64 == 0 required");
   AWT_REQUIRE(ws_bytes >= awt_op_linear_workspace_bytes(M, N, K), AWT_ERR_WORKSPACE, "op_linear: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)workspace;
-  bf16_t* xh = (bf16_t*)base;                 base += align_up((size_t)M * K * 2);
-  bf16_t* xl = (bf16_t*)base;                 base += align_up((size_t)M * K * 2);
-  bf16_t* wh = (bf16_t*)base;                 base += align_up((size_t)N * K * 2);
-  bf16_t* wl = (bf16_t*)base;
+  const OpLinearWs ws = op_linear_layout(workspace, M, N, K);
   if (terms == PREC_F16F8 && awt_gemm_pp_mode() == 2 && gemm_pp_supported(M, N, K, EPI_F32)) {
     // the persistent ping-pong kernel (tuning knob "gemm_pp" = 2): x as split lines over the two x planes' space (its 256-row panel reads beyond M
     // stay inside the workspace: the packed weight image of N >= 256 rows follows), the weight in the packed region image over the two w planes' space
-    Act ai; ai.ilv = (char*)xh;
+    Act ai; ai.ilv = ws.x_ilv();
     int rcp = launch_split_planes(c, x, (int64_t)M * K, 1.0f, terms, kF8Act, nullptr, nullptr, nullptr, nullptr, s, ai.ilv); if (rcp) return rcp;
-    if (hipMemsetAsync(wh, 0, gemm_pp_weight_bytes(N, K), s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear: weight image reset failed");
-    rcp = launch_pack_weight_pp(c, w, N, K, 0, (char*)wh, s); if (rcp) return rcp;
-    Planes pwp; pwp.pp = (char*)wh; pwp.rows = N; pwp.ld = K;
+    if (hipMemsetAsync(ws.w_pp(), 0, gemm_pp_weight_bytes(N, K), s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear: weight image reset failed");
+    rcp = launch_pack_weight_pp(c, w, N, K, 0, ws.w_pp(), s); if (rcp) return rcp;
+    Planes pwp; pwp.pp = ws.w_pp(); pwp.rows = N; pwp.ld = K;
     GemmSeg sgp = seg_plain(ai, K, pwp, 0, K, M);
     GemmOut op{}; op.f32 = y; op.ldo = N; op.bias = bias; op.n_valid = N;
     return launch_gemm_pp(c, M, N, sgp, EPI_F32, op, s);
   }
-  const Act ax = make_act(xh, xl, (size_t)M * K, terms);
-  int rc = launch_split_planes(c, x, (int64_t)M * K, 1.0f, terms, kF8Act, xh, xl, ax.hi8, ax.lo8, s); if (rc) return rc;
-  Planes pw; pw.hi = wh; pw.lo = wl; pw.x8 = (uint8_t*)wl + (size_t)N * K; pw.rows = N; pw.ld = K;
-  if (terms == PREC_F16F8 || terms == PREC_F16X3) {   // as awt_encoder_set_weight does: fp16-exact weights take the GEMM without the x_hi w_lo product; the flag is the
-    int* flag = (int*)((char*)wl + align_up((size_t)N * K * 2));      // word of the workspace's 256-byte tail
+  const Act ax = make_act(ws.x.hi, ws.x.lo, (size_t)M * K, terms);
+  int rc = launch_split_planes(c, x, (int64_t)M * K, 1.0f, terms, kF8Act, ws.x.hi, ws.x.lo, ax.hi8, ax.lo8, s); if (rc) return rc;
+  Planes pw; pw.hi = ws.w.hi; pw.lo = ws.w.lo; pw.x8 = (uint8_t*)pw.lo + (size_t)N * K; pw.rows = N; pw.ld = K;
+  if (terms == PREC_F16F8 || terms == PREC_F16X3) {   // as awt_encoder_set_weight does: fp16-exact weights take the GEMM without the x_hi w_lo product
     int host = 1;
-    if (hipMemsetAsync(flag, 0, sizeof(int), s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear: flag reset failed");
+    if (hipMemsetAsync(ws.flag, 0, sizeof(int), s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear: flag reset failed");
     if (terms == PREC_F16F8) {
       pw.s_rows = ((int64_t)N + 255) / 256 * 256;
-      pw.s16 = (bf16_t*)((char*)flag + 256); pw.s8 = (uint8_t*)pw.s16 + align_up((size_t)pw.s_rows * K * 2);
+      pw.s16 = ws.s16; pw.s8 = ws.s8;
       if (N % 256 != 0) {   // the rows beyond N are read by the last column tile (never stored): keep them finite
-        if (hipMemsetAsync(pw.s16, 0, 2 * align_up((size_t)pw.s_rows * K * 2), s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear: weight copy reset failed");
+        if (hipMemsetAsync(ws.s16, 0, ws.s_bytes, s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear: weight copy reset failed");
       }
     }
-    rc = launch_pack_weight(c, w, N, K, 1, K, 0, 0, 1.0f, wh, wl, pw.x8, terms, s, flag, pw.s16, pw.s8); if (rc) return rc;
-    if (hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    rc = launch_pack_weight(c, w, N, K, 1, K, 0, 0, 1.0f, pw.hi, pw.lo, pw.x8, terms, s, ws.flag, pw.s16, pw.s8); if (rc) return rc;
+    if (hipMemcpyAsync(&host, ws.flag, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
       return awt_fail(AWT_ERR_HIP, "op_linear: flag read-back failed");
     pw.exact16 = host == 0;
   } else {
-    rc = launch_pack_weight(c, w, N, K, 1, K, 0, 0, 1.0f, wh, wl, pw.x8, terms, s); if (rc) return rc;     // fragment-major
+    rc = launch_pack_weight(c, w, N, K, 1, K, 0, 0, 1.0f, pw.hi, pw.lo, pw.x8, terms, s); if (rc) return rc;     // fragment-major
   }
   GemmSeg sg = seg_plain(ax, K, pw, 0, K, M);
   GemmOut o{}; o.f32 = y; o.ldo = N; o.bias = bias; o.n_valid = N;
@@ -995,7 +1005,7 @@ extern "C" int awt_op_layernorm(awt_ctx* c, const float* x, const float* gamma, 
   return launch_layernorm(c, x, gamma, beta, M, d, eps, y, Act{}, PREC_BF16X3, (hipStream_t)stream);
 }
 
-extern "C" size_t awt_op_attention_workspace_bytes(int B, int H, int S) { return 6 * align_up((size_t)B * H * S * 64 * 2); }
+extern "C" size_t awt_op_attention_workspace_bytes(int B, int H, int S) { return op_attention_layout(nullptr, B, H, S).bytes; }
 extern "C" int awt_op_attention(awt_ctx* c, const float* q, const float* k, const float* v, float* o, int B, int H, int S,
                                 int terms, void* workspace, size_t ws_bytes, void* stream) {
   AWT_REQUIRE(prec_known(terms), AWT_ERR_INVALID, "op_attention: terms must be 1 (bf16), 2 (fp16), 3 (bf16x3), 4 (fp16x3) or 5 (f16f8)");
@@ -1003,9 +1013,8 @@ extern "C" int awt_op_attention(awt_ctx* c, const float* q, const float* k, cons
   AWT_REQUIRE(ws_bytes >= awt_op_attention_workspace_bytes(B, H, S), AWT_ERR_WORKSPACE, "op_attention: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int64_t n = (int64_t)B * H * S * 64;
-  const size_t pb = align_up((size_t)n * 2);
-  bf16_t* pl[6];
-  for (int i = 0; i < 6; ++i) pl[i] = (bf16_t*)((char*)workspace + i * pb);
+  const OpAttentionWs ws = op_attention_layout(workspace, B, H, S);
+  bf16_t* const pl[6] = {ws.q.hi, ws.q.lo, ws.k.hi, ws.k.lo, ws.v.hi, ws.v.lo};
   const float* src[3] = {q, k, v};
   const int f8exp[3] = {kF8Q, kF8KV, kF8KV};
   for (int i = 0; i < 3; ++i) {   // the kernel expects q * log2(e); f16f8: the second 2-byte plane holds the two e4m3 planes

@@ -20,8 +20,6 @@ int launch_gemm_batched(awt_ctx* c, int batch, int M, int N, int K, const bf16_t
                         const bf16_t* w_lo, int64_t bs_w, float* out, const float* resid, int64_t ldo, int64_t bs_o, int n_valid, hipStream_t s);
 
 namespace {
-constexpr size_t kAlign = 256;
-size_t align_up(size_t x) { return (x + kAlign - 1) & ~(kAlign - 1); }
 int pad_to(int x, int m) { return (x + m - 1) / m * m; }
 
 // fp32 sources -> split-bf16 planes of a zero-padded [rows_p, cols_p] matrix per batch entry.  FRAG: fragment-major (w_frag_index: the GEMM's B
@@ -77,16 +75,6 @@ int launch_planes(const float* src, const float* src2, int k1, bool trans, int b
   return AWT_OK;
 }
 
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-  return x;
-}
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
 // all-threads reduction of a 256-thread workgroup through 4 wave partials (fixed order: deterministic)
 template <bool MAX>
 __device__ __forceinline__ float block_reduce(float x, float* sh) {
@@ -142,9 +130,12 @@ __global__ __launch_bounds__(256) void softmax_rows_bwd_kernel(const float* __re
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ C-ABI
+// the hi / lo planes of `batch` zero-padded [rows, Kp] matrices: awt_bmm's workspace (rows = M, its A operand) and the packed buffer of
+// awt_bmm_pack* (rows = N padded to 128, its B operand)
+static PlanesWs bmm_planes_layout(void* base, int batch, int rows, int Kp) { return planes_layout(base, (size_t)batch * rows * Kp); }
 extern "C" size_t awt_bmm_packed_bytes(int batch, int N, int K) {
   if (batch <= 0 || N <= 0 || K <= 0) return 0;
-  return 2 * align_up((size_t)batch * pad_to(N, 128) * pad_to(K, 64) * 2);
+  return bmm_planes_layout(nullptr, batch, pad_to(N, 128), pad_to(K, 64)).bytes;
 }
 
 namespace {
@@ -155,10 +146,9 @@ int bmm_pack_impl(awt_ctx* c, const float* b, const float* b2, int k1, bool tran
   AWT_REQUIRE(packed_bytes >= awt_bmm_packed_bytes(batch, N, K), AWT_ERR_WORKSPACE, std::string(who) + ": packed buffer too small (awt_bmm_packed_bytes)");
   AWT_REQUIRE(((uintptr_t)packed & 255) == 0, AWT_ERR_INVALID, std::string(who) + ": packed buffer must be 256-byte aligned");
   const int Np = pad_to(N, 128), Kp = pad_to(K, 64);
-  bf16_t* hi = (bf16_t*)packed;
-  bf16_t* lo = (bf16_t*)((char*)packed + align_up((size_t)batch * Np * Kp * 2));
+  const PlanePair w = bmm_planes_layout(packed, batch, Np, Kp).p;
   ProfScope prof(c, AWT_PROF_OTHER, (hipStream_t)stream, 0.0);
-  return launch_planes<true>(b, b2, k1, trans, batch, N, K, ldb, stride_b, Np, Kp, hi, lo, (hipStream_t)stream);
+  return launch_planes<true>(b, b2, k1, trans, batch, N, K, ldb, stride_b, Np, Kp, w.hi, w.lo, (hipStream_t)stream);
 }
 
 int bmm_impl(awt_ctx* c, const float* a, const float* a2, int k1, bool trans, int64_t lda, int64_t stride_a, const void* packed_b, const float* resid, float* out,
@@ -171,15 +161,13 @@ int bmm_impl(awt_ctx* c, const float* a, const float* a2, int k1, bool trans, in
   AWT_REQUIRE(((uintptr_t)workspace & 255) == 0 && ((uintptr_t)packed_b & 255) == 0, AWT_ERR_INVALID, std::string(who) + ": workspace and packed operand must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int Np = pad_to(N, 128), Kp = pad_to(K, 64);
-  bf16_t* ah = (bf16_t*)workspace;
-  bf16_t* al = (bf16_t*)((char*)workspace + align_up((size_t)batch * M * Kp * 2));
+  const PlanePair ap = bmm_planes_layout(workspace, batch, M, Kp).p;
   {
     ProfScope prof(c, AWT_PROF_OTHER, s, 0.0);
-    int rc = launch_planes<false>(a, a2, k1, trans, batch, M, K, lda, stride_a, M, Kp, ah, al, s); if (rc) return rc;
+    int rc = launch_planes<false>(a, a2, k1, trans, batch, M, K, lda, stride_a, M, Kp, ap.hi, ap.lo, s); if (rc) return rc;
   }
-  const bf16_t* wh = (const bf16_t*)packed_b;
-  const bf16_t* wl = (const bf16_t*)((const char*)packed_b + align_up((size_t)batch * Np * Kp * 2));
-  return launch_gemm_batched(c, batch, M, Np, Kp, ah, al, Kp, (int64_t)M * Kp, wh, wl, (int64_t)Np * Kp, out, resid, ldo, stride_o, N, s);
+  const PlanePair w = bmm_planes_layout(const_cast<void*>(packed_b), batch, Np, Kp).p;     // read only
+  return launch_gemm_batched(c, batch, M, Np, Kp, ap.hi, ap.lo, Kp, (int64_t)M * Kp, w.hi, w.lo, (int64_t)Np * Kp, out, resid, ldo, stride_o, N, s);
 }
 }  // namespace
 
@@ -193,7 +181,7 @@ extern "C" int awt_bmm_pack_kmajor(awt_ctx* c, const float* b1, const float* b2,
 
 extern "C" size_t awt_bmm_workspace_bytes(int batch, int M, int K) {
   if (batch <= 0 || M <= 0 || K <= 0) return 0;
-  return 2 * align_up((size_t)batch * M * pad_to(K, 64) * 2);
+  return bmm_planes_layout(nullptr, batch, M, pad_to(K, 64)).bytes;
 }
 
 extern "C" int awt_bmm(awt_ctx* c, const float* a, int64_t lda, int64_t stride_a, const void* packed_b, const float* resid, float* out, int64_t ldo,

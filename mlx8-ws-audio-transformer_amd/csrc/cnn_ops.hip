@@ -18,9 +18,6 @@
 
 namespace {
 
-constexpr size_t kAlign = 256;
-size_t align_up(size_t x) { return (x + kAlign - 1) & ~(kAlign - 1); }
-
 constexpr int kCols = 32;                 // column groups (float4) per workgroup: 128 channels
 constexpr int kLanes = 8;                 // row lanes per workgroup
 constexpr int kPerLane = 8;               // row units per row lane
@@ -295,12 +292,19 @@ int slabs(int64_t units) { return (int)((units + kSlab - 1) / kSlab); }
 size_t partial_bytes(int64_t units, int C) { return (size_t)slabs(units) * 2 * (size_t)C * 4; }
 bool shape_ok(int B, int T, int C) { return B > 0 && T > 0 && C > 0 && (int64_t)B * T <= (int64_t)kSlab * 65535; }
 
+// awt_op_conv1d's workspace: the planes of x [B T, Cin], then the packed planes of w [Cout, 3 Cin]
+struct Conv1dWs { PlanePair x, w; size_t bytes; };
+Conv1dWs conv1d_layout(void* base, int B, int T, int Cin, int Cout) {
+  Carver cv(base);
+  return {take_planes(cv, (size_t)B * T * Cin), take_planes(cv, (size_t)Cout * 3 * Cin), cv.bytes()};
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ C ABI (include/awt.h)
 extern "C" size_t awt_op_conv1d_workspace_bytes(int B, int T, int Cin, int Cout) {
   if (B <= 0 || T <= 0 || Cin <= 0 || Cout <= 0) return 0;
-  return 2 * align_up((size_t)B * T * Cin * 2) + 2 * align_up((size_t)Cout * 3 * Cin * 2);       // x planes, packed w planes
+  return conv1d_layout(nullptr, B, T, Cin, Cout).bytes;
 }
 extern "C" int awt_op_conv1d(awt_ctx* c, const float* x, const float* w, const float* bias, float* y, int B, int T, int Cin, int Cout, int taps,
                              int terms, void* workspace, size_t ws_bytes, void* stream) {
@@ -313,10 +317,8 @@ extern "C" int awt_op_conv1d(awt_ctx* c, const float* x, const float* w, const f
   AWT_REQUIRE(ws_bytes >= awt_op_conv1d_workspace_bytes(B, T, Cin, Cout), AWT_ERR_WORKSPACE, "op_conv1d: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int M = B * T, K = 3 * Cin;
-  char* base = (char*)workspace;
-  const size_t xb = align_up((size_t)M * Cin * 2), wb = align_up((size_t)Cout * K * 2);
-  bf16_t* xh = (bf16_t*)base; bf16_t* xl = (bf16_t*)(base + xb);
-  bf16_t* wh = (bf16_t*)(base + 2 * xb); bf16_t* wl = (bf16_t*)(base + 2 * xb + wb);
+  const Conv1dWs ws = conv1d_layout(workspace, B, T, Cin, Cout);
+  bf16_t *const xh = ws.x.hi, *const xl = ws.x.lo, *const wh = ws.w.hi, *const wl = ws.w.lo;
   // terms 4: the same three products on fp16 hi + lo planes -- 22 significant bits per operand where the bf16 pair has 16, for operands inside
   // fp16's range (the forward's activations and weights; gradients are not: they take the bf16 planes).  BatchNorm + ReLU + max-pool downstream
   // are discontinuous, so the forward's last bits decide masks: this is the format the model's forward convs run in (cnn_classifier.py).
@@ -327,11 +329,8 @@ extern "C" int awt_op_conv1d(awt_ctx* c, const float* x, const float* w, const f
   rc = launch_pack_weight(c, w, Cout, Cin, 3, K, 0, 0, 1.0f, wh, two ? wl : nullptr, nullptr, terms, s); if (rc) return rc;   // k = tap Cin + ci
   GemmSeg sg[3];
   for (int tap = 0; tap < 3; ++tap) {     // output frame t of a clip reads frame t + tap - 1 of the SAME clip; outside [0, T) reads as zero (the padding)
-    GemmSeg g{};
-    g.a_hi = xh; g.a_lo = two ? xl : nullptr; g.lda = Cin;
-    g.w_hi = wh; g.w_lo = two ? wl : nullptr; g.w_ksteps = K / 32; g.w_k0 = tap * Cin / 32; g.K = Cin;
-    g.rows_out = T; g.rows_in = T; g.row_mul = 1; g.row_add = tap - 1;
-    sg[tap] = g;
+    sg[tap] = gemm_seg_plain(xh, two ? xl : nullptr, Cin, wh, two ? wl : nullptr, K / 32, tap * Cin / 32, Cin, M);
+    sg[tap].rows_out = T; sg[tap].rows_in = T; sg[tap].row_mul = 1; sg[tap].row_add = tap - 1;
   }
   GemmOut o{}; o.f32 = y; o.ldo = Cout; o.bias = bias; o.n_valid = Cout;
   return launch_gemm(c, M, Cout, sg, 3, terms, EPI_F32, o, s);

@@ -248,6 +248,18 @@ __device__ __forceinline__ void store_act4(const Act& o, int64_t off, const floa
   }
 }
 
+// ---------------------------------------------------------------- wave reductions (device): all 64 lanes get the result, fixed order
+__device__ __forceinline__ float wave_max(float x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
+  return x;
+}
+__device__ __forceinline__ float wave_sum(float x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+  return x;
+}
+
 // ---------------------------------------------------------------- workgroup order and row maps (device), shared by the GEMM, weight-gradient and attention kernels
 // XCD-contiguous remap of a 1-D grid of n workgroups: the hardware deals block b to XCD b % 8; the logical index returned gives each XCD a contiguous
 // run of logical indices instead (bijective for every n: the first n % 8 XCDs own one index more), so that neighbours in the logical order share an L2.
@@ -294,6 +306,24 @@ int awt_fail(int code, const std::string& msg);
   do {                                       \
     if (!(cond)) return awt_fail(code, msg); \
   } while (0)
+
+// ---------------------------------------------------------------- caller workspaces (host)
+inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }   // every piece of a workspace starts on a 256-byte boundary of an aligned base
+// Bump allocator over a caller's workspace.  A workspace's size and its layout are ONE function that takes the shape and a base and returns the pieces
+// plus bytes(): the `*_workspace_bytes()` query runs it with a null base (every piece comes back null, only the offsets advance), the entry point
+// with the caller's pointer -- so the two cannot disagree.  `off` is public for layouts whose phases alias one region (carve() in awt_api.hip).
+struct Carver {
+  char* base; size_t off = 0;
+  explicit Carver(void* b) : base((char*)b) {}
+  template <class T = char> T* take(size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes); return (T*)p; }
+  size_t bytes() const { return off; }
+};
+// the hi / lo planes of a matrix of `elems` 2-byte elements, the commonest pieces; and the workspace that is nothing else
+// (a layout returns its struct as a braced list: the initialisers run left to right, bytes() last)
+struct PlanePair { bf16_t *hi, *lo; };
+inline PlanePair take_planes(Carver& cv, size_t elems) { return {cv.take<bf16_t>(elems * 2), cv.take<bf16_t>(elems * 2)}; }
+struct PlanesWs { PlanePair p; size_t bytes; };
+inline PlanesWs planes_layout(void* base, size_t elems) { Carver cv(base); return {take_planes(cv, elems), cv.bytes()}; }
 
 // ---------------------------------------------------------------- profiling (HIP events on the launch stream)
 struct awt_prof_state;
@@ -363,6 +393,14 @@ struct GemmSeg {
   // [0, rows_in) of their group read as zeros (the conv stem's padding).  Plain GEMM: rows_out = rows_in = M.
   int rows_out, rows_in, row_mul, row_add;
 };
+
+// one plain K segment (identity row map over M rows) on 2-byte hi (+ lo) planes; the f16f8, ping-pong and 16-row fields stay zero
+inline GemmSeg gemm_seg_plain(const bf16_t* a_hi, const bf16_t* a_lo, int64_t lda, const bf16_t* w_hi, const bf16_t* w_lo, int w_ksteps, int w_k0, int K, int M) {
+  GemmSeg s{};
+  s.a_hi = a_hi; s.a_lo = a_lo; s.lda = lda; s.w_hi = w_hi; s.w_lo = w_lo; s.w_ksteps = w_ksteps; s.w_k0 = w_k0; s.K = K;
+  s.rows_out = M; s.rows_in = M; s.row_mul = 1; s.row_add = 0;
+  return s;
+}
 
 enum GemmEpilogue {
   EPI_F32 = 0,        // out_f32[m, n] = acc + bias                        (ldo)

@@ -26,8 +26,6 @@ struct awt_weight {
 };
 
 namespace {
-constexpr size_t kAlign = 256;
-size_t align_up(size_t x) { return (x + kAlign - 1) & ~(kAlign - 1); }
 int dmalloc0(void** p, size_t bytes) {
   AWT_HIP_CHECK(hipMalloc(p, bytes));
   AWT_HIP_CHECK(hipMemset(*p, 0, bytes));
@@ -81,9 +79,11 @@ extern "C" int awt_weight_update(awt_ctx* c, awt_weight* h, const float* w, cons
   return rc;
 }
 
+// workspace of awt_linear_forward / awt_linear_backward_input: the hi / lo planes of x [M, K] or of dy [M, Np]
+static PlanesWs linear_layout(void* base, const awt_weight* w, int M, int backward) { return planes_layout(base, (size_t)M * (backward ? w->Np : w->K)); }
 extern "C" size_t awt_linear_workspace_bytes(const awt_weight* w, int M, int backward) {
   if (!w || M <= 0) return 0;
-  return 2 * align_up((size_t)M * (backward ? w->Np : w->K) * 2);     // the hi / lo planes of x [M, K] or of dy [M, Np]
+  return linear_layout(nullptr, w, M, backward).bytes;
 }
 
 // y [M, Np] = x [M, K] W^T + bias (+ resid [M, Np]); columns N .. Np - 1 of y are written as 0 + resid
@@ -92,13 +92,9 @@ extern "C" int awt_linear_forward(awt_ctx* c, const awt_weight* w, const float* 
   AWT_REQUIRE(c && w && x && y && workspace && M > 0, AWT_ERR_INVALID, "linear_forward: bad argument");
   AWT_REQUIRE(ws_bytes >= awt_linear_workspace_bytes(w, M, 0), AWT_ERR_WORKSPACE, "linear_forward: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  bf16_t* xh = (bf16_t*)workspace;
-  bf16_t* xl = (bf16_t*)((char*)workspace + align_up((size_t)M * w->K * 2));
-  int rc = launch_split_planes(c, x, (int64_t)M * w->K, 1.0f, w->prec, 0, xh, xl, nullptr, nullptr, s); if (rc) return rc;
-  GemmSeg sg{};
-  sg.a_hi = xh; sg.a_lo = w->prec == PREC_BF16X3 ? xl : nullptr; sg.lda = w->K;
-  sg.w_hi = w->hi; sg.w_lo = w->lo; sg.w_ksteps = w->K / 32; sg.w_k0 = 0; sg.K = w->K;
-  sg.rows_out = M; sg.rows_in = M; sg.row_mul = 1; sg.row_add = 0;
+  const PlanePair xp = linear_layout(workspace, w, M, 0).p;
+  int rc = launch_split_planes(c, x, (int64_t)M * w->K, 1.0f, w->prec, 0, xp.hi, xp.lo, nullptr, nullptr, s); if (rc) return rc;
+  GemmSeg sg = gemm_seg_plain(xp.hi, w->prec == PREC_BF16X3 ? xp.lo : nullptr, w->K, w->hi, w->lo, w->K / 32, 0, w->K, M);
   GemmOut o{}; o.f32 = y; o.resid = resid; o.ldo = w->Np; o.bias = w->bias; o.n_valid = w->Np;
   return launch_gemm(c, M, w->Np, &sg, 1, w->prec, resid ? EPI_F32_RESID : EPI_F32, o, s);
 }
@@ -111,13 +107,9 @@ extern "C" int awt_linear_backward_input(awt_ctx* c, const awt_weight* w, const 
   AWT_REQUIRE(w->K % 128 == 0, AWT_ERR_INVALID, "linear_backward_input: the weight's K (= N of this product) must be a multiple of 128");
   AWT_REQUIRE(ws_bytes >= awt_linear_workspace_bytes(w, M, 1), AWT_ERR_WORKSPACE, "linear_backward_input: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  bf16_t* gh = (bf16_t*)workspace;
-  bf16_t* gl = (bf16_t*)((char*)workspace + align_up((size_t)M * w->Np * 2));
-  int rc = launch_split_planes(c, dy, (int64_t)M * w->Np, 1.0f, w->prec, 0, gh, gl, nullptr, nullptr, s); if (rc) return rc;
-  GemmSeg sg{};
-  sg.a_hi = gh; sg.a_lo = w->prec == PREC_BF16X3 ? gl : nullptr; sg.lda = w->Np;
-  sg.w_hi = w->t_hi; sg.w_lo = w->t_lo; sg.w_ksteps = w->Np / 32; sg.w_k0 = 0; sg.K = w->Np;
-  sg.rows_out = M; sg.rows_in = M; sg.row_mul = 1; sg.row_add = 0;
+  const PlanePair gp = linear_layout(workspace, w, M, 1).p;
+  int rc = launch_split_planes(c, dy, (int64_t)M * w->Np, 1.0f, w->prec, 0, gp.hi, gp.lo, nullptr, nullptr, s); if (rc) return rc;
+  GemmSeg sg = gemm_seg_plain(gp.hi, w->prec == PREC_BF16X3 ? gp.lo : nullptr, w->Np, w->t_hi, w->t_lo, w->Np / 32, 0, w->Np, M);
   GemmOut o{}; o.f32 = dx; o.ldo = w->K; o.n_valid = w->K;
   return launch_gemm(c, M, w->K, &sg, 1, w->prec, EPI_F32, o, s);
 }
@@ -233,17 +225,6 @@ __device__ __forceinline__ float drop_keep(const SmallAttn& a, int bh, int i, in
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   z ^= z >> 31;
   return ((float)(unsigned)(z >> 40) * (1.0f / 16777216.0f) >= a.drop_p) ? a.inv_keep : 0.0f;
-}
-
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-  return x;
-}
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
 }
 
 // ---------------------------------------------------------------------------------------------- parameter-gradient reductions
@@ -586,26 +567,18 @@ int launch_param_grad(awt_ctx* c, const float* dy, const bf16_t* dy_hi, const bf
   AWT_HIP_CHECK(hipGetLastError());
   return AWT_OK;
 }
-extern "C" size_t awt_op_param_grad_workspace_bytes(int M, int d) { return (size_t)((M + kSlabRows - 1) / kSlabRows) * 2 * (size_t)d * 4; }
+extern "C" size_t awt_op_param_grad_workspace_bytes(int M, int d) { return param_grad_partial_bytes(M, d); }
 extern "C" int awt_op_layernorm_param_grad(awt_ctx* c, const float* dy, const float* x, float* dgamma, float* dbeta, int M, int d, float eps,
                                            void* workspace, size_t ws_bytes, void* stream) {
   AWT_REQUIRE(c && dy && x && dgamma && dbeta && workspace && M > 0 && d > 0 && d <= 64 * kColMaxChunks, AWT_ERR_INVALID,
               "op_layernorm_param_grad: bad argument (d <= 1280)");
   AWT_REQUIRE(ws_bytes >= awt_op_param_grad_workspace_bytes(M, d), AWT_ERR_WORKSPACE, "op_layernorm_param_grad: workspace too small");
-  const int nslab = (M + kSlabRows - 1) / kSlabRows;
-  hipLaunchKernelGGL(ln_param_grad_kernel, dim3(nslab), dim3(256), 0, (hipStream_t)stream, dy, x, M, d, eps, (float*)workspace, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (int64_t)0);
-  hipLaunchKernelGGL(slab_sum_kernel, dim3((d + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, nslab, d, dgamma, dbeta, 1.0f, 0);
-  AWT_HIP_CHECK(hipGetLastError());
-  return AWT_OK;
+  return launch_param_grad(c, dy, nullptr, nullptr, 0, x, M, d, eps, 1.0f, 0, dgamma, dbeta, (float*)workspace, (hipStream_t)stream);
 }
 extern "C" int awt_op_column_sums(awt_ctx* c, const float* a, float* sums, int M, int d, void* workspace, size_t ws_bytes, void* stream) {
   AWT_REQUIRE(c && a && sums && workspace && M > 0 && d > 0 && d <= 64 * kColMaxChunks, AWT_ERR_INVALID, "op_column_sums: bad argument (d <= 1280)");
   AWT_REQUIRE(ws_bytes >= awt_op_param_grad_workspace_bytes(M, d), AWT_ERR_WORKSPACE, "op_column_sums: workspace too small");
-  const int nslab = (M + kSlabRows - 1) / kSlabRows;
-  hipLaunchKernelGGL(ln_param_grad_kernel, dim3(nslab), dim3(256), 0, (hipStream_t)stream, a, (const float*)nullptr, M, d, 0.f, (float*)workspace, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (int64_t)0);
-  hipLaunchKernelGGL(slab_sum_kernel, dim3((d + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, nslab, d, (float*)nullptr, sums, 1.0f, 0);
-  AWT_HIP_CHECK(hipGetLastError());
-  return AWT_OK;
+  return launch_param_grad(c, a, nullptr, nullptr, 0, nullptr, M, d, 0.f, 1.0f, 0, nullptr, sums, (float*)workspace, (hipStream_t)stream);
 }
 extern "C" int awt_op_cross_entropy(awt_ctx* c, const float* logits, const int64_t* labels, int M, int vocab, int ld, float* loss, float* dlogits,
                                     void* scratch /* >= (M + 1) * 4 bytes */, void* stream) {

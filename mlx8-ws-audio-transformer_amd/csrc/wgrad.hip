@@ -245,11 +245,17 @@ int launch_conv_tap(awt_ctx* c, const float* src, int N, int C, int tap, float* 
 
 // ------------------------------------------------------------------------------------------------ single-operator entry (include/awt.h)
 namespace {
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// awt_op_weight_grad's workspace: the split-bf16 planes of dy [M, ldy] and of x [rows_x, ldx], then the slab partials of the product
+struct OpWgradWs { PlanePair y, x; float* partial; size_t partial_bytes, bytes; };
+OpWgradWs op_wgrad_layout(void* base, int M, int rows_x, int ldy, int ldx, int N, int K) {
+  const size_t pb = align_up(N > 0 && K > 0 ? wgrad_partial_bytes(M, N, K) : 0);     // an empty product: launch_wgrad refuses it
+  Carver cv(base);
+  return {take_planes(cv, (size_t)M * ldy), take_planes(cv, (size_t)rows_x * ldx), cv.take<float>(pb), pb, cv.bytes()};
 }
+}  // namespace
 extern "C" size_t awt_op_weight_grad_workspace_bytes(int M, int rows_x, int ldy, int ldx, int N, int K) {
   if (M <= 0 || rows_x <= 0 || ldy <= 0 || ldx <= 0 || N <= 0 || K <= 0) return 0;
-  return 2 * align256((size_t)M * ldy * 2) + 2 * align256((size_t)rows_x * ldx * 2) + align256(wgrad_partial_bytes(M, N, K));
+  return op_wgrad_layout(nullptr, M, rows_x, ldy, ldx, N, K).bytes;
 }
 extern "C" int awt_op_weight_grad(awt_ctx* c, const float* dy, int ldy, int ycol, int N, const float* x, int rows_x, int ldx, int xcol, int K, int M,
                                   int rows_out, int rows_in, int row_mul, int row_add, int terms, float scale, int accumulate, float* out,
@@ -264,14 +270,10 @@ extern "C" int awt_op_weight_grad(awt_ctx* c, const float* dy, int ldy, int ycol
               "op_weight_grad: x must have M rows, or (M / rows_out) * rows_in rows under a row map");
   AWT_REQUIRE(ws_bytes >= awt_op_weight_grad_workspace_bytes(M, rows_x, ldy, ldx, N, K), AWT_ERR_WORKSPACE, "op_weight_grad: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)workspace;
-  const size_t yb = align256((size_t)M * ldy * 2), xb = align256((size_t)rows_x * ldx * 2);
-  bf16_t* yh = (bf16_t*)base; bf16_t* yl = (bf16_t*)(base + yb);
-  bf16_t* xh = (bf16_t*)(base + 2 * yb); bf16_t* xl = (bf16_t*)(base + 2 * yb + xb);
-  float* partial = (float*)(base + 2 * yb + 2 * xb);
-  int rc = launch_split_f32(c, dy, (int64_t)M * ldy, 1.0f, yh, yl, s); if (rc) return rc;
-  rc = launch_split_f32(c, x, (int64_t)rows_x * ldx, 1.0f, xh, xl, s); if (rc) return rc;
-  const WgradOperand yo{yh, yl, ldy, ycol}, xo{xh, xl, ldx, xcol};
+  const OpWgradWs w = op_wgrad_layout(workspace, M, rows_x, ldy, ldx, N, K);
+  int rc = launch_split_f32(c, dy, (int64_t)M * ldy, 1.0f, w.y.hi, w.y.lo, s); if (rc) return rc;
+  rc = launch_split_f32(c, x, (int64_t)rows_x * ldx, 1.0f, w.x.hi, w.x.lo, s); if (rc) return rc;
+  const WgradOperand yo{w.y.hi, w.y.lo, ldy, ycol}, xo{w.x.hi, w.x.lo, ldx, xcol};
   const WgradRowMap map{rows_out, rows_in, row_mul, row_add};
-  return launch_wgrad(c, yo, N, xo, K, M, mapped ? &map : nullptr, terms, scale, out, sn, sk, accumulate, partial, ws_bytes - 2 * yb - 2 * xb, s);
+  return launch_wgrad(c, yo, N, xo, K, M, mapped ? &map : nullptr, terms, scale, out, sn, sk, accumulate, w.partial, w.partial_bytes, s);
 }
