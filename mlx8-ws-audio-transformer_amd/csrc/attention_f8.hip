@@ -25,6 +25,8 @@ extern int g_attn_shape;
 namespace {
 
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int KB = 64;               // keys per tile
 constexpr int PL16 = KB * 64 * 2;    // 8 KiB: [64 keys][64 dims] fp16
@@ -200,22 +202,24 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f16f8_pipe_kernel(Attn8A
     else r.v8[0] = r.v8[1] = 0;
     return r;
   };
+  using I0 = std::integral_constant<int, 0>;
   auto lds128 = [](unsigned addr) { return *(const __attribute__((address_space(3))) i32x4_t*)(uintptr_t)addr; };
-  auto read_slot = [&](auto slot_t, const RdAddr& ra, i32x8& f) {
-    constexpr int SLOT = decltype(slot_t)::value;
+  // (KADD / VADD: a compile-time ring-slot offset on top of ra, for the iterations that know their slot)
+  auto read_slot = [&](auto slot_t, const RdAddr& ra, i32x8& f, auto kadd_t, auto vadd_t) {
+    constexpr int SLOT = decltype(slot_t)::value, KADD = decltype(kadd_t)::value, VADD = decltype(vadd_t)::value;
     if constexpr (SLOT < 12) {
       constexpr int kt2 = SLOT / 6, w = SLOT % 6;
       if constexpr (w < 2) {
-        constexpr int pl = (w == 0 ? KO8 : KOL8) + kt2 * 2048;
+        constexpr int pl = (w == 0 ? KO8 : KOL8) + kt2 * 2048 + KADD;
         const i32x4_t x0 = lds128(ra.k8[0] + pl), x1 = lds128(ra.k8[1] + pl);
         f = (i32x8){x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
       } else {
-        const i32x4_t x0 = lds128(ra.k16[w - 2] + kt2 * 4096);
+        const i32x4_t x0 = lds128(ra.k16[w - 2] + kt2 * 4096 + KADD);
         f[0] = x0[0]; f[1] = x0[1]; f[2] = x0[2]; f[3] = x0[3];
       }
     } else if constexpr (SLOT < 20) {
       constexpr int I = SLOT - 12, kt2 = I >> 2, s2 = (I >> 1) & 1, et = I & 1;
-      constexpr int cst = kt2 * 4096 + s2 * 2048;
+      constexpr int cst = kt2 * 4096 + s2 * 2048 + VADD;
       const unsigned a0 = (et == 0 ? ra.v0 : ra.v1) + cst, a1 = a0 + 1024;     // keys + 8: swz_v16 repeats every 4 rows, so the same lane offset
       const i32x2 va = __builtin_bit_cast(i32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(uintptr_t)a0));
       const i32x2 vb2 = __builtin_bit_cast(i32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) bf16x4*)(uintptr_t)a1));
@@ -259,10 +263,10 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f16f8_pipe_kernel(Attn8A
   {
     i32x8 ring[RING];
     const RdAddr ra0 = rd_addr(kslot(0), vslot(0));
-    [&]<int... P>(std::integer_sequence<int, P...>) { (read_slot(std::integral_constant<int, P>{}, ra0, ring[P]), ...); }(std::make_integer_sequence<int, DEPTH>{});
+    [&]<int... P>(std::integer_sequence<int, P...>) { (read_slot(std::integral_constant<int, P>{}, ra0, ring[P], I0{}, I0{}), ...); }(std::make_integer_sequence<int, DEPTH>{});
     [&]<int... I>(std::integer_sequence<int, I...>) {
       ([&] {
-        if constexpr (I + DEPTH < 12) read_slot(std::integral_constant<int, I + DEPTH>{}, ra0, ring[(I + DEPTH) % RING]);
+        if constexpr (I + DEPTH < 12) read_slot(std::integral_constant<int, I + DEPTH>{}, ra0, ring[(I + DEPTH) % RING], I0{}, I0{});
         qk_mma(std::integral_constant<int, I>{}, ring[I % RING], sa);
       }(), ...);
     }(std::make_integer_sequence<int, 12>{});
@@ -272,119 +276,269 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f16f8_pipe_kernel(Attn8A
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __syncthreads();
 
-  // one iteration: softmax + PV of tile kt (scores in sc), and -- unless LAST -- the scores of tile kt + 1 into sn
-  auto iter = [&](auto last_t, auto tail_t, int kt, f32x16 (&sc)[2], f32x16 (&sn)[2]) {
-    constexpr bool LAST = decltype(last_t)::value, TAIL = decltype(tail_t)::value;
-    constexpr int FIRST = LAST ? 12 : 0;                  // the last tile has no next scores to compute
-    const RdAddr ra = rd_addr(kslot(kt + 1), vslot(kt));   // K(kt + 1) for the next scores, V(kt) for this tile's output
-    if constexpr (!LAST) {
-      if constexpr (RING3) {                              // K(kt + 3) takes K(kt)'s slot, V(kt + 2) takes V(kt - 1)'s
+  if constexpr (RING3) {
+    // ---- the single-product P V form.  The 20 MFMAs of an iteration keep the order above (12 of S(kt + 1)^T, 8 of P V of tile kt); the VALU work
+    // of tile kt is cut into chunks of about one MFMA's length, one per gap, so that every MFMA has vector work issued behind it and the
+    // iteration opens with an MFMA (VALU at the head of a segment after s_barrier is not overlapped: DESIGN.md section 4.3a):
+    //   gap  0       --
+    //   gaps 1, 2    exponentials of accumulator registers 0..3, 4..7 of sub-tile 0 (behind the two 64-cycle e4m3 MFMAs)
+    //   gaps 3..6    rescale of O, eight registers each: done before the tile's first P V MFMA
+    //   gaps 7, 8    registers 8..11, 12..15 of sub-tile 0 (behind the e4m3 MFMAs of sub-tile 1)
+    //   gaps 9..16   sub-tile 1, two registers each; gap 16 closes the row sum
+    //   gaps 17..19  running maximum of tile kt + 1, whose scores are complete after MFMA 11 (with the tail mask when that tile is the
+    //                sequence's last, partial one); m_run and alpha are carried into the next iteration, the prologue does tile 0
+    // The row sum is ONE chain over the keys in this order; each chunk ends in an empty asm on psum, without which the compiler sinks all 32 adds
+    // behind the last MFMA, in front of the barrier.
+    float alpha, tmax, tmax_x;
+    auto max_sub = [&](auto c_t, auto tail_t, int t, f32x16 (&s)[2]) {      // running maximum over sub-tile C of tile t
+      constexpr int C = decltype(c_t)::value;
+      constexpr bool TAIL = decltype(tail_t)::value;
+      if constexpr (C == 0) tmax = -1.0e30f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (TAIL) {
+          const int key = t * KB + C * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+          s[C][r] = key < a.S ? s[C][r] : -1.0e30f;
+        }
+        tmax = fmaxf(tmax, s[C][r]);
+      }
+      if constexpr (C == 1) tmax_x = __shfl_xor(tmax, 32);
+    };
+    auto max_fin = [&] {
+      tmax = fmaxf(tmax, tmax_x);
+      const float m_new = fmaxf(m_run, tmax);
+      alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+      m_run = m_new;
+      asm volatile("" : "+v"(alpha), "+v"(m_run));       // here, not sunk to the next iteration's first use
+    };
+    max_sub(std::integral_constant<int, 0>{}, std::true_type{}, 0, sa);
+    max_sub(std::integral_constant<int, 1>{}, std::true_type{}, 0, sa);
+    max_fin();
+
+    // one iteration: softmax + PV of tile kt (scores in sc, their maximum in m_run), and -- unless LAST -- the scores of tile kt + 1 into sn and
+    // their maximum (ntail_t: tile kt + 1 may be the partial one)
+    // PH = kt % 3 where the caller knows it at compile time (the loop unrolled by six, in which every ring slot and score buffer is a constant:
+    // the reads are the loop-invariant lane addresses `rb` plus immediates, no K or V tile is missing and none is the partial one), else -1
+    const RdAddr rb = rd_addr(lds0, lds0 + V3_BASE);
+    auto iter = [&](auto last_t, auto ntail_t, auto ph_t, int kt, f32x16 (&sc)[2], f32x16 (&sn)[2]) {
+      constexpr bool LAST = decltype(last_t)::value;
+      constexpr int PH = decltype(ph_t)::value;
+      constexpr int FIRST = LAST ? 12 : 0;                  // the last tile has no next scores to compute
+      using KAdd = std::integral_constant<int, PH < 0 ? 0 : ((PH + 1) % 3) * K3_SLOT>;
+      using VAdd = std::integral_constant<int, PH < 0 ? 0 : PH * V3_SLOT>;
+      RdAddr ra;                                            // K(kt + 1) for the next scores, V(kt) for this tile's output
+      if constexpr (PH < 0) ra = rd_addr(kslot(kt + 1), vslot(kt));
+      else ra = rb;
+      if constexpr (PH >= 0) {                              // K(kt + 3) takes K(kt)'s slot, V(kt + 2) takes V(kt - 1)'s
+        static_assert(!LAST);
+        stage_kv1<NW, true, true, true>(a, head_off, kt + 3, lds0 + PH * K3_SLOT, wave, lo_full);
+        stage_kv1<NW, false, false, true>(a, head_off, kt + 2, lds0 + V3_BASE + ((PH + 2) % 3) * V3_SLOT, wave, lo_full);
+      } else if constexpr (!LAST) {
         if (kt + 3 < ntiles) stage_kv1<NW, true, true, true>(a, head_off, kt + 3, kslot(kt), wave, lane_off(kt + 3));
         if (kt + 2 < ntiles) stage_kv1<NW, false, false, true>(a, head_off, kt + 2, vslot(kt + 2), wave, lane_off(kt + 2));
-      } else {                                            // K(kt + 2) takes K(kt)'s half of the stage, V(kt + 1) V(kt - 1)'s
+      }
+      unsigned p16[4][4];                                   // P as fp16 pairs: fragment 2 kt2 + s2 of the P V MFMAs, four dwords each
+      float psum = 0.f;
+      auto exps = [&](auto e_t, auto j0_t, auto n_t) {      // N exponentials from register 4 E + J0 on, and their fp16 pairs
+        constexpr int E = decltype(e_t)::value, J0 = decltype(j0_t)::value, N = decltype(n_t)::value, kt2 = E >> 2, r4 = E & 3;
+#pragma unroll
+        for (int j = J0; j < J0 + N; j += 2) {
+          const float pv0 = __builtin_amdgcn_exp2f(sc[kt2][4 * r4 + j] - m_run), pv1 = __builtin_amdgcn_exp2f(sc[kt2][4 * r4 + j + 1] - m_run);
+          psum += pv0;
+          psum += pv1;
+          unsigned w = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){pv0, pv1}, f16x2));   // v_cvt_pk_f16_f32: RNE, as f32_to_f16
+          asm volatile("" : "+v"(w));                       // converted in this chunk
+          p16[2 * kt2 + (r4 >> 1)][2 * (r4 & 1) + j / 2] = w;
+        }
+        asm volatile("" : "+v"(psum));
+      };
+      auto valu_chunk = [&](auto g_t) {
+        constexpr int G = decltype(g_t)::value;
+        using I4 = std::integral_constant<int, 4>;
+        using I2 = std::integral_constant<int, 2>;
+        if constexpr (G == 1 || G == 2) exps(std::integral_constant<int, G - 1>{}, I0{}, I4{});
+        else if constexpr (G >= 3 && G <= 6) {
+          constexpr int et = (G - 3) >> 1, r0 = 8 * ((G - 3) & 1);
+#pragma unroll
+          for (int r = r0; r < r0 + 8; ++r) {                // each product pinned: left alone, the compiler packs the 32 multiplies into v_pk_mul_f32
+            float x = oacc[et][r] * alpha;                  // across the chunks (one gap empty, the next with 16 of them)
+            asm volatile("" : "+v"(x));
+            oacc[et][r] = x;
+          }
+        } else if constexpr (G == 7 || G == 8) exps(std::integral_constant<int, G - 5>{}, I0{}, I4{});
+        else if constexpr (G >= 9 && G <= 16) {
+          exps(std::integral_constant<int, 4 + (G - 9) / 2>{}, std::integral_constant<int, 2 * ((G - 9) & 1)>{}, I2{});
+          if constexpr (G == 16) { l_run = __builtin_fmaf(l_run, alpha, psum); asm volatile("" : "+v"(l_run)); }
+        } else if constexpr (G >= 17 && !LAST) {
+          if constexpr (G < 19) max_sub(std::integral_constant<int, G - 17>{}, ntail_t, kt + 1, sn);
+          else max_fin();
+        }
+      };
+      auto mma = [&](auto slot_t, const i32x8& f) {
+        constexpr int SLOT = decltype(slot_t)::value;
+        if constexpr (SLOT < 12) qk_mma(slot_t, f, sn);
+        else {
+          constexpr int I = SLOT - 12, kt2 = I >> 2, s2 = (I >> 1) & 1, et = I & 1;
+          const bf16x8 vh = __builtin_bit_cast(bf16x8, (i32x4_t){f[0], f[1], f[2], f[3]});
+          const unsigned(&pw)[4] = p16[2 * kt2 + s2];
+          oacc[et] = mfma32<true>(vh, __builtin_bit_cast(bf16x8, (i32x4_t){(int)pw[0], (int)pw[1], (int)pw[2], (int)pw[3]}), oacc[et]);
+        }
+      };
+      i32x8 ring[RING];
+      [&]<int... P>(std::integer_sequence<int, P...>) { (read_slot(std::integral_constant<int, FIRST + P>{}, ra, ring[(FIRST + P) % RING], KAdd{}, VAdd{}), ...); }(std::make_integer_sequence<int, DEPTH>{});
+      if constexpr (LAST) {   // no S^T MFMAs to hide gaps 1..12 behind
+        [&]<int... C>(std::integer_sequence<int, C...>) { (valu_chunk(std::integral_constant<int, C + 1>{}), ...); }(std::make_integer_sequence<int, 12>{});
+      }
+      [&]<int... J>(std::integer_sequence<int, J...>) {
+        ([&] {
+          constexpr int I = FIRST + J;
+          if constexpr (I + DEPTH < NSLOT) read_slot(std::integral_constant<int, I + DEPTH>{}, ra, ring[(I + DEPTH) % RING], KAdd{}, VAdd{});
+          if constexpr (!LAST || I > 12) valu_chunk(std::integral_constant<int, I>{});
+          __builtin_amdgcn_sched_barrier(0);
+          mma(std::integral_constant<int, I>{}, ring[I % RING]);
+          __builtin_amdgcn_sched_barrier(0);
+        }(), ...);
+      }(std::make_integer_sequence<int, NSLOT - FIRST>{});
+      if constexpr (!LAST) {
+        // only the loads of the PREVIOUS iteration have to have landed: this iteration issued NK (fp16 groups + e4m3 groups) K and NV V
+        // LDS-DMA instructions per wave (fewer near the end of the key range)
+        constexpr int NK = 8 / NW + 2, NV = 8 / NW;
+        if (PH >= 0 || kt + 3 < ntiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NK + NV) : "memory");
+        else if (kt + 2 < ntiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NV) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+      }
+    };
+    // tiles in pairs so that the two score buffers swap roles without register copies; the pairs stop two or three tiles short of the end, so that
+    // only the remainder iterations carry the tail mask
+    using Ph = std::integral_constant<int, -1>;
+    int kt = 0;
+    // six tiles = lcm(2 score buffers, 3 ring slots) per trip, while K(kt + 8) exists and is a whole tile
+    for (; kt + 9 < ntiles; kt += 6) {
+      iter(std::false_type{}, std::false_type{}, std::integral_constant<int, 0>{}, kt, sa, sb);
+      iter(std::false_type{}, std::false_type{}, std::integral_constant<int, 1>{}, kt + 1, sb, sa);
+      iter(std::false_type{}, std::false_type{}, std::integral_constant<int, 2>{}, kt + 2, sa, sb);
+      iter(std::false_type{}, std::false_type{}, std::integral_constant<int, 0>{}, kt + 3, sb, sa);
+      iter(std::false_type{}, std::false_type{}, std::integral_constant<int, 1>{}, kt + 4, sa, sb);
+      iter(std::false_type{}, std::false_type{}, std::integral_constant<int, 2>{}, kt + 5, sb, sa);
+    }
+    for (; kt + 3 < ntiles; kt += 2) {
+      iter(std::false_type{}, std::false_type{}, Ph{}, kt, sa, sb);
+      iter(std::false_type{}, std::false_type{}, Ph{}, kt + 1, sb, sa);
+    }
+    if (kt + 3 == ntiles) {
+      iter(std::false_type{}, std::false_type{}, Ph{}, kt, sa, sb);
+      iter(std::false_type{}, std::true_type{}, Ph{}, kt + 1, sb, sa);
+      iter(std::true_type{}, std::false_type{}, Ph{}, kt + 2, sa, sb);
+    } else if (kt + 2 == ntiles) {
+      iter(std::false_type{}, std::true_type{}, Ph{}, kt, sa, sb);
+      iter(std::true_type{}, std::false_type{}, Ph{}, kt + 1, sb, sa);
+    } else {
+      iter(std::true_type{}, std::false_type{}, Ph{}, kt, sa, sb);
+    }
+  } else {
+    // one iteration: softmax + PV of tile kt (scores in sc), and -- unless LAST -- the scores of tile kt + 1 into sn
+    auto iter = [&](auto last_t, auto tail_t, int kt, f32x16 (&sc)[2], f32x16 (&sn)[2]) {
+      constexpr bool LAST = decltype(last_t)::value, TAIL = decltype(tail_t)::value;
+      constexpr int FIRST = LAST ? 12 : 0;                  // the last tile has no next scores to compute
+      const RdAddr ra = rd_addr(kslot(kt + 1), vslot(kt));   // K(kt + 1) for the next scores, V(kt) for this tile's output
+      if constexpr (!LAST) {
+        // K(kt + 2) takes K(kt)'s half of the stage, V(kt + 1) V(kt - 1)'s
         if (kt + 2 < ntiles) stage_kv1<NW, true>(a, head_off, kt + 2, kslot(kt), wave, lane_off(kt + 2));
         stage_kv1<NW, false, PV8>(a, head_off, kt + 1, vslot(kt + 1), wave, lane_off(kt + 1));
       }
-    }
-    bf16x8 p16[4];
-    i32x8 p8, pl8;
-    float tmax = -1.0e30f, m_new, alpha, psum = 0.f;
-    // VALU chunks: softmax of tile kt (chunks 0..11), e4m3 packing of P (chunks 12..19)
-    auto valu_chunk = [&](auto c_t) {
-      constexpr int C = decltype(c_t)::value;
-      if constexpr (C < 2) {                       // running maximum over sub-tile C
+      bf16x8 p16[4];
+      i32x8 p8, pl8;
+      float tmax = -1.0e30f, m_new, alpha, psum = 0.f;
+      // VALU chunks: softmax of tile kt (chunks 0..11), e4m3 packing of P (chunks 12..19)
+      auto valu_chunk = [&](auto c_t) {
+        constexpr int C = decltype(c_t)::value;
+        if constexpr (C < 2) {                       // running maximum over sub-tile C
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          if (TAIL) {
-            const int key = kt * KB + C * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            sc[C][r] = key < a.S ? sc[C][r] : -1.0e30f;
+          for (int r = 0; r < 16; ++r) {
+            if (TAIL) {
+              const int key = kt * KB + C * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+              sc[C][r] = key < a.S ? sc[C][r] : -1.0e30f;
+            }
+            tmax = fmaxf(tmax, sc[C][r]);
           }
-          tmax = fmaxf(tmax, sc[C][r]);
-        }
-        if constexpr (C == 1) {
-          tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
-          m_new = fmaxf(m_run, tmax);
-          alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-          m_run = m_new;
-        }
-      } else if constexpr (C < 10) {               // exponentials of four accumulator registers, fp16 fragment halves
-        constexpr int e = C - 2, kt2 = e >> 2, r4 = e & 3;
+          if constexpr (C == 1) {
+            tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
+            m_new = fmaxf(m_run, tmax);
+            alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+            m_run = m_new;
+          }
+        } else if constexpr (C < 10) {               // exponentials of four accumulator registers, fp16 fragment halves
+          constexpr int e = C - 2, kt2 = e >> 2, r4 = e & 3;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float pv = __builtin_amdgcn_exp2f(sc[kt2][4 * r4 + j] - m_new);
-          sc[kt2][4 * r4 + j] = pv;
-          psum += pv;
-          p16[2 * kt2 + (r4 >> 1)][4 * (r4 & 1) + j] = (short)f32_to_f16(pv);
-        }
-      } else if constexpr (C < 12) {               // rescale of one output tile
-        constexpr int et = C - 10;
+          for (int j = 0; j < 4; ++j) {
+            const float pv = __builtin_amdgcn_exp2f(sc[kt2][4 * r4 + j] - m_new);
+            sc[kt2][4 * r4 + j] = pv;
+            psum += pv;
+            p16[2 * kt2 + (r4 >> 1)][4 * (r4 & 1) + j] = (short)f32_to_f16(pv);
+          }
+        } else if constexpr (C < 12) {               // rescale of one output tile
+          constexpr int et = C - 10;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          oacc[et][r] *= alpha;
-        }
-        if constexpr (et == 1) l_run = l_run * alpha + psum;
-      } else if constexpr (C < 20 && PV8) {        // four accumulator registers -> one dword of each e4m3 operand
-        constexpr int I = C - 12, c2 = I >> 2, r4 = I & 3;
-        float lo[4];
+          for (int r = 0; r < 16; ++r) {
+            oacc[et][r] *= alpha;
+          }
+          if constexpr (et == 1) l_run = l_run * alpha + psum;
+        } else if constexpr (C < 20 && PV8) {        // four accumulator registers -> one dword of each e4m3 operand
+          constexpr int I = C - 12, c2 = I >> 2, r4 = I & 3;
+          float lo[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) lo[j] = __builtin_fmaf(f16_to_f32((bf16_t)p16[2 * c2 + (r4 >> 1)][4 * (r4 & 1) + j]), -1.0f, sc[c2][4 * r4 + j]);
-        p8[4 * c2 + r4] = fp8x4_scaled<kF8P>(sc[c2][4 * r4], sc[c2][4 * r4 + 1], sc[c2][4 * r4 + 2], sc[c2][4 * r4 + 3]);
-        pl8[4 * c2 + r4] = fp8x4_scaled<kF8P + kF8Lo>(lo[0], lo[1], lo[2], lo[3]);
+          for (int j = 0; j < 4; ++j) lo[j] = __builtin_fmaf(f16_to_f32((bf16_t)p16[2 * c2 + (r4 >> 1)][4 * (r4 & 1) + j]), -1.0f, sc[c2][4 * r4 + j]);
+          p8[4 * c2 + r4] = fp8x4_scaled<kF8P>(sc[c2][4 * r4], sc[c2][4 * r4 + 1], sc[c2][4 * r4 + 2], sc[c2][4 * r4 + 3]);
+          pl8[4 * c2 + r4] = fp8x4_scaled<kF8P + kF8Lo>(lo[0], lo[1], lo[2], lo[3]);
+        }
+      };
+      auto mma = [&](auto slot_t, const i32x8& f) {
+        constexpr int SLOT = decltype(slot_t)::value;
+        if constexpr (SLOT < 12) qk_mma(slot_t, f, sn);
+        else if constexpr (SLOT < 20) {
+          constexpr int I = SLOT - 12, kt2 = I >> 2, s2 = (I >> 1) & 1, et = I & 1;
+          const bf16x8 vh = __builtin_bit_cast(bf16x8, (i32x4_t){f[0], f[1], f[2], f[3]});
+          oacc[et] = mfma32<true>(vh, p16[2 * kt2 + s2], oacc[et]);
+        } else {
+          constexpr int I = SLOT - 20, et = I >> 1, lo = I & 1;
+          if constexpr (lo == 0) oacc[et] = mfma32_f8<e8m0(-kF8KV), e8m0(-kF8P - kF8Lo)>(f, pl8, oacc[et]);
+          else oacc[et] = mfma32_f8<e8m0(-kF8KV - kF8Lo), e8m0(-kF8P)>(f, p8, oacc[et]);
+        }
+      };
+      i32x8 ring[RING];
+      [&]<int... P>(std::integer_sequence<int, P...>) { (read_slot(std::integral_constant<int, FIRST + P>{}, ra, ring[(FIRST + P) % RING], I0{}, I0{}), ...); }(std::make_integer_sequence<int, DEPTH>{});
+      if constexpr (LAST) {   // no S^T MFMAs to hide the softmax behind
+        [&]<int... C>(std::integer_sequence<int, C...>) { (valu_chunk(std::integral_constant<int, C>{}), ...); }(std::make_integer_sequence<int, 12>{});
       }
-    };
-    auto mma = [&](auto slot_t, const i32x8& f) {
-      constexpr int SLOT = decltype(slot_t)::value;
-      if constexpr (SLOT < 12) qk_mma(slot_t, f, sn);
-      else if constexpr (SLOT < 20) {
-        constexpr int I = SLOT - 12, kt2 = I >> 2, s2 = (I >> 1) & 1, et = I & 1;
-        const bf16x8 vh = __builtin_bit_cast(bf16x8, (i32x4_t){f[0], f[1], f[2], f[3]});
-        oacc[et] = mfma32<true>(vh, p16[2 * kt2 + s2], oacc[et]);
-      } else {
-        constexpr int I = SLOT - 20, et = I >> 1, lo = I & 1;
-        if constexpr (lo == 0) oacc[et] = mfma32_f8<e8m0(-kF8KV), e8m0(-kF8P - kF8Lo)>(f, pl8, oacc[et]);
-        else oacc[et] = mfma32_f8<e8m0(-kF8KV - kF8Lo), e8m0(-kF8P)>(f, p8, oacc[et]);
-      }
-    };
-    i32x8 ring[RING];
-    [&]<int... P>(std::integer_sequence<int, P...>) { (read_slot(std::integral_constant<int, FIRST + P>{}, ra, ring[(FIRST + P) % RING]), ...); }(std::make_integer_sequence<int, DEPTH>{});
-    if constexpr (LAST) {   // no S^T MFMAs to hide the softmax behind
-      [&]<int... C>(std::integer_sequence<int, C...>) { (valu_chunk(std::integral_constant<int, C>{}), ...); }(std::make_integer_sequence<int, 12>{});
-    }
-    [&]<int... J>(std::integer_sequence<int, J...>) {
-      ([&] {
-        constexpr int I = FIRST + J;
-        if constexpr (I + DEPTH < NSLOT) read_slot(std::integral_constant<int, I + DEPTH>{}, ra, ring[(I + DEPTH) % RING]);
-        if constexpr (!LAST || I >= 12) valu_chunk(std::integral_constant<int, I>{});
-        __builtin_amdgcn_sched_barrier(0);
-        mma(std::integral_constant<int, I>{}, ring[I % RING]);
-        __builtin_amdgcn_sched_barrier(0);
-      }(), ...);
-    }(std::make_integer_sequence<int, NSLOT - FIRST>{});
-    if constexpr (RING3 && !LAST) {
-      // only the loads of the PREVIOUS iteration have to have landed: this iteration issued NK (fp16 groups + e4m3 groups) K and NV V
-      // LDS-DMA instructions per wave (fewer near the end of the key range)
-      constexpr int NK = 8 / NW + 2, NV = 8 / NW;
-      if (kt + 3 < ntiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NK + NV) : "memory");
-      else if (kt + 2 < ntiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NV) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
+      [&]<int... J>(std::integer_sequence<int, J...>) {
+        ([&] {
+          constexpr int I = FIRST + J;
+          if constexpr (I + DEPTH < NSLOT) read_slot(std::integral_constant<int, I + DEPTH>{}, ra, ring[(I + DEPTH) % RING], I0{}, I0{});
+          if constexpr (!LAST || I >= 12) valu_chunk(std::integral_constant<int, I>{});
+          __builtin_amdgcn_sched_barrier(0);
+          mma(std::integral_constant<int, I>{}, ring[I % RING]);
+          __builtin_amdgcn_sched_barrier(0);
+        }(), ...);
+      }(std::make_integer_sequence<int, NSLOT - FIRST>{});
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    };
+    // tiles in pairs so that the two score buffers swap roles without register copies
+    int kt = 0;
+    for (; kt + 2 < ntiles; kt += 2) {
+      iter(std::false_type{}, std::false_type{}, kt, sa, sb);
+      iter(std::false_type{}, std::false_type{}, kt + 1, sb, sa);
     }
-    __syncthreads();
-  };
-  // tiles in pairs so that the two score buffers swap roles without register copies
-  int kt = 0;
-  for (; kt + 2 < ntiles; kt += 2) {
-    iter(std::false_type{}, std::false_type{}, kt, sa, sb);
-    iter(std::false_type{}, std::false_type{}, kt + 1, sb, sa);
-  }
-  if (kt + 2 == ntiles) {
-    iter(std::false_type{}, std::false_type{}, kt, sa, sb);
-    if (a.S % KB) iter(std::true_type{}, std::true_type{}, kt + 1, sb, sa);
-    else iter(std::true_type{}, std::false_type{}, kt + 1, sb, sa);
-  } else {
-    if (a.S % KB) iter(std::true_type{}, std::true_type{}, kt, sa, sb);
-    else iter(std::true_type{}, std::false_type{}, kt, sa, sb);
+    if (kt + 2 == ntiles) {
+      iter(std::false_type{}, std::false_type{}, kt, sa, sb);
+      if (a.S % KB) iter(std::true_type{}, std::true_type{}, kt + 1, sb, sa);
+      else iter(std::true_type{}, std::false_type{}, kt + 1, sb, sa);
+    } else {
+      if (a.S % KB) iter(std::true_type{}, std::true_type{}, kt, sa, sb);
+      else iter(std::true_type{}, std::false_type{}, kt, sa, sb);
+    }
+
   }
 
   const float l_tot = l_run + __shfl_xor(l_run, 32);
