@@ -273,6 +273,18 @@ int awt_op_layernorm(awt_ctx* c, const float* x /*[M,d]*/, const float* gamma, c
 int awt_op_attention(awt_ctx* c, const float* q, const float* k, const float* v, float* o, int B, int H, int S,
                      int terms, void* workspace, size_t ws_bytes, void* stream);
 size_t awt_op_attention_workspace_bytes(int B, int H, int S);
+/* The attention of one encoder layer's training pass on caller tensors: the training form of the forward (row-major o planes and the saved
+ * log-sum-exp), then the backward kernel with the arguments awt_encoder_backward gives it.  No kernel of its own.
+ *   in:  q (already scaled by head_dim^-1/2, as for awt_op_attention), k, v: float32 [B, H, S, 64];  d_o = dL/do: float32 [B, S, H*64]
+ *   out: o_hi / o_lo: bf16 planes [B*S, H*64] of o;  lse2: float32 [B, H, S], log2 of each row's sum of 2^(score log2 e);
+ *        delta: float32 [B, H, S] = rowsum(d_o * o);  g_hi / g_lo: bf16 planes [B*S, 3*H*64] holding dq | dk | dv per row, which is what
+ *        the QKV backward GEMM reads (a value is hi + lo).  dq = qscale * dL/dq, dk and dv are dL/dk and dL/dv.
+ * `terms` = 1 (bf16) or 3 (bf16x3); `grad_terms` = terms, or 1 with terms = 3 (awt_encoder_cfg.backward_terms = 1: the scores stay split-bf16,
+ * the gradient products take one bf16 plane).  Anything else is AWT_ERR_INVALID.  With terms = 1 the lo planes are not written and may be NULL. */
+int awt_op_attention_backward(awt_ctx* c, const float* q, const float* k, const float* v, const float* d_o, void* o_hi, void* o_lo,
+                              float* lse2, float* delta, void* g_hi, void* g_lo, int B, int H, int S, float qscale, int terms,
+                              int grad_terms, void* workspace, size_t ws_bytes, void* stream);
+size_t awt_op_attention_backward_workspace_bytes(int B, int H, int S);
 
 /* ------------------------------------------------------------------------------------------------------
  * Decoder-side operators of the fine-tune step (scope row "next" #1): what `WhisperForConditionalGeneration.forward` runs after

@@ -952,6 +952,13 @@ OpAttentionWs op_attention_layout(void* base, int B, int H, int S) {
   Carver cv(base);
   return {take_planes(cv, n), take_planes(cv, n), take_planes(cv, n), cv.bytes()};
 }
+// awt_op_attention_backward's workspace: the two 2-byte planes of q, of k, of v (head-major) and of dO (row-major)
+struct OpAttentionBwdWs { PlanePair q, k, v, d_o; size_t bytes; };
+OpAttentionBwdWs op_attention_backward_layout(void* base, int B, int H, int S) {
+  const size_t n = (size_t)B * H * S * 64;
+  Carver cv(base);
+  return {take_planes(cv, n), take_planes(cv, n), take_planes(cv, n), take_planes(cv, n), cv.bytes()};
+}
 }  // namespace
 
 extern "C" size_t awt_op_linear_workspace_bytes(int M, int N, int K) { return op_linear_layout(nullptr, M, N, K).bytes; }
@@ -1028,6 +1035,36 @@ extern "C" int awt_op_attention(awt_ctx* c, const float* q, const float* k, cons
     return launch_attention_f16f8(c, P[0], P[1], P[2], F8Planes{nullptr, nullptr, nullptr}, o, nullptr, B, H, S, s);
   }
   return launch_attention(c, pl[0], pl[1], pl[2], pl[3], pl[4], pl[5], nullptr, nullptr, o, nullptr, B, H, S, terms, s);
+}
+
+// What one encoder layer's training pass runs around its attention, on caller tensors: the operand planes, the training form of the forward
+// (row-major o planes and the saved log-sum-exp; forward_layer with `save`), then launch_attention_bwd as awt_encoder_backward calls it.
+extern "C" size_t awt_op_attention_backward_workspace_bytes(int B, int H, int S) { return op_attention_backward_layout(nullptr, B, H, S).bytes; }
+extern "C" int awt_op_attention_backward(awt_ctx* c, const float* q, const float* k, const float* v, const float* d_o, void* o_hi, void* o_lo,
+                                         float* lse2, float* delta, void* g_hi, void* g_lo, int B, int H, int S, float qscale, int terms,
+                                         int grad_terms, void* workspace, size_t ws_bytes, void* stream) {
+  AWT_REQUIRE(terms == PREC_BF16 || terms == PREC_BF16X3, AWT_ERR_INVALID, "op_attention_backward: terms must be 1 (bf16) or 3 (bf16x3)");
+  AWT_REQUIRE(grad_terms == terms || (terms == 3 && grad_terms == 1), AWT_ERR_INVALID, "op_attention_backward: grad_terms must equal terms, or be 1 with terms 3");
+  AWT_REQUIRE(B > 0 && H > 0 && S > 0, AWT_ERR_INVALID, "op_attention_backward: bad shape");
+  AWT_REQUIRE(c && q && k && v && d_o && o_hi && lse2 && delta && g_hi && workspace, AWT_ERR_INVALID, "op_attention_backward: null argument");
+  AWT_REQUIRE(terms == 1 || (o_lo && g_lo), AWT_ERR_INVALID, "op_attention_backward: the lo planes of o and of the gradients are required with terms 3");
+  AWT_REQUIRE(ws_bytes >= awt_op_attention_backward_workspace_bytes(B, H, S), AWT_ERR_WORKSPACE, "op_attention_backward: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n = (int64_t)B * H * S * 64;
+  const OpAttentionBwdWs ws = op_attention_backward_layout(workspace, B, H, S);
+  const PlanePair pl[4] = {ws.q, ws.k, ws.v, ws.d_o};
+  const float* src[4] = {q, k, v, d_o};
+  for (int i = 0; i < 4; ++i) {   // the kernels expect q * log2(e)
+    int rc = launch_split_planes(c, src[i], n, i == 0 ? 1.4426950408889634f : 1.0f, terms, 0, pl[i].hi, pl[i].lo, nullptr, nullptr, s);
+    if (rc) return rc;
+  }
+  bf16_t* const olo = terms == 3 ? (bf16_t*)o_lo : nullptr;   // terms 1: one plane each, as the encoder's buffers have then
+  bf16_t* const glo = terms == 3 ? (bf16_t*)g_lo : nullptr;
+  const auto lo = [&](const PlanePair& p) { return terms == 3 ? p.lo : nullptr; };
+  int rc = launch_attention(c, ws.q.hi, lo(ws.q), ws.k.hi, lo(ws.k), ws.v.hi, lo(ws.v), (bf16_t*)o_hi, olo, nullptr, lse2, B, H, S, terms, s);
+  if (rc) return rc;
+  return launch_attention_bwd(c, ws.q.hi, lo(ws.q), ws.k.hi, lo(ws.k), ws.v.hi, lo(ws.v), (bf16_t*)o_hi, olo, ws.d_o.hi, lo(ws.d_o), lse2, delta,
+                              (bf16_t*)g_hi, glo, B, H, S, qscale, terms, grad_terms, s);
 }
 
 // ------------------------------------------------------------------------------------------------ LoRA fine-tune step

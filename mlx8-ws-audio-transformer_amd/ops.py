@@ -59,6 +59,51 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, precision: str 
     return o
 
 
+def attention_backward_planes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, d_o: torch.Tensor, precision: str = "bf16x3",
+                              grad_precision: Optional[str] = None, qscale: float = 1.0, out: Optional[tuple] = None) -> tuple:
+    """The attention of an encoder layer's training pass (include/awt.h: awt_op_attention_backward) with its outputs as the library writes them:
+    (o_hi, o_lo, lse2, delta, g_hi, g_lo) -- o planes bf16 [B * S, H * 64], lse2 / delta fp32 [B, H, S], gradient planes bf16 [B * S, 3 * H * 64]
+    (dq | dk | dv per row).  precision "bf16": the lo planes are None.  `out`: the same six tensors allocated by the caller (written in place)."""
+    terms = _terms(precision)
+    grad_terms = terms if grad_precision is None else _terms(grad_precision)
+    q, k, v, d_o = (t.float().contiguous() for t in (q, k, v, d_o))
+    B, H, S, hd = q.shape
+    if hd != 64:
+        raise ValueError("head_dim must be 64")
+    if k.shape != q.shape or v.shape != q.shape or d_o.shape != (B, S, H * 64):
+        raise ValueError("attention_backward: k, v must have q's shape [B, H, S, 64] and d_o must be [B, S, H * 64]")
+    L = _lib.lib()
+    if out is None:
+        plane = lambda w: torch.empty((B * S, w), dtype=torch.bfloat16, device=q.device)
+        stat = lambda: torch.empty((B, H, S), dtype=torch.float32, device=q.device)
+        lo = terms != 1
+        out = (plane(H * 64), plane(H * 64) if lo else None, stat(), stat(), plane(3 * H * 64), plane(3 * H * 64) if lo else None)
+    o_hi, o_lo, lse2, delta, g_hi, g_lo = out
+    ws = _lib.workspace(L.awt_op_attention_backward_workspace_bytes(B, H, S), q.device)
+    with torch.cuda.device(q.device):
+        _lib.check(L.awt_op_attention_backward(_lib.ctx(q.device), _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(d_o), _lib.ptr(o_hi), _lib.ptr(o_lo),
+                                               _lib.ptr(lse2), _lib.ptr(delta), _lib.ptr(g_hi), _lib.ptr(g_lo), B, H, S, float(qscale), terms, grad_terms,
+                                               _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
+    return out
+
+
+def attention_backward_join(planes: tuple, B: int, H: int, S: int) -> tuple:
+    """(o [B, S, H * 64], lse2, delta [B, H, S], dq, dk, dv [B, H, S, 64]) in float64 from the six tensors of attention_backward_planes: a value is hi + lo."""
+    o_hi, o_lo, lse2, delta, g_hi, g_lo = planes
+    join = lambda hi, lo: hi.double() if lo is None else hi.double() + lo.double()
+    g = join(g_hi, g_lo).view(B, S, 3, H, 64).permute(2, 0, 3, 1, 4)
+    return join(o_hi, o_lo).view(B, S, H * 64), lse2.double(), delta.double(), g[0].contiguous(), g[1].contiguous(), g[2].contiguous()
+
+
+def attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, d_o: torch.Tensor, precision: str = "bf16x3",
+                       grad_precision: Optional[str] = None, qscale: float = 1.0) -> tuple:
+    """(o, lse2, delta, dq, dk, dv) of softmax(q k^T) v under the upstream gradient d_o, as the encoder's training pass computes them: q (pre-scaled),
+    k, v [B, H, S, 64], d_o [B, S, H * 64].  o is [B, S, H * 64], lse2 (log2 units) and delta = rowsum(d_o * o) are [B, H, S], dq (times qscale), dk, dv are
+    [B, H, S, 64]; all float64, the plane pairs joined.  precision "bf16" or "bf16x3"; grad_precision "bf16" with "bf16x3" is the bf16-gradient option."""
+    B, H, S, _ = q.shape
+    return attention_backward_join(attention_backward_planes(q, k, v, d_o, precision, grad_precision, qscale), B, H, S)
+
+
 def weight_grad(dy: torch.Tensor, x: torch.Tensor, n: Optional[int] = None, k: Optional[int] = None, ycol: int = 0, xcol: int = 0,
                 precision: str = "bf16x3", scale: float = 1.0, out: Optional[torch.Tensor] = None, accumulate: bool = False,
                 row_map: Optional[tuple] = None) -> torch.Tensor:

@@ -58,6 +58,17 @@ def test_op_attention(precision):
     _exact(L.awt_op_attention_workspace_bytes(B, H, S), call, [torch.empty(B, S, H * 64, device="cuda")], [ops.attention(q, k, v, precision)])
 
 
+def test_op_attention_backward():
+    from mlx8_ws_audio_transformer_amd import ops
+    B, H, S = 1, 1, 129                                      # as test_op_attention: eight planes of 16512 bytes
+    q, k, v, d_o = _rand((B, H, S, 64), 1, 0.125), _rand((B, H, S, 64), 2), _rand((B, H, S, 64), 3), _rand((B, S, H * 64), 4)
+    L, s = _lib.lib(), _lib.stream_handle()
+    call = lambda ws, n, *out: L.awt_op_attention_backward(_lib.ctx(), _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(d_o), *(_lib.ptr(t) for t in out), B, H, S,
+                                                           0.125, 3, 3, _lib.ptr(ws), n, s)
+    want = ops.attention_backward_planes(q, k, v, d_o, "bf16x3", qscale=0.125)
+    _exact(L.awt_op_attention_backward_workspace_bytes(B, H, S), call, [torch.empty_like(t) for t in want], list(want))
+
+
 def test_linear_forward_and_backward_input():
     from mlx8_ws_audio_transformer_amd.native_decoder import PackedLinear
     L, s, M, N = _lib.lib(), _lib.stream_handle(), 3, 10

@@ -33,6 +33,17 @@ EXPECTED = {
         ((2, 6, 51), 470016),
         ((0, 6, 51), 0),
     ],
+    # eight planes of B H S 64 2 bytes: q, k, v and dO (recorded from the commit that added the entry point: nothing precedes it)
+    "awt_op_attention_backward_workspace_bytes": [
+        ((64, 12, 1500), 1179648000),
+        ((1, 1, 3), 4096),                # plane 384 bytes
+        ((1, 3, 5), 16384),               # plane 1920 bytes
+        ((2, 6, 51), 626688),
+        ((1, 1, 1), 2048),                # plane 128 bytes
+        ((0, 6, 51), 0),
+        ((2, 0, 51), 0),
+        ((2, 6, 0), 0),
+    ],
     # two planes of batch pad(N, 128) pad(K, 64) 2 bytes (always a multiple of 256)
     "awt_bmm_packed_bytes": [
         ((64, 1500, 768), 301989888),
