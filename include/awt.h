@@ -407,6 +407,23 @@ int awt_op_attention_small_backward_dropout(awt_ctx* c, const float* q, int ldq,
                                             const float* dout, int ldo, const float* lse, float* delta, float* dq, float* dk, float* dv, int B,
                                             int H, int Lq, int Sk, int causal, int causal_off, float drop_p, uint64_t seed, void* stream);
 
+/* Multi-head cross-attention for head_dim 128 without a mask, Lq != Sk (csrc/cross_attention.hip; music2midi.CrossAttentionAdapter):
+ *   o[b, i, h] = softmax_j(128^-1/2 q[b, i, h] . k[b, j, h]) v[b, j, h]
+ * on fp32 row-major operands in place: row (b, i) of q at q + (b Lq + i) ldq + 128 h, row (b, j) of k / v at k + (b Sk + j) ldk + 128 h (k and v may be
+ * the two halves of one [B Sk, 2 H 128] matrix), o like q with ldo.  The score scale is applied inside.  A flash-style kernel on the bf16 MFMAs: terms = 3
+ * splits every operand (q, k, v and the probabilities of each 64-key tile) into bf16 hi + lo and forms three products, terms = 1 one; online softmax with
+ * fp32 running max, sum and output.  lse [B, H, Lq] (optional, natural log) feeds the backward.  Any Lq, Sk >= 1.
+ * Backward: dq (layout of q), dk / dv (layout of k / v), every element of the B x Lq x H x 128 and B x Sk x H x 128 blocks written; P is recomputed from lse,
+ * nothing of size Lq x Sk is stored; o and dout are pitched ldo.  A rowsum(dout * o) launch, a dq launch and a dk / dv launch; no atomics: two runs give the
+ * same bits.  Refused with AWT_ERR_INVALID: a pitch below H * 128 or not a multiple of 4, terms other than 1 or 3, a null pointer, tensors not 16-byte
+ * aligned, a workspace smaller than awt_op_cross_attention_workspace_bytes (answers without a GPU; the forward needs none). */
+size_t awt_op_cross_attention_workspace_bytes(int B, int H, int Lq, int Sk, int backward);
+int awt_op_cross_attention(awt_ctx* c, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo, float* lse,
+                           int B, int H, int Lq, int Sk, int terms, void* workspace, size_t ws_bytes, void* stream);
+int awt_op_cross_attention_backward(awt_ctx* c, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o,
+                                    const float* dout, int ldo, const float* lse, float* dq, float* dk, float* dv, int B, int H, int Lq, int Sk,
+                                    int terms, void* workspace, size_t ws_bytes, void* stream);
+
 /* Causal attention of Lq new query rows per batch over a preallocated decode cache: keys / values of batch b, position j at
  * k + b kv_batch_stride + j ldkv + 64 h (likewise v), T live positions (T >= Lq; query i sees keys j <= T - Lq + i).  q / o as in
  * awt_op_attention_small.  The cache is [rows, Tmax, 2 d] per layer, so kv_batch_stride = Tmax ldkv (csrc/decoder_ops.hip). */

@@ -119,6 +119,9 @@ _SIGNATURES = {
     "awt_op_attention_small_backward": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "awt_op_attention_small_dropout": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, C.c_float, C.c_uint64, _vp]),
     "awt_op_attention_small_backward_dropout": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_float, C.c_uint64, _vp]),
+    "awt_op_cross_attention_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "awt_op_cross_attention": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "awt_op_cross_attention_backward": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "awt_op_attention_cached": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i, _vp]),
     "awt_select_tokens_workspace_bytes": (_sz, [_i, _i, _i]),
     "awt_op_select_tokens": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

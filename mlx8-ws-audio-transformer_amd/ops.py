@@ -131,3 +131,49 @@ def weight_grad(dy: torch.Tensor, x: torch.Tensor, n: Optional[int] = None, k: O
                                         1 if precision == "bf16" else 3, float(scale), int(accumulate), out.data_ptr(), out.stride(0), out.stride(1),
                                         _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
     return out
+
+
+def _at(pair) -> int:
+    """Device address of element `col` of a (tensor, column offset) pair over a row-major fp32 matrix."""
+    t, col = pair
+    if t.dtype != torch.float32:
+        raise ValueError("libawt's pitched operators take float32 tensors")
+    return _lib.ptr(t) + 4 * int(col)
+
+
+def cross_attention_workspace_bytes(B: int, H: int, Lq: int, Sk: int, backward: bool = False) -> int:
+    """Workspace of `cross_attention` / `cross_attention_backward`; answers without a GPU."""
+    return int(_lib.lib().awt_op_cross_attention_workspace_bytes(int(B), int(H), int(Lq), int(Sk), int(backward)))
+
+
+def cross_attention(q, ldq: int, k, ldk: int, v, ldv: int, B: int, H: int, Lq: int, Sk: int, precision="bf16x3", want_lse: bool = True,
+                    o=None, ldo: Optional[int] = None, lse: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """softmax(128^-1/2 q k^T) v for head_dim 128, no mask (include/awt.h: awt_op_cross_attention).  q / k / v (and o, when given with its pitch ldo): (tensor,
+    column offset) pairs over row-major fp32 matrices, row (b, i) of q at pitch ldq, row (b, j) of k / v at ldk / ldv, head h in columns 128 h ...  Returns
+    (o [B * Lq, H * 128] unless given, lse [B, H, Lq] or None).  precision: "bf16x3", "bf16", or the operator's `terms` as an int."""
+    terms = precision if isinstance(precision, int) else _terms(precision)
+    dev = q[0].device
+    if o is None:
+        o, ldo = (torch.empty((B * Lq, H * 128), dtype=torch.float32, device=dev), 0), H * 128
+    if lse is None and want_lse:
+        lse = torch.empty((B, H, Lq), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_op_cross_attention_workspace_bytes(B, H, Lq, Sk, 0), dev) if workspace is None else workspace
+    with torch.cuda.device(dev):
+        _lib.check(L.awt_op_cross_attention(_lib.ctx(dev), _at(q), int(ldq), _at(k), int(ldk), _at(v), int(ldv), _at(o), int(ldo), _lib.ptr(lse), B, H, Lq, Sk,
+                                            int(terms), _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
+    return o[0], lse
+
+
+def cross_attention_backward(q, ldq: int, k, ldk: int, v, ldv: int, o, dout, ldo: int, lse: torch.Tensor, dq, dk, dv, B: int, H: int, Lq: int, Sk: int,
+                             precision="bf16x3", workspace: Optional[torch.Tensor] = None) -> None:
+    """Writes dq / dk / dv at (tensor, column offset) destinations laid out like q / k / v (include/awt.h: awt_op_cross_attention_backward); o and dout are
+    (tensor, column offset) pairs at pitch ldo, lse the forward's [B, H, Lq]."""
+    terms = precision if isinstance(precision, int) else _terms(precision)
+    dev = q[0].device
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_op_cross_attention_workspace_bytes(B, H, Lq, Sk, 1), dev) if workspace is None else workspace
+    with torch.cuda.device(dev):
+        _lib.check(L.awt_op_cross_attention_backward(_lib.ctx(dev), _at(q), int(ldq), _at(k), int(ldk), _at(v), int(ldv), _at(o), _at(dout), int(ldo),
+                                                     _lib.ptr(lse), _at(dq), _at(dk), _at(dv), B, H, Lq, Sk, int(terms), _lib.ptr(ws), ws.numel(),
+                                                     _lib.stream_handle()))
