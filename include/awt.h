@@ -286,6 +286,38 @@ int awt_op_attention_backward(awt_ctx* c, const float* q, const float* k, const 
                               int grad_terms, void* workspace, size_t ws_bytes, void* stream);
 size_t awt_op_attention_backward_workspace_bytes(int B, int H, int S);
 
+/* One GEMM launch with any of its fused epilogues on caller tensors, with the arguments the encoder gives it.  No kernel of its own: the fp32
+ * operands are written as operand planes (as awt_op_linear does, including the upload-time detection of fp16-exact weights with terms 4 and 5), one
+ * launch follows, and the bytes the kernel wrote are the result -- nothing is converted back.  The tuning knobs "gemm_tile", "gemm_mfma16" and
+ * "gemm_pp" = 2 are honoured as by awt_op_linear (the ping-pong kernel takes terms 5, one plain dense segment, N % 256 == 0, K >= 128 and five of
+ * the epilogues; under "gemm_pp" = 2 any other epilogue with such a shape is refused).
+ *   x [x_rows, ldx], w [N, ldw], bias [N] or NULL: float32.  C[m, n] = sum over the nseg <= 3 K segments of x[row_i(m), xcol_i .. + k_i) . w[n, wcol_i .. + k_i),
+ *   row_i(m) = (m / rows_out) * rows_in + (m % rows_out) * row_mul + row_add, a row outside [0, rows_in) of its group reading as zero (rows_in ==
+ *   row_mul * rows_out).  ldx, ldw, xcol, wcol and k are multiples of 64.  Two segments express the LoRA form [x | u] [W | B]^T, three the
+ *   stride-2 conv stem.
+ *   epi (GemmEpilogue of csrc/common.h): 0 out_f32 = C + bias;  1 out_f32 = resid + C + bias (resid may be out_f32);  2 planes of (C + bias) scale;
+ *   3 planes of gelu(C + bias);  4 head-major q | k | v planes [3][M / S][H][S][64] (N == 3 H 64, M % S == 0, plane stride M H 64 elements), the q
+ *   columns times scale;  5 out_f32 = gelu(C + bias) + pos[m % rows_pos];  6 as 3, and bf16 planes out_hi2 / out_lo2 of C + bias;  7 planes of
+ *   C gelu'(pre), pre = pre_hi + pre_lo (bf16 planes, pitch ldo; pre_lo may be NULL).
+ *   Plane outputs (pitch ldo, 0 = N): terms 1 / 3 bf16, 2 / 4 fp16, out_hi (+ out_lo with terms 3 / 4); terms 5: out_hi = fp16, out_hi8 = e4m3(v 2^s)
+ *   (may be NULL), out_lo8 = e4m3((v - fp16(v)) 2^(s + 11)), s = -2 (q: 2, k and v: 0); skip_v8 leaves v's two e4m3 images unwritten;
+ *   split_lines (ping-pong kernel, epi 2 / 3): out_ilv instead, [M][N / 64] pairs of 128-byte lines: 64 fp16, then 64 hi8 | 64 lo8.
+ *   Columns >= n_valid (0 = N; a multiple of 4, of 8 with terms 5) and rows >= M are not written.  m_pick > 0: the kernel is chosen as for a launch of
+ *   m_pick rows.
+ * Whatever the launch itself would refuse is AWT_ERR_INVALID here, before anything is written. */
+typedef struct awt_linear_fused_args {
+  int32_t M, N, terms, epi, nseg;
+  int32_t x_rows, ldx, ldw;
+  int32_t seg_xcol[3], seg_wcol[3], seg_k[3], seg_rows_out[3], seg_rows_in[3], seg_row_mul[3], seg_row_add[3];
+  int32_t rows_pos, S, H, skip_v8, n_valid, m_pick, split_lines, ldo;
+  float scale;
+  const float* x; const float* w; const float* bias;
+  const float* resid; const float* pos; const void* pre_hi; const void* pre_lo;
+  float* out_f32; void* out_hi; void* out_lo; void* out_hi8; void* out_lo8; void* out_ilv; void* out_hi2; void* out_lo2;
+} awt_linear_fused_args;
+int awt_op_linear_fused(awt_ctx* c, const awt_linear_fused_args* a, void* workspace, size_t ws_bytes, void* stream);
+size_t awt_op_linear_fused_workspace_bytes(int x_rows, int ldx, int N, int ldw);
+
 /* ------------------------------------------------------------------------------------------------------
  * Decoder-side operators of the fine-tune step (scope row "next" #1): what `WhisperForConditionalGeneration.forward` runs after
  * the encoder -- /root/reference/AB/fineTune.py:131,186-199 -> HF:modeling_whisper.py:416-507 (decoder layer), :649-797

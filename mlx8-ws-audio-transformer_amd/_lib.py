@@ -32,6 +32,15 @@ class EncoderCfg(C.Structure):
                 ("train_base", C.c_int32)]
 
 
+class LinearFusedArgs(C.Structure):
+    """awt_linear_fused_args of include/awt.h."""
+    _fields_ = ([(n, C.c_int32) for n in ("M", "N", "terms", "epi", "nseg", "x_rows", "ldx", "ldw")] +
+                [(n, C.c_int32 * 3) for n in ("seg_xcol", "seg_wcol", "seg_k", "seg_rows_out", "seg_rows_in", "seg_row_mul", "seg_row_add")] +
+                [(n, C.c_int32) for n in ("rows_pos", "S", "H", "skip_v8", "n_valid", "m_pick", "split_lines", "ldo")] + [("scale", C.c_float)] +
+                [(n, C.c_void_p) for n in ("x", "w", "bias", "resid", "pos", "pre_hi", "pre_lo", "out_f32", "out_hi", "out_lo", "out_hi8", "out_lo8", "out_ilv",
+                                           "out_hi2", "out_lo2")])
+
+
 MFMA_PER_PAIR = {"bf16": 1, "fp16": 1, "bf16x3": 3, "fp16x3": 3, "f16f8": 2}   # MFMA-equivalents issued per fragment pair, by precision mode
 BWD_ACCUMULATE, BWD_ALLREDUCE = 1, 2
 COMM_ID_BYTES = 128
@@ -81,6 +90,8 @@ _SIGNATURES = {
     "awt_conv_stem_positions": (_i, [_i, _i]),
     "awt_op_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "awt_op_linear_workspace_bytes": (_sz, [_i, _i, _i]),
+    "awt_op_linear_fused": (_i, [_vp, C.POINTER(LinearFusedArgs), _vp, _sz, _vp]),
+    "awt_op_linear_fused_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "awt_op_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "awt_op_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "awt_op_attention_workspace_bytes": (_sz, [_i, _i, _i]),

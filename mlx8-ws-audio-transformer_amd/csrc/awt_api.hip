@@ -940,10 +940,33 @@ struct OpLinearWs {
   char* x_ilv() const { return (char*)x.hi; }
   char* w_pp() const { return (char*)w.hi; }
 };
-OpLinearWs op_linear_layout(void* base, int M, int N, int K) {
+// x [M, ldx] and w [N, K] with pitches of their own (awt_op_linear_fused: the conv stem's x [B 2 S, Cin] against w [N, 3 Cin]); awt_op_linear has ldx == K
+OpLinearWs op_linear_layout(void* base, int M, int ldx, int N, int K) {
   const size_t sb = ((size_t)N + 255) / 256 * 256 * K * 2;      // the 16-row w copies cover whole 256-column tiles
   Carver cv(base);
-  return {take_planes(cv, (size_t)M * K), take_planes(cv, (size_t)N * K), cv.take<int>(256), cv.take<bf16_t>(sb), cv.take<uint8_t>(sb), 2 * align_up(sb), cv.bytes()};
+  return {take_planes(cv, (size_t)M * ldx), take_planes(cv, (size_t)N * K), cv.take<int>(256), cv.take<bf16_t>(sb), cv.take<uint8_t>(sb), 2 * align_up(sb), cv.bytes()};
+}
+OpLinearWs op_linear_layout(void* base, int M, int N, int K) { return op_linear_layout(base, M, K, N, K); }
+// w [N, K] fp32 as the operand planes of `terms` in the workspace's w pieces (fragment-major; f16f8: also the 16-row copies)
+int op_linear_pack_weight(awt_ctx* c, const float* w, int N, int K, int terms, const OpLinearWs& ws, Planes& pw, hipStream_t s) {
+  pw.hi = ws.w.hi; pw.lo = ws.w.lo; pw.x8 = (uint8_t*)pw.lo + (size_t)N * K; pw.rows = N; pw.ld = K;
+  if (terms == PREC_F16F8 || terms == PREC_F16X3) {   // as awt_encoder_set_weight does: fp16-exact weights take the GEMM without the x_hi w_lo product
+    int host = 1;
+    if (hipMemsetAsync(ws.flag, 0, sizeof(int), s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear: flag reset failed");
+    if (terms == PREC_F16F8) {
+      pw.s_rows = ((int64_t)N + 255) / 256 * 256;
+      pw.s16 = ws.s16; pw.s8 = ws.s8;
+      if (N % 256 != 0) {   // the rows beyond N are read by the last column tile (never stored): keep them finite
+        if (hipMemsetAsync(ws.s16, 0, ws.s_bytes, s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear: weight copy reset failed");
+      }
+    }
+    int rc = launch_pack_weight(c, w, N, K, 1, K, 0, 0, 1.0f, pw.hi, pw.lo, pw.x8, terms, s, ws.flag, pw.s16, pw.s8); if (rc) return rc;
+    if (hipMemcpyAsync(&host, ws.flag, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+      return awt_fail(AWT_ERR_HIP, "op_linear: flag read-back failed");
+    pw.exact16 = host == 0;
+    return AWT_OK;
+  }
+  return launch_pack_weight(c, w, N, K, 1, K, 0, 0, 1.0f, pw.hi, pw.lo, pw.x8, terms, s);     // fragment-major
 }
 // awt_op_attention's workspace: the two 2-byte planes of q, of k and of v
 struct OpAttentionWs { PlanePair q, k, v; size_t bytes; };
@@ -984,27 +1007,81 @@ extern "C" int awt_op_linear(awt_ctx* c, const float* x, const float* w, const f
   }
   const Act ax = make_act(ws.x.hi, ws.x.lo, (size_t)M * K, terms);
   int rc = launch_split_planes(c, x, (int64_t)M * K, 1.0f, terms, kF8Act, ws.x.hi, ws.x.lo, ax.hi8, ax.lo8, s); if (rc) return rc;
-  Planes pw; pw.hi = ws.w.hi; pw.lo = ws.w.lo; pw.x8 = (uint8_t*)pw.lo + (size_t)N * K; pw.rows = N; pw.ld = K;
-  if (terms == PREC_F16F8 || terms == PREC_F16X3) {   // as awt_encoder_set_weight does: fp16-exact weights take the GEMM without the x_hi w_lo product
-    int host = 1;
-    if (hipMemsetAsync(ws.flag, 0, sizeof(int), s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear: flag reset failed");
-    if (terms == PREC_F16F8) {
-      pw.s_rows = ((int64_t)N + 255) / 256 * 256;
-      pw.s16 = ws.s16; pw.s8 = ws.s8;
-      if (N % 256 != 0) {   // the rows beyond N are read by the last column tile (never stored): keep them finite
-        if (hipMemsetAsync(ws.s16, 0, ws.s_bytes, s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear: weight copy reset failed");
-      }
-    }
-    rc = launch_pack_weight(c, w, N, K, 1, K, 0, 0, 1.0f, pw.hi, pw.lo, pw.x8, terms, s, ws.flag, pw.s16, pw.s8); if (rc) return rc;
-    if (hipMemcpyAsync(&host, ws.flag, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-      return awt_fail(AWT_ERR_HIP, "op_linear: flag read-back failed");
-    pw.exact16 = host == 0;
-  } else {
-    rc = launch_pack_weight(c, w, N, K, 1, K, 0, 0, 1.0f, pw.hi, pw.lo, pw.x8, terms, s); if (rc) return rc;     // fragment-major
-  }
+  Planes pw;
+  rc = op_linear_pack_weight(c, w, N, K, terms, ws, pw, s); if (rc) return rc;
   GemmSeg sg = seg_plain(ax, K, pw, 0, K, M);
   GemmOut o{}; o.f32 = y; o.ldo = N; o.bias = bias; o.n_valid = N;
   return launch_gemm(c, M, N, &sg, 1, terms, EPI_F32, o, s);
+}
+
+extern "C" size_t awt_op_linear_fused_workspace_bytes(int x_rows, int ldx, int N, int ldw) { return op_linear_layout(nullptr, x_rows, ldx, N, ldw).bytes; }
+extern "C" int awt_op_linear_fused(awt_ctx* c, const awt_linear_fused_args* a, void* workspace, size_t ws_bytes, void* stream) {
+  AWT_REQUIRE(c && a && a->x && a->w && workspace, AWT_ERR_INVALID, "op_linear_fused: null argument");
+  const int M = a->M, N = a->N, terms = a->terms, epi = a->epi, nseg = a->nseg;
+  AWT_REQUIRE(prec_known(terms), AWT_ERR_INVALID, "op_linear_fused: terms must be 1 (bf16), 2 (fp16), 3 (bf16x3), 4 (fp16x3) or 5 (f16f8)");
+  AWT_REQUIRE(epi >= EPI_F32 && epi <= EPI_BF16_DGELU, AWT_ERR_INVALID, "op_linear_fused: unknown epilogue");
+  AWT_REQUIRE(M > 0 && N > 0 && N % 128 == 0 && nseg >= 1 && nseg <= 3, AWT_ERR_INVALID, "op_linear_fused: N % 128 == 0 and 1..3 K segments required");
+  AWT_REQUIRE(a->x_rows > 0 && a->ldx > 0 && a->ldx % 64 == 0 && a->ldw > 0 && a->ldw % 64 == 0, AWT_ERR_INVALID, "op_linear_fused: ldx and ldw must be positive multiples of 64");
+  for (int i = 0; i < nseg; ++i) {
+    const int k = a->seg_k[i], xc = a->seg_xcol[i], wc = a->seg_wcol[i], ro = a->seg_rows_out[i], ri = a->seg_rows_in[i], rm = a->seg_row_mul[i];
+    AWT_REQUIRE(k > 0 && k % 64 == 0 && xc >= 0 && xc % 64 == 0 && wc >= 0 && wc % 64 == 0 && xc + k <= a->ldx && wc + k <= a->ldw, AWT_ERR_INVALID,
+                "op_linear_fused: a K segment must be a 64-aligned column slice of x and of w");
+    AWT_REQUIRE(ro > 0 && ri > 0 && rm > 0 && (int64_t)rm * ro == ri, AWT_ERR_INVALID, "op_linear_fused: bad row map (rows_in must be row_mul * rows_out)");
+    AWT_REQUIRE((int64_t)((M - 1) / ro + 1) * ri <= a->x_rows, AWT_ERR_INVALID, "op_linear_fused: the row map reads beyond x_rows");
+  }
+  const bool f8 = terms == PREC_F16F8, planes_out = !(epi == EPI_F32 || epi == EPI_F32_RESID || epi == EPI_F32_GELU_POS);
+  const int n_valid = a->n_valid > 0 ? a->n_valid : N, ldo = a->ldo > 0 ? a->ldo : N;
+  AWT_REQUIRE(a->n_valid >= 0 && n_valid <= N && n_valid % (f8 ? 8 : 4) == 0 && ldo >= n_valid && ldo % 8 == 0, AWT_ERR_INVALID,
+              "op_linear_fused: n_valid must be a multiple of 4 (of 8 with terms 5) in (0, N], ldo a multiple of 8 that holds it");
+  AWT_REQUIRE(a->m_pick >= 0, AWT_ERR_INVALID, "op_linear_fused: m_pick must not be negative");
+  // the ping-pong kernel (tuning knob "gemm_pp" = 2), as awt_op_linear takes it: one plain dense segment of a shape it supports
+  const bool plain = nseg == 1 && a->seg_xcol[0] == 0 && a->seg_wcol[0] == 0 && a->seg_k[0] == a->ldx && a->ldx == a->ldw && a->x_rows == M && a->seg_rows_out[0] == M &&
+                     a->seg_rows_in[0] == M && a->seg_row_mul[0] == 1 && a->seg_row_add[0] == 0;
+  const bool pp_shape = f8 && awt_gemm_pp_mode() == 2 && plain && gemm_pp_supported(M, N, a->ldx, EPI_F32);
+  AWT_REQUIRE(!pp_shape || gemm_pp_supported(M, N, a->ldx, epi), AWT_ERR_INVALID, "op_linear_fused: the ping-pong kernel does not have this epilogue");
+  AWT_REQUIRE(!a->split_lines || (pp_shape && a->out_ilv && (epi == EPI_BF16 || epi == EPI_BF16_GELU) && ldo == N && n_valid == N), AWT_ERR_INVALID,
+              "op_linear_fused: a split-line output is a dense [M, N] activation of the ping-pong kernel's EPI_BF16 / EPI_BF16_GELU");
+  if (!planes_out) AWT_REQUIRE(a->out_f32 && (epi != EPI_F32_RESID || a->resid) && (epi != EPI_F32_GELU_POS || (a->pos && a->rows_pos > 0)), AWT_ERR_INVALID,
+                               "op_linear_fused: null fp32 output or side input");
+  else if (!a->split_lines) AWT_REQUIRE(a->out_hi && (prec_products(terms) == 1 || (f8 ? a->out_lo8 : a->out_lo)), AWT_ERR_INVALID, "op_linear_fused: null output plane");
+  if (epi == EPI_BF16_GELU_SAVE) AWT_REQUIRE(a->out_hi2 && (prec_products(terms) == 1 || a->out_lo2), AWT_ERR_INVALID, "op_linear_fused: null pre-activation plane");
+  if (epi == EPI_BF16_DGELU) AWT_REQUIRE(a->pre_hi, AWT_ERR_INVALID, "op_linear_fused: null saved pre-activation");
+  if (epi == EPI_QKV) AWT_REQUIRE(a->S > 0 && a->H > 0 && N == 3 * a->H * 64 && M % a->S == 0, AWT_ERR_INVALID, "op_linear_fused: EPI_QKV needs N == 3 H 64 and M % S == 0");
+  AWT_REQUIRE(ws_bytes >= awt_op_linear_fused_workspace_bytes(a->x_rows, a->ldx, N, a->ldw), AWT_ERR_WORKSPACE, "op_linear_fused: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const OpLinearWs ws = op_linear_layout(workspace, a->x_rows, a->ldx, N, a->ldw);
+
+  GemmOut o{};
+  o.f32 = a->out_f32; o.resid = a->resid; o.ldo = ldo; o.bias = a->bias; o.n_valid = n_valid; o.scale = a->scale; o.m_pick = a->m_pick;
+  o.pos = a->pos; o.rows_pos = a->rows_pos; o.pre_hi = (const bf16_t*)a->pre_hi; o.pre_lo = (const bf16_t*)a->pre_lo;
+  if (planes_out) {   // one 2-byte plane with a single product, as the encoder's buffers have then
+    o.hi = (bf16_t*)a->out_hi; o.lo = (!f8 && prec_products(terms) == 3) ? (bf16_t*)a->out_lo : nullptr;
+    if (f8) { o.hi8 = (uint8_t*)a->out_hi8; o.lo8 = (uint8_t*)a->out_lo8; }
+    if (epi == EPI_BF16_GELU_SAVE) { o.hi2 = (bf16_t*)a->out_hi2; o.lo2 = prec_products(terms) == 3 ? (bf16_t*)a->out_lo2 : nullptr; }
+    if (a->split_lines) { o.hi = nullptr; o.hi8 = o.lo8 = nullptr; o.ilv = (char*)a->out_ilv; }
+  }
+  if (epi == EPI_QKV) { o.S = a->S; o.H = a->H; o.plane_stride = (int64_t)M * a->H * 64; o.skip_v8 = (f8 && a->skip_v8) ? 1 : 0; }
+
+  const int64_t nx = (int64_t)a->x_rows * a->ldx;
+  if (pp_shape) {
+    const int K = a->ldx;
+    Act ai; ai.ilv = ws.x_ilv();
+    int rcp = launch_split_planes(c, a->x, nx, 1.0f, terms, kF8Act, nullptr, nullptr, nullptr, nullptr, s, ai.ilv); if (rcp) return rcp;
+    if (hipMemsetAsync(ws.w_pp(), 0, gemm_pp_weight_bytes(N, K), s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear_fused: weight image reset failed");
+    rcp = launch_pack_weight_pp(c, a->w, N, K, 0, ws.w_pp(), s); if (rcp) return rcp;
+    Planes pwp; pwp.pp = ws.w_pp(); pwp.rows = N; pwp.ld = K;
+    return launch_gemm_pp(c, M, N, seg_plain(ai, K, pwp, 0, K, M), (GemmEpilogue)epi, o, s);
+  }
+  const Act ax = make_act(ws.x.hi, ws.x.lo, (size_t)nx, terms);
+  int rc = launch_split_planes(c, a->x, nx, 1.0f, terms, kF8Act, ws.x.hi, ws.x.lo, ax.hi8, ax.lo8, s); if (rc) return rc;
+  Planes pw;
+  rc = op_linear_pack_weight(c, a->w, N, a->ldw, terms, ws, pw, s); if (rc) return rc;
+  GemmSeg sg[3];
+  for (int i = 0; i < nseg; ++i) {
+    sg[i] = seg_plain(act_offset(ax, a->seg_xcol[i]), a->ldx, pw, a->seg_wcol[i], a->seg_k[i], M);
+    sg[i].rows_out = a->seg_rows_out[i]; sg[i].rows_in = a->seg_rows_in[i]; sg[i].row_mul = a->seg_row_mul[i]; sg[i].row_add = a->seg_row_add[i];
+  }
+  return launch_gemm(c, M, N, sg, nseg, terms, (GemmEpilogue)epi, o, s);
 }
 
 extern "C" int awt_op_layernorm(awt_ctx* c, const float* x, const float* gamma, const float* beta, float* y, int M, int d,

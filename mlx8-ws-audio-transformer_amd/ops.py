@@ -2,6 +2,7 @@
 Used by the per-kernel parity tests; each raises if the library or the GPU is missing."""
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -31,6 +32,45 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
         _lib.check(L.awt_op_linear(_lib.ctx(x.device), _lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y), M, N, K,
                                    terms, _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
     return y
+
+
+# GemmEpilogue of csrc/common.h
+EPILOGUES = {"f32": 0, "f32_resid": 1, "planes": 2, "gelu": 3, "qkv": 4, "gelu_pos": 5, "gelu_save": 6, "dgelu": 7}
+
+
+def linear_fused_workspace_bytes(x_rows: int, ldx: int, N: int, ldw: int) -> int:
+    """Workspace of `linear_fused`; answers without a GPU."""
+    return int(_lib.lib().awt_op_linear_fused_workspace_bytes(int(x_rows), int(ldx), int(N), int(ldw)))
+
+
+def linear_fused(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], epi, precision, out: dict, M: Optional[int] = None, segs=None, *,
+                 resid: Optional[torch.Tensor] = None, pos: Optional[torch.Tensor] = None, rows_pos: int = 0, pre: tuple = (None, None), scale: float = 1.0,
+                 S: int = 0, H: int = 0, skip_v8: bool = False, n_valid: int = 0, m_pick: int = 0, split_lines: bool = False, ldo: int = 0,
+                 workspace: Optional[torch.Tensor] = None, ws_bytes: Optional[int] = None) -> None:
+    """One GEMM launch with a fused epilogue (include/awt.h: awt_op_linear_fused); the kernel's raw bytes land in the caller's tensors `out`, a dict over
+    "f32", "hi", "lo", "hi8", "lo8", "ilv", "hi2", "lo2" (any dtype; nothing is converted).  x [x_rows, ldx], w [N, ldw] fp32; segs: up to three
+    (xcol, wcol, k, rows_out, rows_in, row_mul, row_add), default one plain segment over all of x; epi: a name of EPILOGUES or its number; precision: a name
+    or the operator's `terms`; pre: the (hi, lo) bf16 planes "dgelu" reads.  Raises _lib.AwtError where the library refuses the call."""
+    terms = precision if isinstance(precision, int) else _terms(precision)
+    x_rows, ldx = x.shape
+    N, ldw = w.shape
+    M = x_rows if M is None else M
+    segs = [(0, 0, ldx, M, M, 1, 0)] if segs is None else list(segs)
+    a = _lib.LinearFusedArgs()
+    a.M, a.N, a.terms, a.epi, a.nseg = M, N, terms, EPILOGUES.get(epi, epi), len(segs)
+    a.x_rows, a.ldx, a.ldw = x_rows, ldx, ldw
+    for i, sg in enumerate(segs[:3]):
+        for name, value in zip(("seg_xcol", "seg_wcol", "seg_k", "seg_rows_out", "seg_rows_in", "seg_row_mul", "seg_row_add"), sg):
+            getattr(a, name)[i] = int(value)
+    a.rows_pos, a.S, a.H, a.skip_v8, a.n_valid, a.m_pick, a.split_lines, a.ldo = rows_pos, S, H, int(skip_v8), n_valid, m_pick, int(split_lines), ldo
+    a.scale = float(scale)
+    a.x, a.w, a.bias, a.resid, a.pos, a.pre_hi, a.pre_lo = (_lib.ptr(t) for t in (x, w, bias, resid, pos, pre[0], pre[1]))
+    for key in ("f32", "hi", "lo", "hi8", "lo8", "ilv", "hi2", "lo2"):
+        setattr(a, "out_" + key, _lib.ptr(out.get(key)))
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_op_linear_fused_workspace_bytes(x_rows, ldx, N, ldw), x.device) if workspace is None else workspace
+    with torch.cuda.device(x.device):
+        _lib.check(L.awt_op_linear_fused(_lib.ctx(x.device), ctypes.byref(a), _lib.ptr(ws), ws.numel() if ws_bytes is None else int(ws_bytes), _lib.stream_handle()))
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:

@@ -48,6 +48,32 @@ def test_op_linear(precision):
     _exact(L.awt_op_linear_workspace_bytes(M, N, K), call, [torch.empty(M, N, device="cuda")], [ops.linear(x, w, b, precision)])
 
 
+@pytest.mark.parametrize("precision,form", [("bf16x3", "conv"), ("fp16x3", "lora"), ("f16f8", "lora"), ("f16f8", "conv")])
+def test_op_linear_fused(precision, form):
+    """The conv stem's three segments over x [B 2 S, Cin] and w [N, 3 Cin], and the LoRA form [x | u] [W | B]^T: x and w pieces of different sizes."""
+    from mlx8_ws_audio_transformer_amd import ops
+    if form == "conv":
+        S, Cin, N = 3, 64, 128                               # x planes of 6 * 64 * 2 = 768 bytes
+        x, w, M = _rand((2 * S, Cin), 1), _rand((N, 3 * Cin), 2, (3 * Cin) ** -0.5), S
+        segs, kw = [(0, t * Cin, Cin, S, 2 * S, 2, t - 1) for t in range(3)], dict(pos=_rand((S, N), 4), rows_pos=S)
+        epi = "gelu_pos"
+    else:
+        M, N, K = 3, 128, 64                                 # x planes of 3 * 128 * 2 = 768 bytes
+        x, w = _rand((M, K + 64), 1), _rand((N, K + 64), 2, K ** -0.5)
+        segs, kw, epi = [(0, 0, K, M, M, 1, 0), (K, K, 64, M, M, 1, 0)], dict(resid=_rand((M, N), 4)), "f32_resid"
+    b = _rand((N,), 3)
+    want = torch.empty(M, N, device="cuda")
+    ops.linear_fused(x, w, b, epi, precision, {"f32": want}, M=M, segs=segs, **kw)
+
+    def call(ws, n, y):
+        try:
+            ops.linear_fused(x, w, b, epi, precision, {"f32": y}, M=M, segs=segs, workspace=ws, ws_bytes=n, **kw)
+        except _lib.AwtError as e:
+            return e.code
+        return 0
+    _exact(ops.linear_fused_workspace_bytes(x.shape[0], x.shape[1], N, w.shape[1]), call, [torch.empty(M, N, device="cuda")], [want])
+
+
 @pytest.mark.parametrize("precision", ["bf16x3", "f16f8"])
 def test_op_attention(precision):
     from mlx8_ws_audio_transformer_amd import ops

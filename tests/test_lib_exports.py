@@ -30,6 +30,7 @@ def test_version_and_workspace_queries_need_no_gpu(built):
     assert b"gfx950" in built.awt_version()
     assert built.awt_logmel_workspace_bytes(64) >= 256
     assert built.awt_op_linear_workspace_bytes(128, 128, 64) > 0
+    assert built.awt_op_linear_fused_workspace_bytes(128, 64, 128, 64) == built.awt_op_linear_workspace_bytes(128, 128, 64)
 
 
 def test_no_cpu_fallback():

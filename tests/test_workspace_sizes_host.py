@@ -25,6 +25,18 @@ EXPECTED = {
         ((1, 128, 64), 99072),
         ((0, 128, 64), 98560),
     ],
+    # (x_rows, ldx, N, ldw): awt_op_linear's pieces with x [x_rows, ldx] and w [N, ldw] of their own pitches -- x planes x_rows ldx 2 (x2), w planes N ldw 2 (x2),
+    # the flag word, the 16-row w copies ceil(N / 256) 256 ldw 2 (x2); with ldx == ldw == K it is awt_op_linear's size (the first four rows repeat its table),
+    # the others are worked out by hand from that list (recorded from the commit that added the entry point: nothing precedes it)
+    "awt_op_linear_fused_workspace_bytes": [
+        ((96000, 768, 2304, 768), 309068032),
+        ((3, 64, 128, 64), 99584),
+        ((5, 64, 384, 64), 231168),
+        ((3, 7, 10, 7), 8448),
+        ((400, 128, 384, 384), 1581312),  # the conv stem's form: 204800 + 589824 + 256 + 786432
+        ((200, 192, 256, 256), 678144),   # the LoRA form: 153600 + 262144 + 256 + 262144
+        ((0, 64, 128, 64), 98560),
+    ],
     # six planes of B H S 64 2 bytes
     "awt_op_attention_workspace_bytes": [
         ((64, 12, 1500), 884736000),
