@@ -17,7 +17,7 @@ once to channels-last rows [B T, C], which every operator below reads and writes
     [Cout, Cin, 3] gradient, its bias gradient `awt_op_column_sums`;
   * BatchNorm1d + ReLU + pooling: `awt_op_batchnorm_stats` (train) then `awt_op_bn_relu_pool`, and `awt_op_bn_relu_pool_backward`, which
     recomputes the ReLU mask and the pooling winner from the saved conv output; eval() feeds the running statistics to the same kernel;
-  * head: `_Linear` of the Transformer classifier (MFMA GEMM forward and both gradients); loss: `native_cross_entropy`.
+  * head: `autograd_ops.Linear` (MFMA GEMM forward and both gradients); loss: `autograd_ops.native_cross_entropy` (inside `train_epoch`).
 The running statistics are updated with torch ops on the [C] vectors; ReLU in the head and the five Dropouts are element-wise torch ops under
 autograd, as in the Transformer classifier.  There is no torch fallback for conv, BatchNorm or pooling: without libawt the first call raises.
 Nothing is cached between calls (the conv weights are packed per call, like `awt_op_linear`'s), so there is no state that a parameter update
@@ -32,15 +32,15 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib, ops
+from . import _lib, native_decoder as nd, ops
+from .autograd_ops import Linear, native_linear, train_epoch
 from .urbansound import N_MELS
-from .urbansound_classifier import _Linear, _column_sums, native_cross_entropy, native_linear
 
 CNN_DROPOUT, CNN_LR, CNN_WEIGHT_DECAY = 0.3, 3e-4, 1e-4       # spectrogram.py:65-67
 CNN_CHANNELS = (128, 256, 512, 512)
 HEAD_WIDTHS = (256, 128)
-_TERMS = {"bf16": 1, "bf16x3": 3}
-_FORWARD_TERMS = {"bf16": 1, "bf16x3": 3, "fp16x3": 4}       # common.h PREC_*
+_TERMS = frozenset(("bf16", "bf16x3"))                        # names of ops._TERMS a gradient GEMM takes
+_FORWARD_TERMS = _TERMS | {"fp16x3"}                          # ... and a conv forward
 POOL_MEAN, POOL_MAX2, POOL_MAX4, POOL_MAX4_MEAN = 0, 2, 4, 5  # include/awt.h AWT_POOL_*
 _POOL_WINDOW = {POOL_MEAN: 0, POOL_MAX2: 2, POOL_MAX4: 4, POOL_MAX4_MEAN: 4}
 
@@ -48,17 +48,13 @@ _POOL_WINDOW = {POOL_MEAN: 0, POOL_MAX2: 2, POOL_MAX4: 4, POOL_MAX4_MEAN: 4}
 def _terms(precision: str) -> int:
     if precision not in _TERMS:
         raise ValueError("the CNN's GEMMs run in 'bf16' or 'bf16x3' operand planes (gradients need fp32's exponent range)")
-    return _TERMS[precision]
+    return ops._TERMS[precision]
 
 
 def _forward_terms(precision: str) -> int:
     if precision not in _FORWARD_TERMS:
         raise ValueError("a conv forward runs in 'bf16', 'bf16x3' or 'fp16x3' operand planes")
-    return _FORWARD_TERMS[precision]
-
-
-def _pad_to(n: int, multiple: int) -> int:
-    return (n + multiple - 1) // multiple * multiple
+    return ops._TERMS[precision]
 
 
 # ------------------------------------------------------------------------------------------------ operators (no autograd)
@@ -70,7 +66,7 @@ def conv1d(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], B: int, 
     cout, cin, taps = w.shape
     if x.shape != (B * T, cin):
         raise ValueError(f"conv1d: x must be [{B * T}, {cin}], got {tuple(x.shape)}")
-    kp, npad = _pad_to(cin, 64), _pad_to(cout, 128)
+    kp, npad = ops.pad_to(cin, 64), ops.pad_to(cout, 128)
     x, w = x.float(), w.float()
     if kp != cin:
         x, w = F.pad(x, (0, kp - cin)), F.pad(w, (0, 0, 0, kp - cin))
@@ -97,7 +93,7 @@ def conv1d_weight_grad(dy: torch.Tensor, x: torch.Tensor, B: int, T: int, precis
     """dW [Cout, Cin, 3] of `conv1d`: per tap, dW[:, :, tap] = dy^T x[frame + tap - 1] on the weight-gradient GEMM under the conv's row map,
     written through the gradient's strides (3 Cin, 3) at the tap's offset."""
     cin = x.shape[1]
-    kp = _pad_to(cin, 8)                     # the weight-gradient GEMM takes widths and pitches in multiples of 8
+    kp = ops.pad_to(cin, 8)                 # the weight-gradient GEMM takes widths and pitches in multiples of 8
     if kp != cin:
         x = F.pad(x, (0, kp - cin))
     dw = torch.empty((dy.shape[1], kp, 3), dtype=torch.float32, device=dy.device)
@@ -168,7 +164,7 @@ class _Conv1d(torch.autograd.Function):
         B, T = ctx.shape
         dy = dy.contiguous()
         dx = conv1d_input_grad(dy, w, B, T, ctx.precision) if ctx.needs_input_grad[0] else None
-        return dx, conv1d_weight_grad(dy, x, B, T, ctx.precision), _column_sums(dy), None, None, None, None
+        return dx, conv1d_weight_grad(dy, x, B, T, ctx.precision), nd.column_sums(dy), None, None, None, None
 
 
 class _BnReluPool(torch.autograd.Function):
@@ -284,8 +280,8 @@ class CNNUrbanSound8KClassifier(nn.Module):
         if self.training:
             h = self._features(x)
             for fc, drop in zip(lin[:-1], drops):
-                h = drop(F.relu(_Linear.apply(h.contiguous(), fc.weight, fc.bias, P)))
-            return _Linear.apply(h.contiguous(), lin[-1].weight, lin[-1].bias, P)
+                h = drop(F.relu(Linear.apply(h.contiguous(), fc.weight, fc.bias, P)))
+            return Linear.apply(h.contiguous(), lin[-1].weight, lin[-1].bias, P)
         with torch.no_grad():
             h = self._features(x)
             for fc in lin[:-1]:
@@ -303,17 +299,7 @@ def train_cnn(train_loader, model: Optional[CNNUrbanSound8KClassifier] = None, e
     optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
     losses = []
     for epoch in range(epochs):
-        model.train()
-        total, seen = 0.0, 0
-        for xb, yb in train_loader:
-            xb, yb = xb.to(device), yb.to(device)
-            optimizer.zero_grad()
-            loss = native_cross_entropy(model(xb), yb)
-            loss.backward()
-            optimizer.step()
-            total += float(loss.detach()) * xb.size(0)
-            seen += xb.size(0)
-        losses.append(total / max(seen, 1))
+        losses.append(train_epoch(model, train_loader, optimizer, device))
         if log is not None:
             log(f"Epoch {epoch + 1}: Train loss={losses[-1]:.4f}")
     return model, losses

@@ -14,7 +14,8 @@ Same constructor and parameter names as the reference (`audio_projection`, `cros
 `layer_norm1`, `layer_norm2`, `feedforward.0`, `feedforward.2`: 14 tensors), so the `cross_attention_adapter.*` entries of a reference
 `trainable_state_dict` load with `load_state_dict(strict=True)` once the prefix is stripped.
 
-Every operator is a `torch.autograd.Function` whose forward AND backward are libawt calls:
+Every operator is a `torch.autograd.Function` whose forward AND backward are libawt calls (`AlignedLinear`, `LayerNorm` and `Gelu` of
+autograd_ops.py, shared with the classifiers; `_CrossAttention` here):
   * linears: y = x W^T + b and dx = dy W on the MFMA GEMM (`awt_op_linear`), dW = dy^T x on the weight-gradient GEMM (`awt_op_weight_grad`),
     db by pitched column sums (`awt_op_column_sums_ld`; fc1 has 4 text_dim columns);
   * keys and values are ONE GEMM of N = 2 text_dim against rows text_dim .. 3 text_dim of `in_proj_weight`; the attention reads that
@@ -35,30 +36,11 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from . import _lib, native_decoder as nd, ops
-from .urbansound_classifier import _Gelu, _LayerNorm          # the LayerNorm (dx, dgamma, dbeta) and GELU autograd nodes of the classifiers
+from . import _lib, ops
+from .autograd_ops import AlignedLinear, Gelu, LayerNorm
 
 HEAD_DIM = 128            # csrc/cross_attention.hip
 MAX_TEXT_DIM = 1280       # the LayerNorm kernels' row limit
-
-
-class _Linear(torch.autograd.Function):
-    """y [M, N] = x [M, K] w[N, K]^T + b; N % 128 == 0 and K % 64 == 0 (the constructor's checks guarantee both for every linear of the adapter)."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, precision):
-        ctx.save_for_backward(x, w)
-        ctx.precision, ctx.has_bias = precision, b is not None
-        return ops.linear(x, w, b, precision)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = nd.gemm(dy, w.t().contiguous(), ctx.precision).contiguous() if ctx.needs_input_grad[0] else None
-        dw = ops.weight_grad(dy, x, precision=ctx.precision) if ctx.needs_input_grad[1] else None
-        db = nd.column_sums_ld(dy) if ctx.has_bias and ctx.needs_input_grad[2] else None
-        return dx, dw, db, None
 
 
 class _CrossAttention(torch.autograd.Function):
@@ -104,10 +86,10 @@ class CrossAttentionAdapter(nn.Module):
         self.feedforward = nn.Sequential(nn.Linear(text_dim, text_dim * 4, dtype=self.dtype), nn.GELU(), nn.Linear(text_dim * 4, text_dim, dtype=self.dtype))
 
     def _linear(self, x: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-        return _Linear.apply(x, w.float(), b.float(), self.precision)
+        return AlignedLinear.apply(x, w.float(), b.float(), self.precision)
 
     def _layer_norm(self, ln: nn.LayerNorm, x: torch.Tensor) -> torch.Tensor:
-        return _LayerNorm.apply(x.contiguous(), ln.weight.float(), ln.bias.float(), ln.eps)
+        return LayerNorm.apply(x.contiguous(), ln.weight.float(), ln.bias.float(), ln.eps)
 
     def encode_audio(self, audio_features: torch.Tensor) -> torch.Tensor:
         """audio_features [B, Sa, audio_dim] -> audio_kv [B, Sa, 2 text_dim] fp32: the keys (first text_dim columns) and values of every head, what
@@ -139,6 +121,6 @@ class CrossAttentionAdapter(nn.Module):
         q = self._linear(text, att.in_proj_weight[:d], att.in_proj_bias[:d])
         o = _CrossAttention.apply(q, audio_kv.float().reshape(B * Sa, 2 * d).contiguous(), B, self.num_heads, L, Sa, self.precision)
         x = self._layer_norm(self.layer_norm1, text + self._linear(o, att.out_proj.weight, att.out_proj.bias))
-        h = _Gelu.apply(self._linear(x, ff[0].weight, ff[0].bias))
+        h = Gelu.apply(self._linear(x, ff[0].weight, ff[0].bias))
         out = self._layer_norm(self.layer_norm2, x + self._linear(h, ff[2].weight, ff[2].bias))
         return out.reshape(B, L, d).to(text_embeddings.dtype)

@@ -42,9 +42,9 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, ops
 
-_PREC = {"bf16": 1, "bf16x3": 3}
+_PREC = {name: ops._TERMS[name] for name in ("bf16", "bf16x3")}          # the operand planes `awt_weight` packs, out of ops' PREC_* table
 
 
 class PackedLinear:
@@ -235,17 +235,29 @@ def layernorm_param_grad(dy: torch.Tensor, x: torch.Tensor, eps: float = 1e-5) -
     return dg, db
 
 
-def gemm(x: torch.Tensor, w: torch.Tensor, precision: str = "bf16x3") -> torch.Tensor:
-    """x [M, K] @ w [N, K]^T on libawt's MFMA GEMM (`awt_op_linear`): K zero-padded to a multiple of 64, N to a multiple of 128."""
-    from . import ops
+def column_sums(a: torch.Tensor) -> torch.Tensor:
+    """sums[c] = sum_m a[m, c] over a contiguous [M, d] matrix, d <= 1280 (awt_op_column_sums; bias gradients of the classifiers)."""
+    M, d = a.shape
+    out = torch.empty(d, dtype=torch.float32, device=a.device)
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_op_param_grad_workspace_bytes(M, d), a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(L.awt_op_column_sums(_ctx(a), _lib.ptr(a), _lib.ptr(out), M, d, _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
+    return out
+
+
+def gemm(x: torch.Tensor, w: torch.Tensor, precision: str = "bf16x3", bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [M, K] @ w [N, K]^T (+ bias [N]) on libawt's MFMA GEMM (`awt_op_linear`): K zero-padded to a multiple of 64, N to a multiple of 128."""
+    pad = torch.nn.functional.pad
     M, K = x.shape
     N = w.shape[0]
-    kp, np_ = (K + 63) // 64 * 64, (N + 127) // 128 * 128
+    kp, np_ = ops.pad_to(K, 64), ops.pad_to(N, 128)
     if kp != K:
-        x, w = torch.nn.functional.pad(x, (0, kp - K)), torch.nn.functional.pad(w, (0, kp - K))
+        x, w = pad(x, (0, kp - K)), pad(w, (0, kp - K))
     if np_ != N:
-        w = torch.nn.functional.pad(w, (0, 0, 0, np_ - N))
-    return ops.linear(x.contiguous(), w.contiguous(), None, precision)[:, :N]
+        w = pad(w, (0, 0, 0, np_ - N))
+        bias = pad(bias, (0, np_ - N)) if bias is not None else None
+    return ops.linear(x, w, bias, precision)[:, :N]                  # ops.linear makes its operands fp32 and contiguous
 
 
 class PackedBatch:
@@ -798,7 +810,6 @@ class _DecoderLoss(torch.autograd.Function):
             grads[id(Bm)] = gemm(dy.t().contiguous(), u.t().contiguous(), prec) * scale     # dB [d, r] = (alpha / r) dy^T u
             return gemm(du, A.detach().t().contiguous(), prec) * scale                      # [M, d] = (alpha / r) du A
 
-        from . import ops
         base = dec.train_base
         need_enc = ctx.needs_input_grad[0] or not base                                      # a frozen encoder under train_base: no d(encoder states)
 

@@ -18,6 +18,11 @@ def _terms(precision: str) -> int:
     return _TERMS[precision]
 
 
+def pad_to(n: int, multiple: int) -> int:
+    """n rounded up to a multiple (the GEMM's K step of 64 and N tile of 128, the weight-gradient GEMM's widths of 8)."""
+    return (n + multiple - 1) // multiple * multiple
+
+
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, precision: str = "bf16x3") -> torch.Tensor:
     """y = x w^T + bias on the MFMA GEMM kernel; x [M, K], w [N, K] fp32 device tensors, N % 128 == 0, K % 64 == 0."""
     terms = _terms(precision)

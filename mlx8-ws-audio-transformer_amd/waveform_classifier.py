@@ -14,10 +14,10 @@ The modules in the two containers hold the parameters and buffers only; `forward
     operator reads; its weight gradient is `awt_op_weight_grad` once per block of `stride` taps over the waveform viewed as rows of `stride`
     samples (kernel = 5 stride: a 5-tap convolution without padding over those rows), its bias gradient `awt_op_column_sums`; the waveform is
     data and gets no gradient;
-  * blocks 2 and 3: `awt_op_conv1d` as in cnn_classifier.py (forward in `forward_precision`, gradients in `precision`);
+  * blocks 2 and 3: `_Conv1d` / `conv1d` of cnn_classifier.py, which this model is built from (`awt_op_conv1d`: forward in `forward_precision`, gradients in `precision`);
   * BatchNorm1d + ReLU + MaxPool1d(4): `batchnorm_relu_pool` with `POOL_MAX4`; the last block's MaxPool1d(4) + AdaptiveAvgPool1d(1) is one
     launch, `POOL_MAX4_MEAN`, whose pooled tensor is never written;
-  * head: `_Linear`; loss: `native_cross_entropy`.
+  * head: `autograd_ops.Linear`; loss: `autograd_ops.native_cross_entropy` (inside `train_epoch`).
 There is no torch fallback and nothing is cached between calls.
 """
 from __future__ import annotations
@@ -30,11 +30,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.utils.data import Dataset
 
-from . import _lib, ops
+from . import _lib, native_decoder as nd, ops
+from .autograd_ops import Linear, native_linear, train_epoch
 from .cnn_classifier import (CNN_DROPOUT, CNN_LR, CNN_WEIGHT_DECAY, POOL_MAX4, POOL_MAX4_MEAN, _Conv1d, _forward_terms, _terms,
                              batchnorm_relu_pool, conv1d)
 from .urbansound import DATA_ROOT, DURATION, METADATA_CSV, SAMPLE_RATE, preprocess_audio_for_cnn, read_wav
-from .urbansound_classifier import _Linear, _column_sums, native_cross_entropy, native_linear
 
 WAVE_KERNEL, WAVE_STRIDE = 80, 16                       # spectrogram.py:669
 WAVE_CHANNELS = (64, 128, 256)
@@ -98,7 +98,7 @@ class _Conv1dFramed(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         kernel, stride, precision = ctx.cfg
         dy = dy.contiguous()
-        return None, conv1d_framed_weight_grad(dy, x, kernel, stride, precision), _column_sums(dy), None, None
+        return None, conv1d_framed_weight_grad(dy, x, kernel, stride, precision), nd.column_sums(dy), None, None
 
 
 # ------------------------------------------------------------------------------------------------ the model
@@ -159,8 +159,8 @@ class CNNWaveformClassifier(nn.Module):
         fc1, drop, fc2 = self.classifier[1], self.classifier[3], self.classifier[4]
         P = self.precision
         if self.training:
-            h = drop(F.relu(_Linear.apply(self._features(x).contiguous(), fc1.weight, fc1.bias, P)))
-            return _Linear.apply(h.contiguous(), fc2.weight, fc2.bias, P)
+            h = drop(F.relu(Linear.apply(self._features(x).contiguous(), fc1.weight, fc1.bias, P)))
+            return Linear.apply(h.contiguous(), fc2.weight, fc2.bias, P)
         with torch.no_grad():
             h = F.relu(native_linear(self._features(x), fc1.weight, fc1.bias, P))
             return native_linear(h, fc2.weight, fc2.bias, P)
@@ -212,17 +212,7 @@ def train_waveform_classifier(train_loader, val_loader=None, model: Optional[CNN
     optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
     losses, accuracies = [], []
     for epoch in range(epochs):
-        model.train()
-        total, seen = 0.0, 0
-        for xb, yb in train_loader:
-            xb, yb = xb.to(device), yb.to(device)
-            optimizer.zero_grad()
-            loss = native_cross_entropy(model(xb), yb)
-            loss.backward()
-            optimizer.step()
-            total += float(loss.detach()) * xb.size(0)
-            seen += xb.size(0)
-        losses.append(total / max(seen, 1))
+        losses.append(train_epoch(model, train_loader, optimizer, device))
         if log is not None:
             log(f"Epoch {epoch + 1}: Train Loss = {losses[-1]:.4f}")
         if val_loader is not None:

@@ -56,7 +56,7 @@ def test_training_step_gradients_match_autograd_of_the_reference_module(n_mels, 
     """One forward + backward in train() mode with dropout 0: loss and the gradient of EVERY parameter against torch autograd over
     the reference module's restatement (fp32 CPU).  Tolerance: 2e-4 of each gradient's largest magnitude (bf16x3 GEMMs, the
     weight-gradient contraction runs over B (T + 1) rows)."""
-    from mlx8_ws_audio_transformer_amd.urbansound_classifier import native_cross_entropy
+    from mlx8_ws_audio_transformer_amd.autograd_ops import native_cross_entropy
     ref, nat = _train_pair(n_mels, T, seed=7 + T)
     x = torch.from_numpy(wts.unit_variates("cls.xt", batch * n_mels * T, 5).reshape(batch, n_mels, T).astype(np.float32)) * 2.0 - 4.0
     y = torch.tensor([(3 * i + 1) % 10 for i in range(batch)])
@@ -79,15 +79,15 @@ def test_training_step_gradients_match_autograd_of_the_reference_module(n_mels, 
 
 
 def test_reduction_operators_match_torch():
-    from mlx8_ws_audio_transformer_amd import urbansound_classifier as uc
+    from mlx8_ws_audio_transformer_amd import autograd_ops as ao, native_decoder as nd
     g = torch.Generator().manual_seed(3)
     for M, d in [(1, 4), (700, 128), (1030, 10), (513, 1280)]:
         a = torch.randn(M, d, generator=g).cuda()
-        np.testing.assert_allclose(uc._column_sums(a).cpu().numpy(), a.double().sum(0).float().cpu().numpy(), rtol=2e-5, atol=2e-5)
+        np.testing.assert_allclose(nd.column_sums(a).cpu().numpy(), a.double().sum(0).float().cpu().numpy(), rtol=2e-5, atol=2e-5)
     x = (torch.randn(700, 128, generator=g) * 3 + 1).cuda().requires_grad_(True)
     gam, bet = torch.randn(128, generator=g).cuda().requires_grad_(True), torch.randn(128, generator=g).cuda().requires_grad_(True)
     dy = torch.randn(700, 128, generator=g).cuda()
-    uc._LayerNorm.apply(x, gam, bet, 1e-5).backward(dy)
+    ao.LayerNorm.apply(x, gam, bet, 1e-5).backward(dy)
     got = (x.grad.clone(), gam.grad.clone(), bet.grad.clone())
     x64, g64, b64 = (t.detach().double().requires_grad_(True) for t in (x, gam, bet))
     torch.nn.functional.layer_norm(x64, (128,), g64, b64, 1e-5).backward(dy.double())
@@ -135,11 +135,11 @@ def test_attention_probability_dropout_matches_autograd_with_the_same_mask(B, H,
     """`nn.TransformerEncoderLayer(dropout=p)` drops attention weights in train() (spectrogram.py:977-985).  The native attention pair
     regenerates a seeded keep mask in its forward and both backward kernels; `attention_keep_mask` restates the mask on the host, and with that very
     mask torch autograd must give the same output and the same dq / dk / dv."""
-    from mlx8_ws_audio_transformer_amd.urbansound_classifier import _Attention, attention_keep_mask
+    from mlx8_ws_audio_transformer_amd.autograd_ops import Attention, attention_keep_mask
     seed = 123456789 + S
     qkv = torch.from_numpy(wts.unit_variates("drop.qkv", B * S * 3 * H * 64, 11).reshape(B * S, 3 * H * 64).astype(np.float32)).cuda().requires_grad_(True)
     dout = torch.from_numpy(wts.unit_variates("drop.do", B * S * H * 64, 12).reshape(B * S, H * 64).astype(np.float32)).cuda()
-    o = _Attention.apply(qkv, B, H, S, p, seed)
+    o = Attention.apply(qkv, B, H, S, p, seed)
     o.backward(dout)
     mask = attention_keep_mask(seed, B, H, S, S, p)
     frac = float((mask > 0).float().mean())
@@ -153,7 +153,7 @@ def test_attention_probability_dropout_matches_autograd_with_the_same_mask(B, H,
     g, w = qkv.grad.cpu().double(), ref_in.grad
     assert float((g - w).abs().max()) < 2e-5 * max(1.0, float(w.abs().max()))
     # p = 0 is the plain kernel pair, bit for bit
-    assert torch.equal(_Attention.apply(qkv.detach(), B, H, S, 0.0, seed), _Attention.apply(qkv.detach(), B, H, S))
+    assert torch.equal(Attention.apply(qkv.detach(), B, H, S, 0.0, seed), Attention.apply(qkv.detach(), B, H, S))
 
 
 def test_train_mode_applies_attention_dropout_and_eval_caches_packed_weights():
@@ -174,3 +174,31 @@ def test_train_mode_applies_attention_dropout_and_eval_caches_packed_weights():
         nat.head[3].weight.mul_(2.0)
     y2 = nat(x)
     assert not torch.equal(y0, y2) and id(nat._packed.items[id(nat.head[3].weight)][1]) != handles[id(nat.head[3].weight)]
+
+
+def test_both_linear_nodes_share_forward_and_dx_and_match_fp64_gradients():
+    """`autograd_ops.Linear` and `AlignedLinear` at a shape both accept (x [37, 64], w [128, 64], bias, bf16x3; 37 rows are ragged against the GEMM's
+    row tile and the weight-gradient GEMM's 32-row stage): y and dx are the same calls, so equal bit for bit; dW and db come from different kernels
+    and each is held to fp64 at the tolerance of the training-step test above (2e-4 of the gradient's largest magnitude + 1e-7)."""
+    from mlx8_ws_audio_transformer_amd.autograd_ops import AlignedLinear, Linear
+    M, K, N = 37, 64, 128
+    draw = lambda name, *shape: torch.from_numpy(wts.unit_variates("lin." + name, int(np.prod(shape)), 17).reshape(shape).astype(np.float32)).cuda()
+    x0, w0, b0, dy = draw("x", M, K), draw("w", N, K), draw("b", N), draw("dy", M, N)
+    got = {}
+    for node in (Linear, AlignedLinear):
+        x, w, b = (t.clone().requires_grad_(True) for t in (x0, w0, b0))
+        y = node.apply(x, w, b, "bf16x3")
+        y.backward(dy)
+        got[node] = (y.detach(), x.grad, w.grad, b.grad)
+    assert torch.equal(got[Linear][0], got[AlignedLinear][0])
+    assert torch.equal(got[Linear][1], got[AlignedLinear][1])
+    want_y = x0.double() @ w0.double().T + b0.double()
+    assert float((got[Linear][0].double() - want_y).abs().max()) <= 2e-4 * float(want_y.abs().max()) + 1e-7
+    want = {"dW": dy.double().T @ x0.double(), "db": dy.double().sum(0)}
+    for node in (Linear, AlignedLinear):
+        for (name, w64), g in zip(want.items(), got[node][2:]):
+            assert g.shape == w64.shape and g.dtype == torch.float32, (node.__name__, name)
+            scale = float(w64.abs().max())
+            err = float((g.double() - w64).abs().max())
+            print(f"{node.__name__} {name}: err {err:.3e} scale {scale:.3e}")
+            assert scale > 0 and err <= 2e-4 * scale + 1e-7, (node.__name__, name, err, scale)

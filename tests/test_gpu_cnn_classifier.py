@@ -303,7 +303,7 @@ def test_training_step_matches_autograd_of_the_restated_module(n_mels, T, batch)
     other side of its kink than fp64 and the gradients up to that block miss their bounds by two orders (conv_layers.5.weight 1.05e-3 against
     2.9e-6, measured on an MI355X and reproduced on the CPU by rounding the conv operands alone).  The model's default, split-fp16 forwards
     (2^-23 per operand, same three products), is what is tested here; the bounds are those of `_step_bounds`, unchanged."""
-    from mlx8_ws_audio_transformer_amd.urbansound_classifier import native_cross_entropy
+    from mlx8_ws_audio_transformer_amd.autograd_ops import native_cross_entropy
     ref, nat = _pair(n_mels, seed=7 + T)
     x, y = _mel("cnn.xt", batch, n_mels, T, 5), _labels(batch)
     want_loss, want = _train_step_reference(ref, x, y)
@@ -414,7 +414,7 @@ def test_one_adam_step_with_weight_decay_matches_the_restated_module():
 
 # ---------------------------------------------------------------------------------------------------------------- 7. determinism, dropout
 def test_training_is_bit_reproducible_and_dropout_follows_the_seed():
-    from mlx8_ws_audio_transformer_amd.urbansound_classifier import native_cross_entropy
+    from mlx8_ws_audio_transformer_amd.autograd_ops import native_cross_entropy
     _, nat = _pair(64, seed=5)
     x, y = _mel("cnn.xd", 3, 64, 63, 6).cuda(), _labels(3).cuda()
     nat.train()

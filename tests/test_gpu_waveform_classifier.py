@@ -299,7 +299,7 @@ def test_training_step_matches_autograd_of_the_restated_module(batch, N):
     """One train() forward + backward with dropout 0: the loss, the gradient of EVERY parameter, the updated running buffers and counters against
     fp64 autograd over the restated module, at sizes (frames 256 -> 64 -> 16 -> 4 -> 1, and 81 -> 20 -> 5 -> 1) where a seed exists for which
     the fp64 reference stays KINK away from every discontinuity (`step_seed`).  Every figure is printed before it is judged."""
-    from mlx8_ws_audio_transformer_amd.urbansound_classifier import native_cross_entropy
+    from mlx8_ws_audio_transformer_amd.autograd_ops import native_cross_entropy
     table = FP32_VS_FP64[(batch, N)]
     seed = step_seed(batch, N)
     assert seed == table["seed"], "FP32_VS_FP64 was measured for another seed: run tools/waveform_cnn_fp32_vs_fp64.py"
@@ -334,7 +334,7 @@ def test_training_step_at_full_size():
     """N = 64000, B = 2.  With half a million z per block the fp64 reference itself comes within 1e-7 ... 1e-6 of a kink, so gradient parity is
     not a fair question here; asserted is what is continuous: the loss, the running statistics, finite gradients of every parameter, and
     bit-identical gradients over two runs."""
-    from mlx8_ws_audio_transformer_amd.urbansound_classifier import native_cross_entropy
+    from mlx8_ws_audio_transformer_amd.autograd_ops import native_cross_entropy
     ref, nat = _pair(seed=11)
     x, y = _wave("wave.xf", 2, 64000, 9), _labels(2)
     ref.train()

@@ -114,3 +114,54 @@ def test_automatic_precision_choice_reads_the_weights_only():
     assert enc.choose_precision() == "fp16x3"
     rep = enc.precision_report
     assert rep["layernorm_gain_ratio"] > 8 and rep["precision"] == "fp16x3"
+
+
+def test_small_models_take_shared_operators_from_autograd_ops_not_from_each_other():
+    """The dependency rule of the four small models: shared differentiable operators come from `autograd_ops` (with `ops`, `native_decoder`, `_lib`),
+    never from another model module.  The one model-to-model import left is waveform_classifier -> cnn_classifier, for the CNN operators."""
+    import ast
+    import importlib
+    import os
+    import mlx8_ws_audio_transformer_amd as pkg
+    models = ("urbansound_classifier", "cnn_classifier", "waveform_classifier", "music2midi")
+    root = pkg.__path__[0]
+
+    def relative_imports(module):
+        """[(imported sibling module, imported name or None)] of one source file of the package."""
+        with open(os.path.join(root, module + ".py")) as f:
+            tree = ast.parse(f.read())
+        out = []
+        for node in ast.walk(tree):
+            if isinstance(node, ast.ImportFrom) and (node.level == 1 or (node.module or "").startswith(pkg.__name__)):
+                mod = (node.module or "").replace(pkg.__name__, "").lstrip(".")
+                for alias in node.names:
+                    out.append((mod or alias.name, alias.name if mod else None))
+            elif isinstance(node, ast.Import):
+                out += [(a.name[len(pkg.__name__) + 1:], None) for a in node.names if a.name.startswith(pkg.__name__ + ".")]
+        return out
+
+    every = sorted(f[:-3] for f in os.listdir(root) if f.endswith(".py") and f != "__init__.py")
+    assert set(models) <= set(every) and "autograd_ops" in every
+    for module in every:                                   # no private name of the UrbanSound model is anybody's library
+        for mod, name in relative_imports(module):
+            assert not (mod == "urbansound_classifier" and name is not None and name.startswith("_")), (module, name)
+    for module in models:
+        imported = {mod for mod, _ in relative_imports(module)}
+        allowed = {"cnn_classifier"} if module == "waveform_classifier" else set()
+        assert imported & set(models) <= allowed, (module, sorted(imported & set(models)))
+        assert "autograd_ops" in imported, module
+    assert "urbansound_classifier" not in {mod for mod, _ in relative_imports("music2midi")}
+    for module in ("autograd_ops", "native_decoder", "ops"):  # the shared layers sit below the models; the bindings below the autograd nodes
+        imported = {mod for mod, _ in relative_imports(module)}
+        assert not imported & set(models), (module, sorted(imported))
+    assert "autograd_ops" not in {mod for mod, _ in relative_imports("native_decoder")} | {mod for mod, _ in relative_imports("ops")}
+
+    ao = importlib.import_module(pkg.__name__ + ".autograd_ops")
+    assert len(set(ao.__all__)) == len(ao.__all__) >= 11
+    for name in ao.__all__:
+        assert not name.startswith("_") and getattr(ao, name) is not None, name
+    for node in (ao.Linear, ao.AlignedLinear, ao.LayerNorm, ao.Gelu, ao.Attention, ao.CrossEntropy):
+        assert issubclass(node, torch.autograd.Function)
+    for name in ("_Linear", "_LayerNorm", "_Gelu", "_Attention", "_CrossEntropy", "_PackedCache", "_column_sums", "_pad_rows", "native_cross_entropy",
+                 "attention_keep_mask"):                                                      # moved, not aliased
+        assert name not in vars(importlib.import_module(pkg.__name__ + ".urbansound_classifier")), name

@@ -14,7 +14,8 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from mlx8_ws_audio_transformer_amd.urbansound_classifier import TransformerUrbanSound8KClassifier, native_cross_entropy
+from mlx8_ws_audio_transformer_amd.autograd_ops import native_cross_entropy
+from mlx8_ws_audio_transformer_amd.urbansound_classifier import TransformerUrbanSound8KClassifier
 
 
 def main():

@@ -3,7 +3,7 @@
 reference's batch) and B = 64; the weight-gradient GEMM launches' share of the step and their achieved TFLOP/s (in-library event timing,
 class "wgrad"; FLOPs counted as 2 M N K per product, whatever the split-bf16 term count); the per-step re-upload of the updated weights
 (`sync_weights` after `optimizer.step()`); and the baseline the weight-gradient kernel replaces, on fc1's shape (M = 24000, N = 3072,
-K = 768): two fp32 transposes plus `awt_op_linear`, as urbansound_classifier._NativeLinear forms dW.  Prints one JSON line.
+K = 768): two fp32 transposes plus `awt_op_linear`, as autograd_ops.Linear forms dW.  Prints one JSON line.
 
     python tools/full_finetune_bench.py [--batches 16,64] [--steps 3] [--warmup 2]
 Per-kernel table: `rocprofv3 --kernel-trace --stats -- python tools/full_finetune_bench.py --batches 16` (wgrad_kernel / wgrad_reduce_kernel).

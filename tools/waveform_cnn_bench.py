@@ -20,7 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from mlx8_ws_audio_transformer_amd import CNNWaveformClassifier
-from mlx8_ws_audio_transformer_amd.urbansound_classifier import native_cross_entropy
+from mlx8_ws_audio_transformer_amd.autograd_ops import native_cross_entropy
 from mlx8_ws_audio_transformer_amd.waveform_classifier import WAVE_KERNEL, WAVE_STRIDE, conv1d_framed, framed_length
 
 N_SAMPLES = 64000
