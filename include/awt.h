@@ -456,6 +456,37 @@ int awt_op_cross_attention_backward(awt_ctx* c, const float* q, int ldq, const f
                                     const float* dout, int ldo, const float* lse, float* dq, float* dk, float* dv, int B, int H, int Lq, int Sk,
                                     int terms, void* workspace, size_t ws_bytes, void* stream);
 
+/* The operators of a Qwen3 decoder layer (music2midi.Qwen3Decoder; csrc/qwen_ops.hip, and the causal variant of csrc/cross_attention.hip's forward).  fp32
+ * row-major tensors in place, the caller's stream, no synchronisation; AWT_ERR_INVALID for a null pointer, a pitch that cannot hold its row or is not a multiple
+ * of 4 (the vectorised operators), tensors not 16-byte aligned (the same), and the sizes named with each.
+ *
+ * RMSNorm: y[m, :] = gamma * x[m, :] * rsqrt(mean(x[m, :]^2) + eps), row m of x at x + m ldx, of y at y + m ldy (y may alias x).  d: any positive multiple
+ * of 4.  One wave per row, the sum of squares in a fixed order (two runs give the same bits).                         HF:modeling_qwen3.py Qwen3RMSNorm */
+int awt_op_rmsnorm(awt_ctx* c, const float* x, int64_t ldx, const float* gamma, float* y, int64_t ldy, int M, int d, float eps, void* stream);
+/* Everything between a layer's fused q | k | v GEMM and its attention, one launch.  qkv [B Lq, ld]: Hq query heads, then Hkv key heads, then Hkv value
+ * heads, 128 columns each.  Every q and k head gets the per-head RMSNorm over its 128 dims (q_gamma / k_gamma [128], eps) and THEN the rotary embedding in
+ * HF's convention x cos + rotate_half(x) sin, dim i paired with i + 64, at the row's absolute position positions[r] (device int32 [B Lq]): cos / sin are
+ * fp32 tables [rows, 64] built by the caller (angle = position * theta^(-2 i / 128)).  Rotated q goes to q_out + r ldq + 128 h; rotated k and the unchanged
+ * v go into the decode cache at k_cache / v_cache + b kv_batch_stride + positions[r] ldkv + 128 h (b = r / Lq; v arrives bit-identical).  No other cache
+ * row is touched.  A position outside the rows that fit a batch's stride, [0, (kv_batch_stride - Hkv 128) / ldkv], is clamped into it (the call cannot
+ * fail without a synchronisation and never writes outside the cache); cos / sin must hold that many rows.       HF:modeling_qwen3.py Qwen3Attention.forward */
+int awt_op_qk_norm_rope(awt_ctx* c, const float* qkv, int64_t ld, const float* q_gamma, const float* k_gamma, const float* cos, const float* sin,
+                        const int32_t* positions, float* q_out, int64_t ldq, float* k_cache, float* v_cache, int64_t ldkv, int64_t kv_batch_stride,
+                        int B, int Lq, int Hq, int Hkv, float eps, void* stream);
+/* Causal attention for head_dim 128 with grouped KV heads over that cache: o[b, i, h] = softmax_j(128^-1/2 q[b, i, h] . k[b, j, g]) v[b, j, g] over the keys
+ * j <= T - Lq + i of the T live positions (the contract of awt_op_attention_cached), g = h / (Hq / Hkv).  q / o as in awt_op_cross_attention (Hq heads,
+ * ldq / ldo); key / value j of batch b at k / v + b kv_batch_stride + j ldkv + 128 g.  One kernel for prefill (Lq = T) and decoding (Lq = 1): the flash-style
+ * bf16 MFMA forward of awt_op_cross_attention (terms 3 or 1, the score scale applied inside) in which a workgroup of 128 queries streams key tiles up to its
+ * last query's diagonal only and masks inside the tiles it does stream.  No cache row at or past T is read -- the cache may be uninitialised there -- and
+ * no atomics: two runs give the same bits.  Needs Hq % Hkv == 0, 1 <= Lq <= T, kv_batch_stride >= (T - 1) ldkv + Hkv 128.  The workspace query answers
+ * without a GPU (the forward needs none: 0). */
+size_t awt_op_causal_attention_workspace_bytes(int B, int Hq, int Lq, int T);
+int awt_op_causal_attention(awt_ctx* c, const float* q, int ldq, const float* k, const float* v, int ldkv, int64_t kv_batch_stride, float* o, int ldo,
+                            int B, int Hq, int Hkv, int Lq, int T, int terms, void* workspace, size_t ws_bytes, void* stream);
+/* SwiGLU's element-wise half over the output gu [M, ld] of one gate | up GEMM of width 2 I: y[m, i] = silu(gu[m, i]) * gu[m, I + i], silu(x) = x / (1 + exp(-x)).
+ * I: a positive multiple of 4; 16-byte accesses.                                                                   HF:modeling_qwen3.py Qwen3MLP */
+int awt_op_silu_mul(awt_ctx* c, const float* gu, int64_t ld, float* y, int64_t ldy, int M, int I, void* stream);
+
 /* Causal attention of Lq new query rows per batch over a preallocated decode cache: keys / values of batch b, position j at
  * k + b kv_batch_stride + j ldkv + 64 h (likewise v), T live positions (T >= Lq; query i sees keys j <= T - Lq + i).  q / o as in
  * awt_op_attention_small.  The cache is [rows, Tmax, 2 d] per layer, so kv_batch_stride = Tmax ldkv (csrc/decoder_ops.hip). */

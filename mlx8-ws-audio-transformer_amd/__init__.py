@@ -9,4 +9,4 @@ from .weights import (CONFIGS, EncoderConfig, LoraSpec, config, init_encoder_wei
                       init_lora_weights, weights_digest)
 from .cnn_classifier import CNNUrbanSound8KClassifier, eval_or_test_cnn, train_cnn  # noqa: F401,E402
 from .waveform_classifier import CNNWaveformClassifier, UrbanSoundRawDataset, train_waveform_classifier  # noqa: F401,E402
-from .music2midi import CrossAttentionAdapter  # noqa: F401,E402
+from .music2midi import CrossAttentionAdapter, MusicTranscriptionModel, Qwen3Cache, Qwen3Config, Qwen3Decoder  # noqa: F401,E402

@@ -40,6 +40,7 @@ struct XArgs {
   int B, H, Lq, Sk;
   int64_t ldq, ldk, ldv, ldo;
   float scale;                     // 128^-1/2
+  int Hkv; int64_t kvbs;           // causal forward only: KV heads (query head h reads KV head h / (H / Hkv)) and the cache's batch stride; Sk is then T
 };
 
 template <bool LO>
@@ -156,7 +157,13 @@ constexpr int dq_lds(int terms) { return (terms == 3 ? 2 : 1) * (2 * XROW64 + XC
 constexpr int dkv_lds(int terms) { return (terms == 3 ? 2 : 1) * (2 * XROW32 + 2 * XCOL32) + 2 * XQT * 4; }
 
 // ------------------------------------------------------------------------------------------------ forward
-template <int TERMS>
+// CAUSAL (awt_op_causal_attention): k / v are a decode cache -- batch b at k + b kvbs, row pitch ldk = ldv, Hkv heads -- holding a.Sk = T live positions, and query
+// i sees keys j <= T - Lq + i.  A workgroup streams key tiles up to its LAST query's diagonal only (`Sk` below: the staging's `valid` bound, so no row past it --
+// in particular nothing at a cache position >= T, which is uninitialised memory in real use -- is ever loaded; the rest of the last tile is zeros in LDS), a wave
+// skips the tiles past its own last query, and the mask is applied to the scores of the tiles that remain.  Key 0 is visible to every query and tile 0 is
+// processed by every live wave, so a row's running maximum is a real score before any fully masked tile reaches it and masked scores weigh exp2(-1e30 - m) = 0.
+// The non-causal instantiations compile to what they were: every difference is under `if constexpr` or folds to the old expression.
+template <int TERMS, bool CAUSAL = false>
 __global__ __launch_bounds__(XTHREADS) void xattn_fwd_kernel(XArgs a) {
   constexpr bool LO = TERMS == 3;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -171,8 +178,20 @@ __global__ __launch_bounds__(XTHREADS) void xattn_fwd_kernel(XArgs a) {
   const int q0 = qb * XLB + wave * XLW, qi = q0 + r;
   const bool live = q0 < a.Lq;                                     // wave-uniform: a wave past the last query only stages
   const int qc = min(qi, a.Lq - 1);                                // tail queries read the last row and are not stored
-  const float* kbase = a.k + (int64_t)b * a.Sk * a.ldk + XD * head;
-  const float* vbase = a.v + (int64_t)b * a.Sk * a.ldv + XD * head;
+  const float *kbase, *vbase;
+  int Sk, lim = 0, wlim = 0;                                       // keys this workgroup streams; last visible key of this lane's query / of the wave's last query
+  if constexpr (CAUSAL) {
+    const int kvh = head / (a.H / a.Hkv), off = a.Sk - a.Lq;
+    kbase = a.k + (int64_t)b * a.kvbs + XD * kvh;
+    vbase = a.v + (int64_t)b * a.kvbs + XD * kvh;
+    Sk = off + min(qb * XLB + XLB, a.Lq);
+    lim = off + qc;
+    wlim = off + min(q0 + XLW, a.Lq) - 1;
+  } else {
+    kbase = a.k + (int64_t)b * a.Sk * a.ldk + XD * head;
+    vbase = a.v + (int64_t)b * a.Sk * a.ldv + XD * head;
+    Sk = a.Sk;
+  }
 
   bf16x8 qh[8], ql[8];
   load_frags<LO>(a.q + ((int64_t)b * a.Lq + qc) * a.ldq + XD * head, h, qh, ql);
@@ -186,20 +205,21 @@ __global__ __launch_bounds__(XTHREADS) void xattn_fwd_kernel(XArgs a) {
   const float sc2 = a.scale * kLog2e;
 
   float4 kr[XKT / 8]; float vr[XKT / 2];
-  load_rows<XKT>(kbase, a.ldk, a.Sk, tid, kr);
-  load_cols<XKT>(vbase, a.ldv, a.Sk, tid, vr);
-  const int nt = (a.Sk + XKT - 1) / XKT;
+  load_rows<XKT>(kbase, a.ldk, Sk, tid, kr);
+  load_cols<XKT>(vbase, a.ldv, Sk, tid, vr);
+  const int nt = (Sk + XKT - 1) / XKT;
   for (int t = 0; t < nt; ++t) {
     const int k0 = t * XKT;
     __syncthreads();                                               // the previous tile's fragment reads are done
-    write_rows<XKT, LO>(kr, a.Sk - k0, tid, kh, kl);
-    write_cols<XKT, LO>(vr, a.Sk - k0, tid, vth, vtl);
+    write_rows<XKT, LO>(kr, Sk - k0, tid, kh, kl);
+    write_cols<XKT, LO>(vr, Sk - k0, tid, vth, vtl);
     __syncthreads();
     if (t + 1 < nt) {                                              // the next tile's loads fly under this tile's products
-      load_rows<XKT>(kbase + (int64_t)(k0 + XKT) * a.ldk, a.ldk, a.Sk - k0 - XKT, tid, kr);
-      load_cols<XKT>(vbase + (int64_t)(k0 + XKT) * a.ldv, a.ldv, a.Sk - k0 - XKT, tid, vr);
+      load_rows<XKT>(kbase + (int64_t)(k0 + XKT) * a.ldk, a.ldk, Sk - k0 - XKT, tid, kr);
+      load_cols<XKT>(vbase + (int64_t)(k0 + XKT) * a.ldv, a.ldv, Sk - k0 - XKT, tid, vr);
     }
     if (!live) continue;
+    if constexpr (CAUSAL) { if (k0 > wlim) continue; }           // wave-uniform: every key of the tile lies past this wave's last query
 
     f32x16 st[2];
 #pragma unroll
@@ -217,7 +237,8 @@ __global__ __launch_bounds__(XTHREADS) void xattn_fwd_kernel(XArgs a) {
     for (int blk = 0; blk < 2; ++blk)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const float x = k0 + 32 * blk + acc_row(i, h) < a.Sk ? st[blk][i] * sc2 : -1.0e30f;   // tail keys never win and weigh exp2(-1e30 - m) = 0
+        const int kj = k0 + 32 * blk + acc_row(i, h);
+        const float x = (CAUSAL ? kj <= lim : kj < Sk) ? st[blk][i] * sc2 : -1.0e30f;   // tail (masked) keys never win and weigh exp2(-1e30 - m) = 0
         st[blk][i] = x;
         tmax = fmaxf(tmax, x);
       }
@@ -521,4 +542,33 @@ extern "C" int awt_op_cross_attention_backward(awt_ctx* c, const float* q, int l
   rc = terms == 3 ? launch_kernel<xattn_dq_kernel<3>>(gq, block, dq_lds(3), s, a) : launch_kernel<xattn_dq_kernel<1>>(gq, block, dq_lds(1), s, a);
   if (rc) return rc;
   return terms == 3 ? launch_kernel<xattn_dkv_kernel<3>>(gk, block, dkv_lds(3), s, a) : launch_kernel<xattn_dkv_kernel<1>>(gk, block, dkv_lds(1), s, a);
+}
+
+// ------------------------------------------------------------------------------------------------ causal self-attention over a decode cache (Qwen3Decoder)
+extern "C" size_t awt_op_causal_attention_workspace_bytes(int B, int Hq, int Lq, int T) {
+  (void)T;
+  if (B <= 0 || Hq <= 0 || Lq <= 0) return 0;
+  return xattn_layout(nullptr, B, Hq, Lq, 0).bytes;                // the forward keeps nothing outside its registers and LDS
+}
+
+extern "C" int awt_op_causal_attention(awt_ctx* c, const float* q, int ldq, const float* k, const float* v, int ldkv, int64_t kv_batch_stride, float* o, int ldo,
+                                       int B, int Hq, int Hkv, int Lq, int T, int terms, void* workspace, size_t ws_bytes, void* stream) {
+  AWT_REQUIRE(c && q && k && v && o, AWT_ERR_INVALID, "op_causal_attention: null argument");
+  AWT_REQUIRE(Hkv > 0 && Hq > 0 && Hq % Hkv == 0, AWT_ERR_INVALID, "op_causal_attention: Hq must be a positive multiple of Hkv");
+  AWT_REQUIRE(Lq >= 1 && T >= Lq, AWT_ERR_INVALID, "op_causal_attention: needs 1 <= Lq <= T (T live cache positions, the Lq new ones included)");
+  int rc = check_shape("op_causal_attention", B, Hq, Lq, T, ldq, ldq, ldq, ldo, terms); if (rc) return rc;   // the cache's pitch has Hkv heads: checked below
+  AWT_REQUIRE(ldkv >= (int64_t)Hkv * XD && ldkv % 4 == 0, AWT_ERR_INVALID, "op_causal_attention: ldkv must hold Hkv * 128 columns and be a multiple of 4");
+  AWT_REQUIRE(kv_batch_stride % 4 == 0 && kv_batch_stride >= (int64_t)(T - 1) * ldkv + (int64_t)Hkv * XD, AWT_ERR_INVALID,
+              "op_causal_attention: kv_batch_stride must be a multiple of 4 and hold a batch's T cache rows");
+  AWT_REQUIRE(aligned16(q) && aligned16(k) && aligned16(v) && aligned16(o), AWT_ERR_INVALID, "op_causal_attention: tensors must be 16-byte aligned");
+  AWT_REQUIRE(ws_bytes >= xattn_layout(nullptr, B, Hq, Lq, 0).bytes, AWT_ERR_INVALID, "op_causal_attention: workspace too small");
+  (void)workspace;
+  XArgs a{};
+  a.q = q; a.k = k; a.v = v; a.out = o; a.lse = nullptr; a.B = B; a.H = Hq; a.Hkv = Hkv; a.Lq = Lq; a.Sk = T; a.ldq = ldq; a.ldk = ldkv; a.ldv = ldkv; a.ldo = ldo;
+  a.kvbs = kv_batch_stride;
+  a.scale = 0.08838834764831845f;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(c, AWT_PROF_ATTENTION, s, 2.0 * B * Hq * (double)Lq * (2.0 * T - Lq + 1) * XD * terms);   // the visible (query, key) pairs only
+  const dim3 grid(B * Hq * ((Lq + XLB - 1) / XLB)), block(XTHREADS);
+  return terms == 3 ? launch_kernel<xattn_fwd_kernel<3, true>>(grid, block, fwd_lds(3), s, a) : launch_kernel<xattn_fwd_kernel<1, true>>(grid, block, fwd_lds(1), s, a);
 }

@@ -26,11 +26,16 @@ autograd_ops.py, shared with the classifiers; `_CrossAttention` here):
 The two residual adds, the dtype casts and the row slices of `in_proj_weight` are element-wise / view ops of torch under autograd.  There is no
 torch fallback for any operator above: without libawt or without a GPU the first call raises.
 
+`Qwen3Decoder` and `MusicTranscriptionModel` (further down) are the stock Qwen decoder and the model around all three pieces,
+inference only: teacher-forced loss and logits, and `generate` with a KV cache, on awt_op_rmsnorm / awt_op_qk_norm_rope / awt_op_causal_attention /
+awt_op_silu_mul and the packed-weight GEMMs.
+
 `encode_audio(audio_features)` returns the projected key / value buffer `audio_kv` [B, Sa, 2 text_dim]; `forward(text, audio_kv=audio_kv)` reuses it.
 The reference's `generate` recomputes the projection for every new token (model.py:314-341); a caller of this module computes it once per clip.
 """
 from __future__ import annotations
 
+import dataclasses
 from typing import Optional
 
 import torch
@@ -124,3 +129,304 @@ class CrossAttentionAdapter(nn.Module):
         h = Gelu.apply(self._linear(x, ff[0].weight, ff[0].bias))
         out = self._layer_norm(self.layer_norm2, x + self._linear(h, ff[2].weight, ff[2].bias))
         return out.reshape(B, L, d).to(text_embeddings.dtype)
+
+
+# ====================================================================================================================== Qwen3 text decoder (inference)
+@dataclasses.dataclass
+class Qwen3Config:
+    """The fields of a Qwen3 `config.json` that the decoder reads.  Only head_dim has a default: a checkpoint's other values come from its config, which
+    this package cannot fetch, so they are never assumed -- `Qwen3Config.qwen3_0_6b()` names the published values of Qwen/Qwen3-0.6B-Base."""
+    vocab_size: int
+    hidden_size: int
+    intermediate_size: int
+    num_hidden_layers: int
+    num_attention_heads: int
+    num_key_value_heads: int
+    rms_norm_eps: float
+    rope_theta: float
+    tie_word_embeddings: bool
+    max_position_embeddings: int
+    head_dim: int = HEAD_DIM
+
+    @classmethod
+    def qwen3_0_6b(cls) -> "Qwen3Config":
+        return cls(vocab_size=151936, hidden_size=1024, intermediate_size=3072, num_hidden_layers=28, num_attention_heads=16, num_key_value_heads=8,
+                   rms_norm_eps=1e-6, rope_theta=1e6, tie_word_embeddings=True, max_position_embeddings=40960)
+
+
+class _Weight(nn.Module):
+    """A parameter named `weight`: the RMSNorm gains and the bias-free projections under HF's state-dict names."""
+
+    def __init__(self, *shape, ones: bool = False):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(shape) if ones else torch.empty(shape), requires_grad=False)
+        if not ones:
+            nn.init.normal_(self.weight, std=0.02)                         # HF's initializer_range
+
+
+class Qwen3Cache:
+    """Keys and values of incremental decoding: per layer k and v [B, Tmax, Hkv * 128] (uninitialised: the kernels never read past `length`), the
+    number of live positions, and the int32 position ramp the rotary kernel indexes."""
+
+    def __init__(self, config: Qwen3Config, batch: int, max_length: int, device):
+        if max_length < 1 or max_length > config.max_position_embeddings:
+            raise ValueError(f"max_length must be in [1, {config.max_position_embeddings}] (max_position_embeddings), got {max_length}")
+        w = config.num_key_value_heads * HEAD_DIM
+        self.batch, self.max_length, self.length = batch, max_length, 0
+        self.k = [torch.empty((batch, max_length, w), dtype=torch.float32, device=device) for _ in range(config.num_hidden_layers)]
+        self.v = [torch.empty((batch, max_length, w), dtype=torch.float32, device=device) for _ in range(config.num_hidden_layers)]
+        self.ramp = torch.arange(max_length, dtype=torch.int32, device=device)
+
+
+class Qwen3Decoder(nn.Module):
+    """`Qwen3ForCausalLM` driven by `inputs_embeds` (the reference's text decoder, .charles/music2midi/model.py:209-213), inference only, on libawt:
+
+        per layer   h = RMSNorm(x); q | k | v = h Wqkv^T (ONE GEMM); per-head RMSNorm of q and k, rotary embedding, k and v into the cache (awt_op_qk_norm_rope);
+                    causal attention over the cache with grouped KV heads (awt_op_causal_attention); x += o Wo^T (residual in the GEMM's epilogue);
+                    h = RMSNorm(x); gate | up = h Wgu^T (ONE GEMM); x += (silu(gate) * up) Wdown^T (awt_op_silu_mul, residual in the epilogue)
+        then        logits = RMSNorm(x) Wlm^T
+
+    Parameters carry HF's names (`model.embed_tokens.weight`, `model.layers.N.self_attn.q_proj.weight`, ..., `model.norm.weight`, `lm_head.weight` when
+    untied), fp32; a bf16 checkpoint is upcast by `load_state_dict`.  The packed GEMM operands are built on first use and again after `load_state_dict`,
+    `resize_token_embeddings` or a move to another device.  Everything runs under `torch.no_grad()`; asked for an autograd graph it raises
+    NotImplementedError (training through the decoder is DESIGN.md section 8's next item).  There is no torch fallback: without libawt or a GPU it raises."""
+
+    def __init__(self, config: Qwen3Config, precision: str = "bf16x3"):
+        super().__init__()
+        c = config
+        if c.head_dim != HEAD_DIM:
+            raise ValueError(f"head_dim must be {HEAD_DIM}, the native kernels' head_dim (got {c.head_dim})")
+        if precision not in ("bf16", "bf16x3"):
+            raise ValueError("precision must be 'bf16x3' or 'bf16'")
+        if c.num_attention_heads <= 0 or c.num_key_value_heads <= 0 or c.num_attention_heads % c.num_key_value_heads:
+            raise ValueError("num_attention_heads must be a positive multiple of num_key_value_heads")
+        if c.hidden_size <= 0 or c.hidden_size % 128 or c.intermediate_size <= 0 or c.intermediate_size % 64:
+            raise ValueError("hidden_size must be a multiple of 128 and intermediate_size of 64 (the MFMA GEMM's N tile and K step)")
+        self.config, self.precision = c, precision
+        d, I, Hq, Hkv = c.hidden_size, c.intermediate_size, c.num_attention_heads, c.num_key_value_heads
+        self.model = nn.Module()
+        self.model.embed_tokens = nn.Embedding(c.vocab_size, d)
+        nn.init.normal_(self.model.embed_tokens.weight, std=0.02)
+        self.model.embed_tokens.weight.requires_grad_(False)
+        layers = []
+        for _ in range(c.num_hidden_layers):
+            layer, att, mlp = nn.Module(), nn.Module(), nn.Module()
+            att.q_proj, att.k_proj, att.v_proj, att.o_proj = _Weight(Hq * HEAD_DIM, d), _Weight(Hkv * HEAD_DIM, d), _Weight(Hkv * HEAD_DIM, d), _Weight(d, Hq * HEAD_DIM)
+            att.q_norm, att.k_norm = _Weight(HEAD_DIM, ones=True), _Weight(HEAD_DIM, ones=True)
+            mlp.gate_proj, mlp.up_proj, mlp.down_proj = _Weight(I, d), _Weight(I, d), _Weight(d, I)
+            layer.self_attn, layer.mlp = att, mlp
+            layer.input_layernorm, layer.post_attention_layernorm = _Weight(d, ones=True), _Weight(d, ones=True)
+            layers.append(layer)
+        self.model.layers = nn.ModuleList(layers)
+        self.model.norm = _Weight(d, ones=True)
+        if not c.tie_word_embeddings:
+            self.lm_head = _Weight(c.vocab_size, d)
+        self._packed = None
+        self._rope = None
+
+    # ---- parameters
+    def get_input_embeddings(self) -> nn.Embedding:
+        return self.model.embed_tokens
+
+    def resize_token_embeddings(self, n: int) -> nn.Embedding:
+        """Grows or shrinks the vocabulary to n rows (model.py:221): the rows both sizes share are kept, new rows are drawn as the old ones were initialised;
+        the output head follows (the same tensor when tied)."""
+        old = self.model.embed_tokens.weight
+
+        def resized(w):
+            out = torch.empty((n, w.shape[1]), dtype=w.dtype, device=w.device)
+            nn.init.normal_(out, std=0.02)
+            out[: min(n, w.shape[0])] = w[: min(n, w.shape[0])]
+            return nn.Parameter(out, requires_grad=False)
+
+        emb = nn.Embedding(n, old.shape[1], device=old.device, dtype=old.dtype)
+        emb.weight = resized(old)
+        self.model.embed_tokens = emb
+        if not self.config.tie_word_embeddings:
+            self.lm_head.weight = resized(self.lm_head.weight)
+        self.config = dataclasses.replace(self.config, vocab_size=n)
+        self._packed = None
+        return emb
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        sd = {k: (v.float() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in state_dict.items()}
+        if self.config.tie_word_embeddings:
+            sd.pop("lm_head.weight", None)                                 # HF lists the tied head as a second name of the embedding
+        out = super().load_state_dict(sd, strict=strict, **kw)
+        self._packed = None
+        return out
+
+    def _apply(self, fn, *a, **kw):
+        self._packed, self._rope = None, None
+        return super()._apply(fn, *a, **kw)
+
+    def _pack(self) -> dict:
+        if self._packed is None:
+            from .native_decoder import PackedLinear
+            mk = lambda w: PackedLinear(w, None, self.precision, backward=False)
+            layers = []
+            for layer in self.model.layers:
+                att, mlp = layer.self_attn, layer.mlp
+                layers.append({"qkv": mk(torch.cat([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])), "o": mk(att.o_proj.weight),
+                               "gu": mk(torch.cat([mlp.gate_proj.weight, mlp.up_proj.weight])), "down": mk(mlp.down_proj.weight)})
+            head = self.model.embed_tokens.weight if self.config.tie_word_embeddings else self.lm_head.weight
+            self._packed = {"layers": layers, "lm_head": mk(head)}
+        return self._packed
+
+    def _rope_tables(self, device):
+        """cos / sin [max_position_embeddings, 64] fp32 as HF's Qwen3RotaryEmbedding forms them: fp32 inv_freq, fp32 outer product, then cos / sin."""
+        if self._rope is None or self._rope[0].device != device:
+            c = self.config
+            inv_freq = 1.0 / (c.rope_theta ** (torch.arange(0, HEAD_DIM, 2, dtype=torch.int64).to(dtype=torch.float32) / HEAD_DIM))   # on the host, as HF does
+            ang = torch.arange(c.max_position_embeddings, dtype=torch.float32)[:, None] * inv_freq[None, :]
+            self._rope = (ang.cos().to(device).contiguous(), ang.sin().to(device).contiguous())
+        return self._rope
+
+    # ---- the layers
+    def _check_input(self, x: torch.Tensor) -> None:
+        if x.dim() != 3 or x.shape[-1] != self.config.hidden_size:
+            raise ValueError(f"inputs_embeds must be [B, L, {self.config.hidden_size}], got {tuple(x.shape)}")
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("Qwen3Decoder is inference only: there is no backward through the decoder (call it under torch.no_grad(), with its "
+                                      "parameters frozen); training is DESIGN.md section 8's next item")
+        _lib.ctx(x.device)                                                 # raises without a GPU: no CPU fallback
+
+    @staticmethod
+    def _check_mask(m: Optional[torch.Tensor], B: int, L: int) -> None:
+        if m is not None and (tuple(m.shape) != (B, L) or bool(((m != 0) & (m != 1)).any()) or bool((m[:, 1:] > m[:, :-1]).any())):
+            raise ValueError("attention_mask must be [B, L] rows of ones followed by zeros (right padding); other masks are not supported")
+
+    @torch.no_grad()
+    def _run(self, inputs_embeds: torch.Tensor, cache: Qwen3Cache, last_only: bool) -> torch.Tensor:
+        """Appends the L positions of inputs_embeds [B, L, hidden] to the cache; the lm_head GEMM's output [B * L, Np] (Np = vocab padded to the GEMM's N
+        tile), or [B, Np] for the last position of each row with last_only."""
+        c, dev = self.config, inputs_embeds.device
+        B, L, d = inputs_embeds.shape
+        if B != cache.batch or cache.length + L > cache.max_length:
+            raise ValueError(f"the cache holds {cache.batch} rows of {cache.max_length} positions ({cache.length} live); cannot append [{B}, {L}]")
+        Hq, Hkv, I, eps = c.num_attention_heads, c.num_key_value_heads, c.intermediate_size, c.rms_norm_eps
+        M, T, wkv = B * L, cache.length + L, Hkv * HEAD_DIM
+        packed, (cos, sin) = self._pack(), self._rope_tables(dev)
+        positions = cache.ramp[cache.length:T]
+        positions = positions if B == 1 else positions.repeat(B)
+        x = inputs_embeds.float().reshape(M, d).contiguous()
+        if x.data_ptr() == inputs_embeds.data_ptr():
+            x = x.clone()                                                  # the residual GEMMs write x in place
+        q = torch.empty((M, Hq * HEAD_DIM), dtype=torch.float32, device=dev)
+        o = torch.empty_like(q)
+        h = torch.empty_like(x)
+        act = torch.empty((M, I), dtype=torch.float32, device=dev)
+        ws = _lib.workspace(ops.causal_attention_workspace_bytes(B, Hq, L, T), dev)
+        for i, (layer, pk) in enumerate(zip(self.model.layers, packed["layers"])):
+            ops.rmsnorm((x, 0), d, layer.input_layernorm.weight, M, d, eps, y=(h, 0), ldy=d)
+            qkv = pk["qkv"].forward(h)
+            ops.qk_norm_rope((qkv, 0), pk["qkv"].Np, layer.self_attn.q_norm.weight, layer.self_attn.k_norm.weight, cos, sin, positions, (q, 0), Hq * HEAD_DIM,
+                             (cache.k[i], 0), (cache.v[i], 0), wkv, cache.max_length * wkv, B, L, Hq, Hkv, eps)
+            ops.causal_attention((q, 0), Hq * HEAD_DIM, (cache.k[i], 0), (cache.v[i], 0), wkv, cache.max_length * wkv, B, Hq, Hkv, L, T, self.precision,
+                                 o=(o, 0), ldo=Hq * HEAD_DIM, workspace=ws)
+            pk["o"].forward(o, resid=x, out=x)
+            ops.rmsnorm((x, 0), d, layer.post_attention_layernorm.weight, M, d, eps, y=(h, 0), ldy=d)
+            gu = pk["gu"].forward(h)
+            ops.silu_mul((gu, 0), pk["gu"].Np, M, I, y=(act, 0), ldy=I)
+            pk["down"].forward(act, resid=x, out=x)
+        cache.length = T
+        if last_only:
+            x = x.view(B, L, d)[:, -1].contiguous()
+        hn = ops.rmsnorm((x, 0), d, self.model.norm.weight, x.shape[0], d, eps)
+        return packed["lm_head"].forward(hn)
+
+    def prefill(self, inputs_embeds: torch.Tensor, cache: Qwen3Cache) -> torch.Tensor:
+        """Appends L positions to the cache (from position cache.length on); returns the last position's logits [B, vocab] (a view of the padded GEMM output)."""
+        self._check_input(inputs_embeds)
+        return self._run(inputs_embeds, cache, True)[:, : self.config.vocab_size]
+
+    def step(self, inputs_embeds: torch.Tensor, cache: Qwen3Cache) -> torch.Tensor:
+        """One new position per row: inputs_embeds [B, 1, hidden] -> logits [B, vocab]; the lm_head GEMM has B rows."""
+        self._check_input(inputs_embeds)
+        if inputs_embeds.shape[1] != 1:
+            raise ValueError(f"step takes one position per row, got {inputs_embeds.shape[1]} (use prefill)")
+        return self._run(inputs_embeds, cache, True)[:, : self.config.vocab_size]
+
+    def forward(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None):
+        """logits [B, L, vocab], and with labels (logits, loss): HF's causal-LM loss -- the logits at t against the label at t + 1, ignore_index -100, mean over
+        the counted positions (awt_op_cross_entropy).  attention_mask: rows of ones followed by zeros (right padding) or None.  Under causality a live position
+        never sees a padded one, so the mask changes nothing at live positions and is only validated; the outputs at padded positions are unspecified."""
+        self._check_input(inputs_embeds)
+        B, L, _ = inputs_embeds.shape
+        self._check_mask(attention_mask, B, L)
+        if labels is not None and tuple(labels.shape) != (B, L):
+            raise ValueError(f"labels must be [{B}, {L}], got {tuple(labels.shape)}")
+        padded = self._run(inputs_embeds, Qwen3Cache(self.config, B, L, inputs_embeds.device), False)
+        logits = padded.view(B, L, -1)[:, :, : self.config.vocab_size]
+        if labels is None:
+            return logits
+        from .native_decoder import cross_entropy
+        shifted = torch.full((B, L), -100, dtype=torch.int64, device=padded.device)
+        shifted[:, :-1] = labels[:, 1:].to(padded.device)
+        return logits, cross_entropy(padded, shifted.reshape(-1), self.config.vocab_size)[0]
+
+
+class MusicTranscriptionModel(nn.Module):
+    """The reference's MusicTranscriptionModel (model.py:190-344) from its three pieces: an audio tower (`WhisperAudioEncoder`, or any callable
+    (waveforms, sampling_rate) -> [B, Sa, audio_dim]), the `CrossAttentionAdapter` and a `Qwen3Decoder`.  Inference only: `forward` returns the
+    teacher-forced loss under `torch.no_grad()`, `generate` decodes with a KV cache."""
+
+    def __init__(self, audio_encoder, adapter: CrossAttentionAdapter, decoder: Qwen3Decoder, tokenizer=None):
+        super().__init__()
+        if adapter.text_dim != decoder.config.hidden_size:
+            raise ValueError(f"the adapter's text_dim ({adapter.text_dim}) must be the decoder's hidden_size ({decoder.config.hidden_size})")
+        self.audio_encoder, self.cross_attention_adapter, self.text_decoder, self.tokenizer = audio_encoder, adapter, decoder, tokenizer
+
+    def _embed(self, ids: torch.Tensor) -> torch.Tensor:
+        emb = self.text_decoder.get_input_embeddings()
+        return emb(ids.to(emb.weight.device))
+
+    def forward(self, waveforms, sampling_rate: int, target_token_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The teacher-forced loss of model.py:263-288 (labels = target_token_ids, shifted inside).  The reference leaves the labels at padded positions as
+        they are; so does this: pass -100 there through `target_token_ids`' own padding convention if they are to be ignored."""
+        if torch.is_grad_enabled():
+            raise NotImplementedError("MusicTranscriptionModel.forward is inference only: the adapter's gradient needs a backward through the decoder "
+                                      "(call it under torch.no_grad())")
+        audio = self.audio_encoder(waveforms, sampling_rate)
+        fused = self.cross_attention_adapter(self._embed(target_token_ids.clamp_min(0)), audio.float())
+        return self.text_decoder(fused, attention_mask=attention_mask, labels=target_token_ids)[1]
+
+    @torch.no_grad()
+    def generate(self, waveform, sampling_rate: int, max_new_tokens: int = 256, temperature: float = 0.7, do_sample: bool = True,
+                 generator: Optional[torch.Generator] = None, bos_token_id=None, eos_token_id: Optional[int] = None):
+        """model.py:293-344 with a KV cache: the audio is projected once (`encode_audio`), and each step runs the adapter on the NEW token's embedding only --
+        the adapter is position-wise in the text and causal decoding over a cache equals full recomputation, so this is the reference's computation, not an
+        approximation of it.  bos_token_id: the start token, or a sequence of prompt ids; with a tokenizer both ids default to its bos (else eos) / eos ids
+        and the decoded string is returned, without one the ids are required and the generated ids are returned (EOS excluded, as the reference does).
+        do_sample: torch.multinomial(softmax(logits / temperature)) with `generator`, the reference's expression; else argmax (awt_op_select_tokens)."""
+        from .generation import select_tokens
+        tok, dec = self.tokenizer, self.text_decoder
+        if bos_token_id is None and tok is not None:
+            bos_token_id = tok.bos_token_id if tok.bos_token_id is not None else tok.eos_token_id
+        if eos_token_id is None and tok is not None:
+            eos_token_id = tok.eos_token_id
+        if bos_token_id is None or eos_token_id is None:
+            raise ValueError("generate needs bos_token_id and eos_token_id when the model has no tokenizer")
+        if do_sample and not temperature > 0:
+            raise ValueError("temperature must be positive when sampling")
+        prompt = [int(bos_token_id)] if isinstance(bos_token_id, int) else [int(t) for t in bos_token_id]
+        if not prompt or max_new_tokens < 1:
+            raise ValueError("generate needs at least one prompt token and max_new_tokens >= 1")
+        dev, vocab = dec.get_input_embeddings().weight.device, dec.config.vocab_size
+        audio = self.audio_encoder([waveform], sampling_rate)
+        audio_kv = self.cross_attention_adapter.encode_audio(audio.float().to(dev))
+        cache = Qwen3Cache(dec.config, 1, len(prompt) + max_new_tokens - 1, dev)
+        ids = torch.tensor([prompt], dtype=torch.long, device=dev)
+        out = []
+        for n in range(max_new_tokens):
+            fused = self.cross_attention_adapter(self._embed(ids), audio_kv=audio_kv)
+            logits = dec.prefill(fused, cache) if n == 0 else dec.step(fused, cache)
+            if do_sample:
+                ids = torch.multinomial(torch.softmax(logits / temperature, dim=-1), 1, generator=generator)
+            else:
+                ids = select_tokens(logits, vocab)[1][:, :1]
+            nxt = int(ids.item())
+            if nxt == eos_token_id:
+                break
+            out.append(nxt)
+        return tok.decode(out, skip_special_tokens=True) if tok is not None else out

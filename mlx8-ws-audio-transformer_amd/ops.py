@@ -222,3 +222,62 @@ def cross_attention_backward(q, ldq: int, k, ldk: int, v, ldv: int, o, dout, ldo
         _lib.check(L.awt_op_cross_attention_backward(_lib.ctx(dev), _at(q), int(ldq), _at(k), int(ldk), _at(v), int(ldv), _at(o), _at(dout), int(ldo),
                                                      _lib.ptr(lse), _at(dq), _at(dk), _at(dv), B, H, Lq, Sk, int(terms), _lib.ptr(ws), ws.numel(),
                                                      _lib.stream_handle()))
+
+
+# ---- the operators of a Qwen3 decoder layer (include/awt.h; csrc/qwen_ops.hip and the causal variant of csrc/cross_attention.hip)
+def rmsnorm(x, ldx: int, gamma: torch.Tensor, M: int, d: int, eps: float, y=None, ldy: Optional[int] = None):
+    """y[m, :] = gamma * x[m, :] * rsqrt(mean(x[m, :]^2) + eps) (awt_op_rmsnorm).  x (and y, when given with its pitch ldy): (tensor, element offset) pairs over
+    row-major fp32 matrices of pitch ldx / ldy.  Returns y's tensor ([M, d] unless given)."""
+    dev = x[0].device
+    if y is None:
+        y, ldy = (torch.empty((M, d), dtype=torch.float32, device=dev), 0), d
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().awt_op_rmsnorm(_lib.ctx(dev), _at(x), int(ldx), _at((gamma, 0)), _at(y), int(ldy), int(M), int(d), float(eps), _lib.stream_handle()))
+    return y[0]
+
+
+def qk_norm_rope(qkv, ld: int, q_gamma: torch.Tensor, k_gamma: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, positions: torch.Tensor, q_out, ldq: int,
+                 k_cache, v_cache, ldkv: int, kv_batch_stride: int, B: int, Lq: int, Hq: int, Hkv: int, eps: float) -> None:
+    """Per-head RMSNorm of q and k, rotary embedding, q to q_out, k and v into the decode cache at positions[r] (awt_op_qk_norm_rope).  qkv, q_out, k_cache,
+    v_cache: (tensor, element offset) pairs; cos / sin fp32 [rows, 64]; positions int32 [B * Lq] on the device."""
+    dev = qkv[0].device
+    if positions.dtype != torch.int32 or positions.numel() != B * Lq or not positions.is_contiguous():
+        raise ValueError("qk_norm_rope: positions must be a contiguous int32 tensor of B * Lq elements")
+    if cos.dtype != torch.float32 or sin.dtype != torch.float32 or cos.shape != sin.shape or cos.dim() != 2 or cos.shape[1] != 64:
+        raise ValueError("qk_norm_rope: cos and sin must be float32 [rows, 64]")
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().awt_op_qk_norm_rope(_lib.ctx(dev), _at(qkv), int(ld), _at((q_gamma, 0)), _at((k_gamma, 0)), _at((cos, 0)), _at((sin, 0)),
+                                                  _lib.ptr(positions), _at(q_out), int(ldq), _at(k_cache), _at(v_cache), int(ldkv), int(kv_batch_stride),
+                                                  int(B), int(Lq), int(Hq), int(Hkv), float(eps), _lib.stream_handle()))
+
+
+def causal_attention_workspace_bytes(B: int, Hq: int, Lq: int, T: int) -> int:
+    """Workspace of `causal_attention`; answers without a GPU."""
+    return int(_lib.lib().awt_op_causal_attention_workspace_bytes(int(B), int(Hq), int(Lq), int(T)))
+
+
+def causal_attention(q, ldq: int, k, v, ldkv: int, kv_batch_stride: int, B: int, Hq: int, Hkv: int, Lq: int, T: int, precision="bf16x3", o=None,
+                     ldo: Optional[int] = None, workspace: Optional[torch.Tensor] = None):
+    """Causal attention of Lq new query rows per batch over T live positions of a decode cache, head_dim 128, grouped KV heads (awt_op_causal_attention).
+    q / k / v (and o, when given with its pitch ldo): (tensor, element offset) pairs.  Returns o's tensor ([B * Lq, Hq * 128] unless given)."""
+    terms = precision if isinstance(precision, int) else _terms(precision)
+    dev = q[0].device
+    if o is None:
+        o, ldo = (torch.empty((B * Lq, Hq * 128), dtype=torch.float32, device=dev), 0), Hq * 128
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_op_causal_attention_workspace_bytes(B, Hq, Lq, T), dev) if workspace is None else workspace
+    with torch.cuda.device(dev):
+        _lib.check(L.awt_op_causal_attention(_lib.ctx(dev), _at(q), int(ldq), _at(k), _at(v), int(ldkv), int(kv_batch_stride), _at(o), int(ldo), int(B), int(Hq),
+                                             int(Hkv), int(Lq), int(T), int(terms), _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
+    return o[0]
+
+
+def silu_mul(gu, ld: int, M: int, I: int, y=None, ldy: Optional[int] = None):
+    """y[m, i] = silu(gu[m, i]) * gu[m, I + i] (awt_op_silu_mul).  gu (and y, when given with its pitch ldy): (tensor, element offset) pairs.  Returns y's
+    tensor ([M, I] unless given)."""
+    dev = gu[0].device
+    if y is None:
+        y, ldy = (torch.empty((M, I), dtype=torch.float32, device=dev), 0), I
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().awt_op_silu_mul(_lib.ctx(dev), _at(gu), int(ld), _at(y), int(ldy), int(M), int(I), _lib.stream_handle()))
+    return y[0]
