@@ -421,10 +421,16 @@ int awt_op_cross_entropy(awt_ctx* c, const float* logits, const int64_t* labels,
 /* softmax(0.125 q k^T [+ causal mask]) v for head_dim 64 with few query rows.  Row (b, i) of q at q + (b Lq + i) ldq + 64 h; row
  * (b, j) of k / v at k + (b Sk + j) ldk + 64 h; o like q with ldo.  causal != 0: key j is visible to query i iff
  * j <= i + causal_off (causal_off = Sk - Lq for cached decoding).  lse [B, H, Lq] (optional) feeds the backward pass.
- * HF:modeling_whisper.py:215-238, 284-356 (q scaled by head_dim^-1/2; eager attention with the causal mask). */
+ * HF:modeling_whisper.py:215-238, 284-356 (q scaled by head_dim^-1/2; eager attention with the causal mask).
+ * Refused with AWT_ERR_INVALID, by this entry and by every other one of the family (the backward, the dropout pair, awt_op_attention_cached): a null
+ * pointer, a pitch below H * 64 or not a multiple of 4, B * H * Lq >= 2^31, causal != 0 with causal_off < 0 (the first query rows would see no key at
+ * all: 0 / 0 in o, -inf in lse), and q, k, v, o -- in the backward also dout, dq, dk, dv -- not 16-byte aligned (the kernels use 16-byte accesses).
+ * No atomics: two runs give the same bits. */
 int awt_op_attention_small(awt_ctx* c, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* o, int ldo,
                            float* lse, int B, int H, int Lq, int Sk, int causal, int causal_off, void* stream);
-/* dq (layout of q), dk / dv (layout of k / v: every element of the B x Sk x H x 64 blocks is written); delta [B, H, Lq] scratch */
+/* dq (layout of q), dk / dv (layout of k / v: every element of the B x Sk x H x 64 blocks is written); delta [B, H, Lq] = rowsum(dout * o), an
+ * output.  P is recomputed as exp(s - lse) with s formed by the forward's own instruction sequence, so that it is the forward's P to fp32 rounding
+ * at any score magnitude. */
 int awt_op_attention_small_backward(awt_ctx* c, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o,
                                     const float* dout, int ldo, const float* lse, float* delta, float* dq, float* dk, float* dv, int B,
                                     int H, int Lq, int Sk, int causal, int causal_off, void* stream);

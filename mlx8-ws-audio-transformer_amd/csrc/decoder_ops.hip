@@ -227,6 +227,15 @@ __device__ __forceinline__ float drop_keep(const SmallAttn& a, int bh, int i, in
   return ((float)(unsigned)(z >> 40) * (1.0f / 16777216.0f) >= a.drop_p) ? a.inv_keep : 0.0f;
 }
 
+// One group of four of a score sum s_ij = q_i . k_j, spelled out so that the forward and both backward kernels issue the same instructions for it.  The
+// backward recomputes P = exp(s - lse) from the forward's lse; left to the compiler, a plain a*b + c*d + ... is contracted and paired differently from
+// kernel to kernel (packed multiplies and adds in one, an FMA chain in another), and a score that differs from the forward's in its last place is a
+// relative error of ulp(|s|) in P: 4e-6 at |s| = 64, where fp32 allows 1e-7.  The order is the one the forward was compiled to.
+__device__ __forceinline__ float score4(float s, const float4& q, float k0, float k1, float k2, float k3) {
+#pragma clang fp contract(off)
+  return s + __builtin_fmaf(q.w, k3, __builtin_fmaf(q.z, k2, __builtin_fmaf(q.x, k0, q.y * k1)));
+}
+
 // ---------------------------------------------------------------------------------------------- parameter-gradient reductions
 // (trainable consumers of the operators: the UrbanSound8K Transformer classifier, /root/reference/.charles/spectrogram.py:944-1160)
 // Column sums over a slab of rows: sums[c] = sum_m a[m, c] (bias gradients) and, for LayerNorm, dgamma[c] = sum_m dy[m, c] xhat[m, c],
@@ -333,7 +342,7 @@ __global__ __launch_bounds__(256) void small_attn_fwd_kernel(SmallAttn a) {
     for (int i = 0; i < QB; ++i) {
       float s = 0.f;
 #pragma unroll
-      for (int e = 0; e < 64; e += 4) { const float4 t = *reinterpret_cast<const float4*>(&qs[i][e]); s += t.x * k[e] + t.y * k[e + 1] + t.z * k[e + 2] + t.w * k[e + 3]; }
+      for (int e = 0; e < 64; e += 4) s = score4(s, *reinterpret_cast<const float4*>(&qs[i][e]), k[e], k[e + 1], k[e + 2], k[e + 3]);
       const bool ok = j <= kmax && i < nq && (!a.causal || j <= i0 + i + a.causal_off);
       s = ok ? s : -3.0e38f;
       const float m_new = fmaxf(m[i], wave_max(s));
@@ -421,7 +430,7 @@ __global__ __launch_bounds__(256) void small_attn_dq_kernel(SmallAttn a) {
 #pragma unroll
       for (int e = 0; e < 64; e += 4) {
         const float4 t = *reinterpret_cast<const float4*>(&qs[i][e]), u = *reinterpret_cast<const float4*>(&gs[i][e]);
-        s += t.x * k[e] + t.y * k[e + 1] + t.z * k[e + 2] + t.w * k[e + 3];
+        s = score4(s, t, k[e], k[e + 1], k[e + 2], k[e + 3]);
         dp += u.x * v[e] + u.y * v[e + 1] + u.z * v[e + 2] + u.w * v[e + 3];
       }
       const bool ok = j <= kmax && i < nq && (!a.causal || j <= i0 + i + a.causal_off);
@@ -503,7 +512,7 @@ __global__ __launch_bounds__(64) void small_attn_dkv_kernel(SmallAttn a) {
 #pragma unroll
     for (int e = 0; e < 64; e += 4) {      // wave-uniform addresses: scalar loads
       const float4 t = *reinterpret_cast<const float4*>(qr + e), u = *reinterpret_cast<const float4*>(gr + e);
-      s += k[e] * t.x + k[e + 1] * t.y + k[e + 2] * t.z + k[e + 3] * t.w;
+      s = score4(s, t, k[e], k[e + 1], k[e + 2], k[e + 3]);      // of the unscaled q: 8 x the forward's sum, bit for bit
       dp += v[e] * u.x + v[e + 1] * u.y + v[e + 2] * u.z + v[e + 3] * u.w;
     }
     const bool on = live && i >= i0;
@@ -527,6 +536,11 @@ int check_small(const SmallAttn& a, const char* who) {
               AWT_ERR_INVALID, std::string(who) + ": row strides must be multiples of 4 and cover H * 64 columns");
   AWT_REQUIRE((int64_t)a.B * a.H * a.Lq < (1ll << 31), AWT_ERR_INVALID, std::string(who) + ": too many query rows");
   AWT_REQUIRE(a.drop_p >= 0.f && a.drop_p < 1.f, AWT_ERR_INVALID, std::string(who) + ": dropout probability must be in [0, 1)");
+  // a negative offset leaves the first query rows without a visible key: 0 / 0 in o and -inf in lse
+  AWT_REQUIRE(!a.causal || a.causal_off >= 0, AWT_ERR_INVALID, std::string(who) + ": causal_off must not be negative");
+  auto aligned16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };        // float4 accesses; a null pointer (the forward's unused gradients) passes
+  AWT_REQUIRE(aligned16(a.q) && aligned16(a.k) && aligned16(a.v) && aligned16(a.o) && aligned16(a.dout) && aligned16(a.dq) && aligned16(a.dk) && aligned16(a.dv),
+              AWT_ERR_INVALID, std::string(who) + ": tensors must be 16-byte aligned");
   return AWT_OK;
 }
 
