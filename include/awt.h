@@ -273,6 +273,22 @@ int awt_op_layernorm(awt_ctx* c, const float* x /*[M,d]*/, const float* gamma, c
 int awt_op_attention(awt_ctx* c, const float* q, const float* k, const float* v, float* o, int B, int H, int S,
                      int terms, void* workspace, size_t ws_bytes, void* stream);
 size_t awt_op_attention_workspace_bytes(int B, int H, int S);
+/* awt_op_attention with every output form of the forward kernels, as the encoder layer launches them.  No kernel of its own: the operand planes are
+ * written into the workspace (awt_op_attention's layout and size), one launch follows, and the bytes the kernel wrote are the result.
+ *   in:  q (already scaled), k, v: float32 [B, H, S, 64].
+ *   out: exactly one of
+ *          o_f32  float32 [B, S, H*64];
+ *          planes [B*S, H*64]: terms 1 / 3 bf16, 2 / 4 fp16, o_hi (+ o_lo with terms 3 / 4; not written and may be NULL with terms 1 / 2);
+ *                 terms 5: o_hi = fp16, o_hi8 = e4m3(o 2^-2) (may be NULL: not written), o_lo8 = e4m3((o - fp16(o)) 2^9);
+ *          o_ilv  (terms 5) the same three images as split lines: [B*S][H] pairs of 128-byte lines, 64 fp16, then 64 hi8 | 64 lo8;
+ *        and optionally lse2: float32 [B, H, S], log2 of each row's sum of 2^(score log2 e).
+ * With terms 5 the f16f8 form is chosen as in the encoder (tuning knob "attn_shape", else: lse2 requested -> every cross term on 4 or 8 waves, not
+ * requested -> P V as one fp16 product), and v's two e4m3 images are written only for a form that reads them.
+ * AWT_ERR_INVALID before anything is written: no output or more than one output form, split lines with terms != 5, planes without o_lo (terms 3 / 4) or
+ * without o_lo8 (terms 5), a shape that is not positive; AWT_ERR_WORKSPACE: ws_bytes below awt_op_attention_ex_workspace_bytes. */
+int awt_op_attention_ex(awt_ctx* c, const float* q, const float* k, const float* v, float* o_f32, void* o_hi, void* o_lo, void* o_hi8, void* o_lo8,
+                        void* o_ilv, float* lse2, int B, int H, int S, int terms, void* workspace, size_t ws_bytes, void* stream);
+size_t awt_op_attention_ex_workspace_bytes(int B, int H, int S);
 /* The attention of one encoder layer's training pass on caller tensors: the training form of the forward (row-major o planes and the saved
  * log-sum-exp), then the backward kernel with the arguments awt_encoder_backward gives it.  No kernel of its own.
  *   in:  q (already scaled by head_dim^-1/2, as for awt_op_attention), k, v: float32 [B, H, S, 64];  d_o = dL/do: float32 [B, S, H*64]

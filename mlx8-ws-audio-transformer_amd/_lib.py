@@ -95,6 +95,8 @@ _SIGNATURES = {
     "awt_op_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "awt_op_attention": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "awt_op_attention_workspace_bytes": (_sz, [_i, _i, _i]),
+    "awt_op_attention_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "awt_op_attention_ex_workspace_bytes": (_sz, [_i, _i, _i]),
     "awt_op_attention_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _i, _vp, _sz, _vp]),
     "awt_op_attention_backward_workspace_bytes": (_sz, [_i, _i, _i]),
     "awt_weight_create": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, C.POINTER(_vp)]),

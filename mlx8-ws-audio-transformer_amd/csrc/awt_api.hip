@@ -1089,6 +1089,24 @@ extern "C" int awt_op_layernorm(awt_ctx* c, const float* x, const float* gamma, 
   return launch_layernorm(c, x, gamma, beta, M, d, eps, y, Act{}, PREC_BF16X3, (hipStream_t)stream);
 }
 
+namespace {
+// q, k, v [B, H, S, 64] fp32 as the operand planes of `terms` in awt_op_attention's workspace (the kernels expect q * log2(e); f16f8: the second 2-byte
+// plane holds the two e4m3 planes).  v8 = false (f16f8): v's fp16 plane alone, as the QKV epilogue's skip_v8 leaves it.
+int op_attention_planes(awt_ctx* c, const float* q, const float* k, const float* v, int64_t n, int terms, const OpAttentionWs& ws, bool v8, hipStream_t s) {
+  bf16_t* const pl[6] = {ws.q.hi, ws.q.lo, ws.k.hi, ws.k.lo, ws.v.hi, ws.v.lo};
+  const float* src[3] = {q, k, v};
+  const int f8exp[3] = {kF8Q, kF8KV, kF8KV};
+  for (int i = 0; i < 3; ++i) {
+    uint8_t* b8 = (uint8_t*)pl[2 * i + 1];
+    const int prec = (terms == PREC_F16F8 && i == 2 && !v8) ? PREC_F16 : terms;      // PREC_F16 writes the same fp16 plane and nothing else
+    int rc = launch_split_planes(c, src[i], n, i == 0 ? 1.4426950408889634f : 1.0f, prec, f8exp[i], pl[2 * i], pl[2 * i + 1], b8, b8 + n, s);
+    if (rc) return rc;
+  }
+  return AWT_OK;
+}
+F8Planes op_attention_f8(const PlanePair& p, int64_t n) { return F8Planes{p.hi, (uint8_t*)p.lo, (uint8_t*)p.lo + n}; }
+}  // namespace
+
 extern "C" size_t awt_op_attention_workspace_bytes(int B, int H, int S) { return op_attention_layout(nullptr, B, H, S).bytes; }
 extern "C" int awt_op_attention(awt_ctx* c, const float* q, const float* k, const float* v, float* o, int B, int H, int S,
                                 int terms, void* workspace, size_t ws_bytes, void* stream) {
@@ -1098,20 +1116,38 @@ extern "C" int awt_op_attention(awt_ctx* c, const float* q, const float* k, cons
   hipStream_t s = (hipStream_t)stream;
   const int64_t n = (int64_t)B * H * S * 64;
   const OpAttentionWs ws = op_attention_layout(workspace, B, H, S);
-  bf16_t* const pl[6] = {ws.q.hi, ws.q.lo, ws.k.hi, ws.k.lo, ws.v.hi, ws.v.lo};
-  const float* src[3] = {q, k, v};
-  const int f8exp[3] = {kF8Q, kF8KV, kF8KV};
-  for (int i = 0; i < 3; ++i) {   // the kernel expects q * log2(e); f16f8: the second 2-byte plane holds the two e4m3 planes
-    uint8_t* b8 = (uint8_t*)pl[2 * i + 1];
-    int rc = launch_split_planes(c, src[i], n, i == 0 ? 1.4426950408889634f : 1.0f, terms, f8exp[i], pl[2 * i], pl[2 * i + 1], b8, b8 + n, s);
-    if (rc) return rc;
+  int rc = op_attention_planes(c, q, k, v, n, terms, ws, true, s); if (rc) return rc;
+  if (terms == PREC_F16F8)
+    return launch_attention_f16f8(c, op_attention_f8(ws.q, n), op_attention_f8(ws.k, n), op_attention_f8(ws.v, n), F8Planes{nullptr, nullptr, nullptr}, o, nullptr, B, H, S, s);
+  return launch_attention(c, ws.q.hi, ws.q.lo, ws.k.hi, ws.k.lo, ws.v.hi, ws.v.lo, nullptr, nullptr, o, nullptr, B, H, S, terms, s);
+}
+
+// awt_op_attention with the output forms and the log-sum-exp the encoder layer asks of the same launchers (encoder_layer): everything either launcher
+// would refuse is refused here first, under this entry's name
+extern "C" size_t awt_op_attention_ex_workspace_bytes(int B, int H, int S) { return op_attention_layout(nullptr, B, H, S).bytes; }
+extern "C" int awt_op_attention_ex(awt_ctx* c, const float* q, const float* k, const float* v, float* o_f32, void* o_hi, void* o_lo, void* o_hi8,
+                                   void* o_lo8, void* o_ilv, float* lse2, int B, int H, int S, int terms, void* workspace, size_t ws_bytes, void* stream) {
+  AWT_REQUIRE(prec_known(terms), AWT_ERR_INVALID, "op_attention_ex: terms must be 1 (bf16), 2 (fp16), 3 (bf16x3), 4 (fp16x3) or 5 (f16f8)");
+  AWT_REQUIRE(c && q && k && v && workspace, AWT_ERR_INVALID, "op_attention_ex: null argument");
+  AWT_REQUIRE(B > 0 && H > 0 && S > 0, AWT_ERR_INVALID, "op_attention_ex: bad shape");
+  const bool f8 = terms == PREC_F16F8, planes = o_hi || o_lo || o_hi8 || o_lo8;
+  AWT_REQUIRE((o_f32 != nullptr) + (o_ilv != nullptr) + planes == 1, AWT_ERR_INVALID, "op_attention_ex: exactly one of o_f32, the output planes and o_ilv is required");
+  AWT_REQUIRE(!o_ilv || f8, AWT_ERR_INVALID, "op_attention_ex: a split-line output is an f16f8 format (terms 5)");
+  if (planes) {
+    AWT_REQUIRE(o_hi, AWT_ERR_INVALID, "op_attention_ex: null o_hi");
+    if (f8) AWT_REQUIRE(o_lo8 && !o_lo, AWT_ERR_INVALID, "op_attention_ex: terms 5 writes o_hi, o_hi8 (optional) and o_lo8; o_lo8 is null or o_lo is set");
+    else AWT_REQUIRE(!o_hi8 && !o_lo8 && (prec_products(terms) == 1 || o_lo), AWT_ERR_INVALID, "op_attention_ex: terms 1 - 4 write o_hi and, with terms 3 / 4, o_lo");
   }
-  if (terms == PREC_F16F8) {
-    F8Planes P[3];
-    for (int i = 0; i < 3; ++i) P[i] = F8Planes{pl[2 * i], (uint8_t*)pl[2 * i + 1], (uint8_t*)pl[2 * i + 1] + n};
-    return launch_attention_f16f8(c, P[0], P[1], P[2], F8Planes{nullptr, nullptr, nullptr}, o, nullptr, B, H, S, s);
-  }
-  return launch_attention(c, pl[0], pl[1], pl[2], pl[3], pl[4], pl[5], nullptr, nullptr, o, nullptr, B, H, S, terms, s);
+  AWT_REQUIRE(ws_bytes >= awt_op_attention_ex_workspace_bytes(B, H, S), AWT_ERR_WORKSPACE, "op_attention_ex: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n = (int64_t)B * H * S * 64;
+  const OpAttentionWs ws = op_attention_layout(workspace, B, H, S);
+  int rc = op_attention_planes(c, q, k, v, n, terms, ws, !f8 || attention_f16f8_reads_v8(lse2 != nullptr), s); if (rc) return rc;
+  if (f8)
+    return launch_attention_f16f8(c, op_attention_f8(ws.q, n), op_attention_f8(ws.k, n), op_attention_f8(ws.v, n),
+                                  F8Planes{(bf16_t*)o_hi, (uint8_t*)o_hi8, (uint8_t*)o_lo8}, o_f32, lse2, B, H, S, s, (char*)o_ilv);
+  bf16_t* const olo = prec_products(terms) == 3 ? (bf16_t*)o_lo : nullptr;     // one plane with a single product, as the encoder's buffers have then
+  return launch_attention(c, ws.q.hi, ws.q.lo, ws.k.hi, ws.k.lo, ws.v.hi, ws.v.lo, (bf16_t*)o_hi, olo, o_f32, lse2, B, H, S, terms, s);
 }
 
 // What one encoder layer's training pass runs around its attention, on caller tensors: the operand planes, the training form of the forward

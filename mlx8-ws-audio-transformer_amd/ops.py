@@ -104,6 +104,31 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, precision: str 
     return o
 
 
+def attention_ex_workspace_bytes(B: int, H: int, S: int) -> int:
+    """Workspace of `attention_ex`; answers without a GPU."""
+    return int(_lib.lib().awt_op_attention_ex_workspace_bytes(int(B), int(H), int(S)))
+
+
+def attention_ex(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, precision, out: dict, workspace: Optional[torch.Tensor] = None,
+                 ws_bytes: Optional[int] = None) -> None:
+    """One attention forward launch with any of its output forms (include/awt.h: awt_op_attention_ex); the kernel's raw bytes land in the caller's tensors
+    `out`, a dict over "f32", "hi", "lo", "hi8", "lo8", "ilv", "lse2" (any dtype; nothing is converted).  q (pre-scaled), k, v: [B, H, S, 64] fp32;
+    precision: a name or the operator's `terms`.  Raises _lib.AwtError where the library refuses the call."""
+    terms = precision if isinstance(precision, int) else _terms(precision)
+    q, k, v = (t.float().contiguous() for t in (q, k, v))
+    B, H, S, hd = q.shape
+    if hd != 64 or k.shape != q.shape or v.shape != q.shape:
+        raise ValueError("attention_ex: q, k, v must share the shape [B, H, S, 64]")
+    unknown = set(out) - {"f32", "hi", "lo", "hi8", "lo8", "ilv", "lse2"}
+    if unknown:
+        raise KeyError(f"attention_ex: no output named {sorted(unknown)}")
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_op_attention_ex_workspace_bytes(B, H, S), q.device) if workspace is None else workspace
+    with torch.cuda.device(q.device):
+        _lib.check(L.awt_op_attention_ex(_lib.ctx(q.device), _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), *(_lib.ptr(out.get(key)) for key in ("f32", "hi", "lo", "hi8", "lo8", "ilv", "lse2")),
+                                         B, H, S, terms, _lib.ptr(ws), ws.numel() if ws_bytes is None else int(ws_bytes), _lib.stream_handle()))
+
+
 def attention_backward_planes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, d_o: torch.Tensor, precision: str = "bf16x3",
                               grad_precision: Optional[str] = None, qscale: float = 1.0, out: Optional[tuple] = None) -> tuple:
     """The attention of an encoder layer's training pass (include/awt.h: awt_op_attention_backward) with its outputs as the library writes them:

@@ -3,13 +3,16 @@ on whatever device the inputs live on.
 
     exact(q, k, v, d_o)                       float64 autograd of softmax(q k^T) v
     rounded(q, k, v, d_o, terms, grad_terms)  the same formulas in float64 with the roundings the kernels make, and nothing else
+    rounded(q, k, v, None, terms)             its forward half alone, as awt_op_attention stores it (o in fp32, lse2); also terms 2 and 4
     check(...)                                the bound of the operator tests: the kernel may be 4 x as far from `exact` as `rounded` is
 
 q (pre-scaled by head_dim^-1/2), k, v: [B, H, S, 64]; d_o: [B, S, H * 64].  Both return an `Outputs` of float64 tensors: o [B, S, H * 64], lse2 (the
 log-sum-exp of each score row in log2 units) and delta = rowsum(d_o * o) [B, H, S], dq (times qscale), dk, dv [B, H, S, 64].
 
 The roundings restated by `rounded`, read off the two kernels (terms = 3 is split-bf16: every operand a hi + lo pair of bf16 values, hi = rne(x),
-lo = rne(x - hi), and a product of two operands is a_hi b_hi + a_hi b_lo + a_lo b_hi -- the lo x lo term is never formed; terms = 1 keeps hi only):
+lo = rne(x - hi), and a product of two operands is a_hi b_hi + a_hi b_lo + a_lo b_hi -- the lo x lo term is never formed; terms = 1 keeps hi only;
+terms = 4 / 2 are the same on fp16 planes, forward only -- common.h split16<true>: hi = fp16(x), lo = fp16(x - hi), no power-of-two scale on lo, so a
+lo below 2^-24 is lost and one below 2^-14 keeps fewer than 11 bits):
   * q log2(e) (an fp32 product), k, v and d_o are split;
   * scores: the fp32 accumulator is rounded after each MFMA, i.e. after each 16-wide step of each of the three products (at logits of order 100 one
     fp32 ulp of the exponent is 1e-5 of a probability, the size of the split-bf16 error itself);
@@ -41,15 +44,23 @@ def _bf16(x):
     return x.float().bfloat16().double()          # round-to-nearest-even, as v_cvt_pk_bf16_f32
 
 
+def _fp16(x):
+    return x.float().half().double()               # round-to-nearest-even, as v_cvt_f16_f32; subnormals kept
+
+
+PRODUCTS = {1: 1, 2: 1, 3: 3, 4: 3}                # common.h prec_products: terms 1 / 3 on bf16 planes, 2 / 4 on fp16 planes
+
+
 def _split(x, terms):
     x = _f32(x)
-    hi = _bf16(x)
-    return hi, (_bf16(x - hi) if terms == 3 else torch.zeros_like(hi))
+    rne = _bf16 if terms in (1, 3) else _fp16
+    hi = rne(x)
+    return hi, (rne(x - hi) if PRODUCTS[terms] == 3 else torch.zeros_like(hi))
 
 
 def _prod(ah, al, bh, bl, terms):
     """a b for split operands: the hi x lo and lo x hi products join hi x hi only with three terms."""
-    return ah @ bh + (ah @ bl + al @ bh if terms == 3 else 0.0)
+    return ah @ bh + (ah @ bl + al @ bh if PRODUCTS[terms] == 3 else 0.0)
 
 
 def _heads(x, H):
@@ -79,17 +90,17 @@ def rounded(q, k, v, d_o, terms=3, grad_terms=None, qscale=1.0, drop=()):
     """`drop` names lo planes to lose on purpose, for the test that the bound tells such a loss apart: "ds_lo" (the lo plane of dS in the products
     that form dq and dk), "p_lo" (the lo plane of P in the product that forms dv)."""
     gt = terms if grad_terms is None else grad_terms
-    assert terms in (1, 3) and (gt == terms or (terms == 3 and gt == 1)) and not set(drop) - {"ds_lo", "p_lo"}
+    assert terms in PRODUCTS and (gt == terms or (terms == 3 and gt == 1)) and not set(drop) - {"ds_lo", "p_lo"}
+    assert d_o is None or terms in (1, 3)                                # the backward kernels have no fp16 form
     B, H, S, _ = q.shape
     qh, ql = _split(q.float() * torch.tensor(LOG2E, dtype=torch.float32), terms)
     kh, kl = _split(k, terms)
     vh, vl = _split(v, terms)
-    doh, dol = _split(_heads(d_o, H), terms)
 
     s = torch.zeros((B, H, S, S), dtype=torch.float64, device=q.device)
     for c in range(0, 64, 16):
         a_h, a_l, b_h, b_l = qh[..., c:c + 16], ql[..., c:c + 16], kh[..., c:c + 16].transpose(2, 3), kl[..., c:c + 16].transpose(2, 3)
-        if terms == 3:
+        if PRODUCTS[terms] == 3:
             s = _f32(s + a_l @ b_h)
             s = _f32(s + a_h @ b_l)
         s = _f32(s + a_h @ b_h)
@@ -107,8 +118,11 @@ def rounded(q, k, v, d_o, terms=3, grad_terms=None, qscale=1.0, drop=()):
         ph, pl = _split(p, terms)
         acc = acc * alpha[..., None] + _prod(ph, pl, vh[..., t0:t0 + KEY_TILE, :], vl[..., t0:t0 + KEY_TILE, :], terms)
         m = m_new
-    oh, ol = _split(acc / l[..., None], terms)
     lse2 = _f32(m + torch.log2(l))
+    if d_o is None:                                                      # the fp32 store of awt_op_attention: no output planes
+        return Outputs(_rows(_f32(acc / l[..., None])), lse2, None, None, None, None)
+    oh, ol = _split(acc / l[..., None], terms)
+    doh, dol = _split(_heads(d_o, H), terms)
 
     # ---- backward
     delta = _f32(((doh + dol) * (oh + ol)).sum(-1))

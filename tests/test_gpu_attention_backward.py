@@ -14,7 +14,7 @@ import torch
 
 from tests import attention_reference as ar
 from tests.test_gpu_ops import ATT_TOL, _rand
-from tests.util import tuning
+from tests.util import GUARD, guarded as _guarded, tuning
 
 pytestmark = pytest.mark.gpu
 
@@ -137,19 +137,6 @@ def test_peaked_rows_recompute_the_forward_probabilities():
     print("peaked: |sum P - 1|", abs(row_sum - 1.0), "max |P v - o|", (pv - goth.o[0, 5]).abs().max().item(), "tol", tol, "x max|v|", v.abs().max().item())
     assert abs(row_sum - 1.0) < tol
     assert (pv - goth.o[0, 5]).abs().max().item() < tol * v.abs().max().item()
-
-
-GUARD = 4096
-
-
-def _guarded(shape, dtype):
-    """A tensor of NaN bit patterns between two 4 KiB guards of 0xA5 bytes."""
-    n = torch.empty(shape, dtype=dtype).numel() * torch.empty((), dtype=dtype).element_size()
-    buf = torch.full((GUARD + n + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    buf[GUARD:GUARD + n] = 0xFF
-    inner = buf[GUARD:GUARD + n].view(dtype).view(shape)
-    assert inner.data_ptr() % 256 == 0 and bool(torch.isnan(inner).all())
-    return buf, inner
 
 
 @pytest.mark.parametrize("precision", ["bf16x3", "bf16"])

@@ -84,6 +84,33 @@ def test_op_attention(precision):
     _exact(L.awt_op_attention_workspace_bytes(B, H, S), call, [torch.empty(B, S, H * 64, device="cuda")], [ops.attention(q, k, v, precision)])
 
 
+@pytest.mark.parametrize("precision,form", [("bf16x3", "planes"), ("fp16x3", "f32"), ("f16f8", "planes"), ("f16f8", "ilv")])
+def test_op_attention_ex(precision, form):
+    """f16f8 with lse2: the form that reads v's e4m3 images, every byte of the six planes in use; "ilv" without: v's images stay unwritten."""
+    from mlx8_ws_audio_transformer_amd import ops
+    B, H, S = 1, 1, 129                                      # as test_op_attention
+    q, k, v = _rand((B, H, S, 64), 1, 0.125), _rand((B, H, S, 64), 2), _rand((B, H, S, 64), 3)
+    if form == "f32":
+        names, specs = ["f32", "lse2"], [((B, S, H * 64), torch.float32), ((B, H, S), torch.float32)]
+    elif form == "ilv":
+        names, specs = ["ilv"], [((B * S, H * 256), torch.uint8)]
+    elif precision == "f16f8":
+        names, specs = ["hi", "hi8", "lo8", "lse2"], [((B * S, H * 64), torch.float16), ((B * S, H * 64), torch.uint8), ((B * S, H * 64), torch.uint8), ((B, H, S), torch.float32)]
+    else:
+        names, specs = ["hi", "lo", "lse2"], [((B * S, H * 64), torch.bfloat16)] * 2 + [((B, H, S), torch.float32)]
+    new = lambda: [torch.empty(shape, dtype=dt, device="cuda") for shape, dt in specs]
+    want = new()
+    ops.attention_ex(q, k, v, precision, dict(zip(names, want)))
+
+    def call(ws, n, *outs):
+        try:
+            ops.attention_ex(q, k, v, precision, dict(zip(names, outs)), workspace=ws, ws_bytes=n)
+        except _lib.AwtError as e:
+            return e.code
+        return 0
+    _exact(ops.attention_ex_workspace_bytes(B, H, S), call, new(), want)
+
+
 def test_op_attention_backward():
     from mlx8_ws_audio_transformer_amd import ops
     B, H, S = 1, 1, 129                                      # as test_op_attention: eight planes of 16512 bytes

@@ -31,6 +31,8 @@ def test_version_and_workspace_queries_need_no_gpu(built):
     assert built.awt_logmel_workspace_bytes(64) >= 256
     assert built.awt_op_linear_workspace_bytes(128, 128, 64) > 0
     assert built.awt_op_linear_fused_workspace_bytes(128, 64, 128, 64) == built.awt_op_linear_workspace_bytes(128, 128, 64)
+    assert built.awt_op_attention_ex_workspace_bytes(2, 3, 129) == built.awt_op_attention_workspace_bytes(2, 3, 129) > 0
+    assert "awt_op_attention_ex" in _lib.declared_symbols() and "awt_op_attention_ex_workspace_bytes" in _lib.declared_symbols()
 
 
 def test_no_cpu_fallback():

@@ -45,6 +45,17 @@ EXPECTED = {
         ((2, 6, 51), 470016),
         ((0, 6, 51), 0),
     ],
+    # awt_op_attention's six planes, whichever outputs are asked for (its own table repeated; the single-key shape added by hand: six planes of 128 bytes)
+    "awt_op_attention_ex_workspace_bytes": [
+        ((64, 12, 1500), 884736000),
+        ((1, 1, 3), 3072),
+        ((1, 3, 5), 12288),
+        ((2, 6, 51), 470016),
+        ((1, 1, 1), 1536),                # plane 128 bytes
+        ((0, 6, 51), 0),
+        ((2, 0, 51), 0),
+        ((2, 6, 0), 0),
+    ],
     # eight planes of B H S 64 2 bytes: q, k, v and dO (recorded from the commit that added the entry point: nothing precedes it)
     "awt_op_attention_backward_workspace_bytes": [
         ((64, 12, 1500), 1179648000),

@@ -30,6 +30,25 @@ def tuning(**knobs):
             _lib.tuning_set(key, value)
 
 
+GUARD = 4096
+
+
+def guarded(shape, dtype, device="cuda"):
+    """(buffer, tensor): a tensor of 0xFF bytes (NaN in every floating-point format) between two 4 KiB guards of 0xA5 bytes."""
+    import torch
+
+    n = torch.empty(shape, dtype=dtype).numel() * torch.empty((), dtype=dtype).element_size()
+    buf = torch.full((GUARD + n + GUARD,), 0xA5, dtype=torch.uint8, device=device)
+    buf[GUARD:GUARD + n] = 0xFF
+    inner = buf[GUARD:GUARD + n].view(dtype).view(shape)
+    assert inner.data_ptr() % 256 == 0 and (not inner.is_floating_point() or bool(torch.isnan(inner).all()))
+    return buf, inner
+
+
+def guards_intact(buf):
+    return bool((buf[:GUARD] == 0xA5).all()) and bool((buf[-GUARD:] == 0xA5).all())
+
+
 def golden(name):
     return np.load(os.path.join(GOLD, name))
 
