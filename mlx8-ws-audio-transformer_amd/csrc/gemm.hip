@@ -217,6 +217,43 @@ __device__ __forceinline__ void store_out4(const GemmOut& o, int m, int n, float
   }
 }
 
+// The fp32 epilogues on eight consecutive columns of a row the caller has addressed (RowOff8 below): (acc + bias) + residual, two 16-byte stores -- the
+// arithmetic of store_out8_f8's fp32 branch, which stays spelt out there (routed through this function, gemm_f8_kernel's EPI_F32_GELU_POS form spilled).
+template <int EPI>
+__device__ __forceinline__ void store_out8_f32(float* dst, float4 acc0, float4 acc1, float4 side0, float4 side1, float4 b0, float4 b1) {
+  static_assert(EPI == EPI_F32 || EPI == EPI_F32_RESID, "an fp32 epilogue on row-major rows");
+  float v[8] = {acc0.x, acc0.y, acc0.z, acc0.w, acc1.x, acc1.y, acc1.z, acc1.w};
+  const float sd[8] = {side0.x, side0.y, side0.z, side0.w, side1.x, side1.y, side1.z, side1.w};
+  v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w; v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
+#pragma unroll
+  for (int t = 0; t < 8; ++t) v[t] = EPI == EPI_F32_RESID ? v[t] + sd[t] : v[t];
+  *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+  *reinterpret_cast<float4*>(dst + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
+
+// The lane index (threadIdx.x & 63 of these one-dimensional blocks), computed WHERE IT IS CALLED: two VALU instructions that the compiler can neither hoist
+// nor merge with the kernel's own `lane`.  An epilogue that derives its patch addresses, row indices and offsets from `lane` has them computed ahead of the
+// K loop (they are loop invariants of a persistent kernel), where they do not fit beside accumulators and fragments; they came back as scratch reloads in
+// the epilogue, each with an s_waitcnt vmcnt(0).  Derived from lane_here() they exist only while the epilogue runs.
+__device__ __forceinline__ int lane_here() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+
+// Row addressing of the fp32 epilogues' strips (EPI_F32, EPI_F32_RESID: output and residual share the pitch ldo).  A lane's eight columns of row
+// `row0 + (lane >> 3)` are  base + (row0 * ldo + col0) [wave-uniform: scalar registers]  +  off [ONE 32-bit per-lane byte offset, the same for every
+// row group of the tile and for both matrices], so a strip's addresses cost no vector registers beyond `off`.  Formed per row as 64-bit m * ldo + n
+// they took two registers per row and matrix, and in the ping-pong kernel the strips' loads and stores spilled around them.
+struct RowOff8 {
+  unsigned off;         // ((lane >> 3) * ldo + (lane & 7) * 8) * 4
+  int64_t ldo;
+  __device__ __forceinline__ RowOff8(int r8, int c8, int64_t ldo_) : off((unsigned)(r8 * (int)ldo_ + c8) * 4u), ldo(ldo_) {}
+  template <class T> __device__ __forceinline__ T* at(T* base, int row0, int col0) const {     // row0, col0 wave-uniform
+    return reinterpret_cast<T*>((char*)(base + ((int64_t)row0 * ldo + col0)) + off);
+  }
+};
+
 // Eight consecutive columns of one row in the f16f8 output format: 16-byte fp16 and 8-byte e4m3 stores (the 4-column form
 // writes 4-byte pieces of the e4m3 planes: twice the store instructions for the same bytes).  n is a multiple of 8, so the
 // eight columns never straddle a head or a q / k / v boundary of EPI_QKV.
@@ -1040,19 +1077,33 @@ __global__ __launch_bounds__(256, 2) void gemm_f8s_kernel(GemmArgs g) {
   // strip i = row tiles 2 i, 2 i + 1; tile (rt, ct) register reg sits at patch row rt 16 + 4 kq + reg, column ct 16 + r16
   constexpr int PITCH = 72;
   float* patch = reinterpret_cast<float*>(smem) + wave * (32 * PITCH);
-  const int c8 = (lane & 7) * 8, r8 = lane >> 3;
-  const int em0 = m0, en = n0 + wc * 64 + c8;
+  // (the lane's coordinates from lane_here(): formed from `lane` the epilogue's offsets were computed ahead of the K loop and spilled there in the
+  // EPI_F32_RESID kernel -- 16 bytes of scratch, reloaded here)
+  const int ln = lane_here();
+  const int c8 = (ln & 7) * 8, r8 = ln >> 3, er16 = ln & 15, ekq = ln >> 4;
+  const int em0 = m0, en0 = n0 + wc * 64, en = en0 + c8;
   float4 b0 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = b0;
   if (g.out.bias && en < g.out.n_valid) { b0 = *reinterpret_cast<const float4*>(g.out.bias + en); b1 = *reinterpret_cast<const float4*>(g.out.bias + en + 4); }
   constexpr bool SIDE = EPI == EPI_F32_RESID || EPI == EPI_F32_GELU_POS || EPI == EPI_BF16_DGELU;
+  constexpr bool ROWS = EPI == EPI_F32 || EPI == EPI_F32_RESID;      // fp32 output (and residual) rows addressed by RowOff8: no address registers per row
+  const RowOff8 rows(r8, c8, g.out.ldo);
   auto strips = [&](auto full_t) {
     constexpr bool FULL = decltype(full_t)::value;
     float4 side[4][2], side_next[4][2];
+    auto inside = [&](int i, int it) { return FULL || (em0 + i * 32 + 8 * it + r8 < g.M && en < g.out.n_valid); };
     auto load_sides = [&](float4 (&d)[4][2], int i) {
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
-        d[it][0] = load_side4<EPI, FULL>(g.out, em0 + i * 32 + r8 + 8 * it, en, g.M);
-        d[it][1] = load_side4<EPI, FULL>(g.out, em0 + i * 32 + r8 + 8 * it, en + 4, g.M);
+        if constexpr (ROWS) {
+          d[it][0] = d[it][1] = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (inside(i, it)) {
+            const float4* p = reinterpret_cast<const float4*>(rows.at(g.out.resid, em0 + i * 32 + 8 * it, en0));
+            d[it][0] = p[0]; d[it][1] = p[1];
+          }
+        } else {
+          d[it][0] = load_side4<EPI, FULL>(g.out, em0 + i * 32 + r8 + 8 * it, en, g.M);
+          d[it][1] = load_side4<EPI, FULL>(g.out, em0 + i * 32 + r8 + 8 * it, en + 4, g.M);
+        }
       }
     };
     if constexpr (SIDE) load_sides(side, 0);
@@ -1063,7 +1114,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f8s_kernel(GemmArgs g) {
 #pragma unroll
         for (int ct = 0; ct < TN; ++ct)
 #pragma unroll
-          for (int reg = 0; reg < 4; ++reg) patch[(rt * 16 + 4 * kq + reg) * PITCH + ct * 16 + r16] = acc[2 * i + rt][ct][reg];
+          for (int reg = 0; reg < 4; ++reg) patch[(rt * 16 + 4 * ekq + reg) * PITCH + ct * 16 + er16] = acc[2 * i + rt][ct][reg];
       __builtin_amdgcn_wave_barrier();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if constexpr (SIDE) { if (i + 1 < TM / 2) load_sides(side_next, i + 1); }
@@ -1071,7 +1122,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f8s_kernel(GemmArgs g) {
       for (int it = 0; it < 4; ++it) {
         const int rl = r8 + 8 * it;
         const float4 v0 = *reinterpret_cast<const float4*>(patch + rl * PITCH + c8), v1 = *reinterpret_cast<const float4*>(patch + rl * PITCH + c8 + 4);
-        store_out8_f8<EPI, FULL>(g.out, em0 + i * 32 + rl, en, v0, v1, side[it][0], side[it][1], b0, b1, g.M);
+        if constexpr (ROWS) {
+          if (inside(i, it)) store_out8_f32<EPI>(rows.at(g.out.f32, em0 + i * 32 + 8 * it, en0), v0, v1, side[it][0], side[it][1], b0, b1);
+        } else {
+          store_out8_f8<EPI, FULL>(g.out, em0 + i * 32 + rl, en, v0, v1, side[it][0], side[it][1], b0, b1, g.M);
+        }
       }
       if constexpr (SIDE) {
 #pragma unroll
@@ -1118,52 +1173,80 @@ int launch_f8(GemmArgs a, hipStream_t s) {
 template <int EPI, bool ILV>
 __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(pp::Args g, GemmOut out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wr = wave >> 2, wc = wave & 3, r16 = lane & 15, kq = lane >> 4;
+  const int wr = wave >> 2, wc = wave & 3;
   float* patch = reinterpret_cast<float*>(smem + pp::PATCH_BASE + wave * 8192);
-  const int c8 = (lane & 7) * 8, r8 = lane >> 3;
   constexpr bool SIDE = EPI == EPI_F32_RESID;
+  constexpr bool ROWS = EPI == EPI_F32 || EPI == EPI_F32_RESID;      // fp32 output: rows addressed by RowOff8
   pp::kloop(g, smem, [&](int tm, int tn, pp::Acc& accs) {
     auto& acc = accs.t;
+    // Everything the epilogue derives from the lane index is derived HERE, once per tile, from lane_here(): as loop invariants of the persistent loop
+    // the patch addresses and row indices (some thirty registers) were formed before the first K loop, did not fit beside its accumulators and
+    // fragments, and came back as scratch reloads -- vector-memory operations, each with an s_waitcnt vmcnt(0) that also waited for the residual rows,
+    // the stores issued so far and the next tile's LDS-DMA.
+    const int ln = lane_here();
+    const int r16 = ln & 15, kq = ln >> 4, c8 = (ln & 7) * 8, r8 = ln >> 3;
     const int m0 = tm * pp::BM, n0 = tn * pp::BN;
-    const int em0 = m0 + wr * 128, en = n0 + wc * 64 + c8;
-    float4 b0 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = b0;
-    if (out.bias && en < out.n_valid) { b0 = *reinterpret_cast<const float4*>(out.bias + en); b1 = *reinterpret_cast<const float4*>(out.bias + en + 4); }
+    const int em0 = m0 + wr * 128, en0 = n0 + wc * 64, en = en0 + c8;
+    // Patch (32 rows x 64 floats).  Position of (row, col): the column rotated by 16 ((row >> 2) & 3) -- the four lane groups of one write then cover all
+    // 64 banks -- and XORed with 4 (row & 1) for the 16-byte reads.  Tile (rt, ct) register reg is row rt 16 + 4 kq + reg, column ct 16 + r16.
+    auto pw = [&](int rt, int ct, int reg, float v) {
+      const int row = rt * 16 + 4 * kq + reg;
+      patch[row * 64 + (((ct * 16 + r16 + 16 * kq) & 63) ^ ((reg & 1) << 2))] = v;
+    };
+    auto pr = [&](int it, int h) {
+      const int rl = r8 + 8 * it, sw = (rl & 1) << 2, rot = 16 * ((rl >> 2) & 3);
+      return *reinterpret_cast<const float4*>(patch + rl * 64 + (((c8 + 4 * h + rot) & 63) ^ sw));
+    };
+    const RowOff8 rows(r8, c8, out.ldo);
     auto strips = [&](auto full_t) {
       constexpr bool FULL = decltype(full_t)::value;
+      // Every load of the epilogue is issued AND consumed inside one of the two paths (the bias here, not ahead of the branch; a ragged tile's residual rows
+      // where they are stored).  A load that some path -- even one that is never taken, such as "neither full nor ragged" in the emitted control flow --
+      // leaves unconsumed is still pending, for the compiler, at the head of the next K loop, and it then puts s_waitcnt vmcnt(0) in front of the first
+      // fragment read that reuses the register: a drain of the LDS-DMA stream in every K-tile pair.
+      float4 b0 = make_float4(0.f, 0.f, 0.f, 0.f), b1 = b0;
+      if (out.bias && en < out.n_valid) { b0 = *reinterpret_cast<const float4*>(out.bias + en); b1 = *reinterpret_cast<const float4*>(out.bias + en + 4); }
       float4 side[4][2], side_next[4][2];
+      auto inside = [&](int i, int it) { return FULL || (em0 + i * 32 + 8 * it + r8 < g.M && en < out.n_valid); };
+      auto load_side = [&](float4 (&d)[2], int i, int it) {
+        const float4* p = reinterpret_cast<const float4*>(rows.at(out.resid, em0 + i * 32 + 8 * it, en0));
+        d[0] = p[0]; d[1] = p[1];
+      };
       auto load_sides = [&](float4 (&d)[4][2], int i) {
 #pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          d[it][0] = load_side4<EPI, FULL>(out, em0 + i * 32 + r8 + 8 * it, en, g.M);
-          d[it][1] = load_side4<EPI, FULL>(out, em0 + i * 32 + r8 + 8 * it, en + 4, g.M);
-        }
+        for (int it = 0; it < 4; ++it) load_side(d[it], i, it);
       };
-      if constexpr (SIDE) load_sides(side, 0);
+      // (a ragged tile may store nothing: it uses the bias registers here, so that no path leaves their load unconsumed)
+      if constexpr (!FULL) asm volatile("" ::"v"(b0.x), "v"(b0.y), "v"(b0.z), "v"(b0.w), "v"(b1.x), "v"(b1.y), "v"(b1.z), "v"(b1.w));
+      if constexpr (SIDE && FULL) load_sides(side, 0);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        // strip i = the 16-row tiles 2 i, 2 i + 1 (C layout: column lane & 15, row 4 (lane >> 4) + reg).  Patch position of (row, col): the column rotated by
-        // 16 ((row >> 2) & 3) -- the four lane groups of one write then cover all 64 banks -- and XORed with 4 (row & 1) for the 16-byte reads below
+        // strip i = the 16-row tiles 2 i, 2 i + 1 (C layout: column lane & 15, row 4 (lane >> 4) + reg)
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
           for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-              const int row = rt * 16 + 4 * kq + reg;
-              patch[row * 64 + (((ct * 16 + r16 + 16 * kq) & 63) ^ ((reg & 1) << 2))] = acc[2 * i + rt][ct][reg];
-            }
+            for (int reg = 0; reg < 4; ++reg) pw(rt, ct, reg, acc[2 * i + rt][ct][reg]);
         __builtin_amdgcn_wave_barrier();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (SIDE) { if (i + 1 < 4) load_sides(side_next, i + 1); }
+        // the residual rows of the NEXT strip are requested before this strip's stores (vmcnt retires in issue order: behind the stores they would wait
+        // for the stores' acknowledgement); every wait for them is the compiler's own count of the operations issued since
+        if constexpr (SIDE && FULL) { if (i + 1 < 4) load_sides(side_next, i + 1); }
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-          const int rl = r8 + 8 * it, sw = (rl & 1) << 2, rot = 16 * ((rl >> 2) & 3);
-          const float4 v0 = *reinterpret_cast<const float4*>(patch + rl * 64 + (((c8 + rot) & 63) ^ sw)), v1 = *reinterpret_cast<const float4*>(patch + rl * 64 + (((c8 + 4 + rot) & 63) ^ sw));
-          store_out8_f8<EPI, FULL, ILV>(out, em0 + i * 32 + rl, en, v0, v1, side[it][0], side[it][1], b0, b1, g.M);
+          const float4 v0 = pr(it, 0), v1 = pr(it, 1);
+          if constexpr (ROWS) {
+            if (inside(i, it)) {
+              if constexpr (SIDE && !FULL) load_side(side[it], i, it);
+              store_out8_f32<EPI>(rows.at(out.f32, em0 + i * 32 + 8 * it, en0), v0, v1, side[it][0], side[it][1], b0, b1);
+            }
+          } else {
+            store_out8_f8<EPI, FULL, ILV>(out, em0 + i * 32 + r8 + 8 * it, en, v0, v1, side[it][0], side[it][1], b0, b1, g.M);
+          }
         }
-        if constexpr (SIDE) {
+        if constexpr (SIDE && FULL) {
 #pragma unroll
           for (int it = 0; it < 4; ++it) { side[it][0] = side_next[it][0]; side[it][1] = side_next[it][1]; }
         }

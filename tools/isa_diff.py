@@ -11,6 +11,17 @@ Kernels are matched by demangled name with `(anonymous namespace)::` left out; t
   * the metadata rows vgpr_count, agpr_count, sgpr_count, vgpr_spill_count, sgpr_spill_count, private_segment_fixed_size, group_segment_fixed_size.
 One line per kernel: `identical`, or `DIFFERS` with both metadata rows and both instruction counts; `WORSE` where the second file has more spilled
 registers, scratch bytes, LDS or VGPRs + AGPRs.  Exit status 1 if the kernel sets differ or any kernel is WORSE.
+
+    python tools/isa_diff.py before.s after.s --table 'gemm_pp_kernel|gemm_f8s_kernel'
+
+prints, for every kernel whose demangled name matches the regex, one row per file: VGPRs, AGPRs, scratch bytes, occupancy (the `; Occupancy:` comment
+behind the kernel), instruction count, and where its `s_waitcnt vmcnt(0)` and scratch (spill) instructions sit relative to the matrix work:
+  k-loop     between the kernel's first and last MFMA
+  ahead      between the last MFMA and the full-tile epilogue
+  full-tile  inside the full-tile epilogue: the branch-free stretch behind the last MFMA that holds the most global stores (the ragged path predicates
+             every row group, so its stores are separated by branches)
+  rest       everything behind it (the ragged path, the kernel's end)
+Same exit status as the comparison: 1 if a matched kernel of the second file has more scratch, lower occupancy or more k-loop instructions.
 """
 from __future__ import annotations
 
@@ -78,8 +89,55 @@ def parse(path: str) -> dict[str, dict]:
             ln = ln.replace(name, "<kernel>")
             ln = LOCAL.sub(lambda t: labels.setdefault(t.group(0), f".L{len(labels)}"), ln)
             code.append(re.sub(r"\s+", " ", ln.strip()))
-        kernels[name] = {"meta": meta[name], "code": code}
+        occ = -1
+        for j in range(i, min(i + 400, len(lines))):                            # the resource comments behind the kernel
+            mo = re.match(r"^; Occupancy: (\d+)", lines[j])
+            if mo:
+                occ = int(mo.group(1))
+                break
+        kernels[name] = {"meta": meta[name], "code": code, "occupancy": occ}
     return kernels
+
+
+def table_row(k: dict) -> dict:
+    """Resource and wait columns of one kernel for --table (see the module docstring)."""
+    code = [ln for ln in k["code"] if not ln.startswith(".") or ln.endswith(":")]
+    is_inst = lambda ln: not ln.endswith(":")
+    mf = [i for i, ln in enumerate(code) if ln.startswith("v_mfma") or ln.startswith("v_smfma")]
+    first, last = (mf[0], mf[-1]) if mf else (0, 0)
+    # branch-free stretches behind the last MFMA
+    blocks, start = [], last + 1
+    for i in range(last + 1, len(code) + 1):
+        if i == len(code) or code[i].endswith(":") or code[i].startswith(("s_cbranch", "s_branch", "s_endpgm")):
+            blocks.append((start, i))
+            start = i + 1
+    stores = lambda b: sum(1 for ln in code[b[0]:b[1]] if ln.startswith(("global_store", "buffer_store", "flat_store")))
+    full = max(blocks, key=stores) if blocks else (len(code), len(code))
+    spans = {"k-loop": (first, last), "ahead": (last + 1, full[0]), "full-tile": full, "rest": (full[1], len(code))}
+    drain = lambda ln: ln.startswith("s_waitcnt") and "vmcnt(0)" in ln
+    spill = lambda ln: ln.startswith("scratch_")
+    out = {"vgpr": k["meta"].get("vgpr_count", -1), "agpr": k["meta"].get("agpr_count", -1), "scratch": k["meta"].get("private_segment_fixed_size", -1),
+           "occupancy": k.get("occupancy", -1), "instructions": sum(1 for ln in code if is_inst(ln)), "k-loop instructions": sum(1 for ln in code[first:last + 1] if is_inst(ln)),
+           "full-tile stores": stores(full)}
+    for name, (a, b) in spans.items():
+        out[f"vmcnt(0) {name}"] = sum(1 for ln in code[a:b] if drain(ln))
+        out[f"spill ops {name}"] = sum(1 for ln in code[a:b] if spill(ln))
+    return out
+
+
+def table(paths: list[str], sides: list[dict], pattern: str) -> int:
+    rx, bad = re.compile(pattern), 0
+    cols = ["vgpr", "agpr", "scratch", "occupancy", "instructions", "k-loop instructions", "full-tile stores"] + [f"{w} {s}" for s in ("k-loop", "ahead", "full-tile", "rest") for w in ("vmcnt(0)", "spill ops")]
+    print("# columns: " + " | ".join(cols))
+    for name in sorted(n for n in set(sides[0]) | set(sides[1]) if rx.search(n)):
+        rows = [table_row(sd[name]) if name in sd else None for sd in sides]
+        print(name)
+        for path, r in zip(paths, rows):
+            print(f"  {path}: " + ("(absent)" if r is None else " | ".join(str(r[c]) for c in cols)))
+        if rows[0] and rows[1] and (rows[1]["scratch"] > rows[0]["scratch"] or rows[1]["occupancy"] < rows[0]["occupancy"] or rows[1]["k-loop instructions"] > rows[0]["k-loop instructions"]):
+            print("  WORSE")
+            bad += 1
+    return 1 if bad else 0
 
 
 def row(k: dict) -> str:
@@ -99,6 +157,7 @@ def main() -> int:
     ap.add_argument("before")
     ap.add_argument("after")
     ap.add_argument("--rename", action="append", default=[], metavar="REGEX=REPLACEMENT", help="rewrite demangled kernel names of the first file")
+    ap.add_argument("--table", metavar="REGEX", default=None, help="resource / wait table of the kernels whose demangled name matches, instead of the comparison")
     args = ap.parse_args()
     sides = []
     for path, renames in ((args.before, args.rename), (args.after, [])):
@@ -108,6 +167,8 @@ def main() -> int:
             pat, _, repl = r.partition("=")
             names = [re.sub(pat, repl, n) for n in names]
         sides.append(dict(zip(names, k.values())))
+    if args.table:
+        return table([args.before, args.after], sides, args.table)
     a, b = sides
     n_same = n_diff = n_worse = 0
     for name in sorted(set(a) & set(b)):
