@@ -509,6 +509,45 @@ int awt_op_causal_attention(awt_ctx* c, const float* q, int ldq, const float* k,
  * I: a positive multiple of 4; 16-byte accesses.                                                                   HF:modeling_qwen3.py Qwen3MLP */
 int awt_op_silu_mul(awt_ctx* c, const float* gu, int64_t ld, float* y, int64_t ldy, int M, int I, void* stream);
 
+/* The backward of those operators (training through music2midi.Qwen3Decoder).  fp32 in and out on the caller's stream, no
+ * synchronisation, no atomics (two runs give the same bits); each refuses with AWT_ERR_INVALID what its forward counterpart refuses.
+ *
+ * awt_op_causal_attention with the log-sum-exp lse [B, Hq, Lq] (natural log) written out: the same kernel instantiation, what the backward reads. */
+int awt_op_causal_attention_lse(awt_ctx* c, const float* q, int ldq, const float* k, const float* v, int ldkv, int64_t kv_batch_stride, float* o, int ldo,
+                                float* lse, int B, int Hq, int Hkv, int Lq, int T, int terms, void* workspace, size_t ws_bytes, void* stream);
+/* dq (layout of q: ldq, Hq heads), dk / dv (the cache's layout with their own pitch lddkv and batch stride dkv_batch_stride: row (b, j) at
+ * dk + b dkv_batch_stride + j lddkv + 128 g) of that attention under the gradient dout of o (o and dout pitched ldo).  The forward's contract, 1 <= Lq <= T.
+ * Every element of dq (B x Lq x Hq x 128) and of dk / dv (B x T x Hkv x 128) is written; nothing at or past row T of k / v is read.  Three launches:
+ * delta = rowsum(dout * o); dq, a workgroup of 128 queries streaming key tiles up to its last query's diagonal; dk / dv, one workgroup per (batch, KV head,
+ * 64-key block) that walks the group's Hq / Hkv query heads and, per head, the 32-query tiles from the first one that sees the block, with dk and dv kept in
+ * registers across the heads (the group sum in a fixed order).  P is recomputed from lse.  The workspace query answers without a GPU. */
+size_t awt_op_causal_attention_backward_workspace_bytes(int B, int Hq, int Lq, int T);
+int awt_op_causal_attention_backward(awt_ctx* c, const float* q, int ldq, const float* k, const float* v, int ldkv, int64_t kv_batch_stride, const float* o,
+                                     const float* dout, int ldo, const float* lse, float* dq, float* dk, float* dv, int lddkv, int64_t dkv_batch_stride,
+                                     int B, int Hq, int Hkv, int Lq, int T, int terms, void* workspace, size_t ws_bytes, void* stream);
+/* RMSNorm backward: with r = rsqrt(mean(x^2) + eps) and u = gamma * dy, dx = [dres +] r u - x r^3 mean(x u).  One wave per row; dy, x and dx pitched
+ * lddy / ldx / lddx; dres (NULL, or the residual stream's gradient, pitched lddx; dx may alias it) is added in the same pass. */
+int awt_op_rmsnorm_backward(awt_ctx* c, const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* gamma, const float* dres, float* dx,
+                            int64_t lddx, int M, int d, float eps, void* stream);
+/* dgamma[j] = sum_m dy[m, j] x[m, j] r_m: slabs of 256 rows summed top to bottom, then added in slab order (as awt_op_column_sums_ld).  The workspace
+ * (256-byte aligned) holds r and the slabs; its query answers without a GPU. */
+size_t awt_op_rmsnorm_param_grad_workspace_bytes(int M, int d);
+int awt_op_rmsnorm_param_grad(awt_ctx* c, const float* dy, int64_t lddy, const float* x, int64_t ldx, float* dgamma, int M, int d, float eps,
+                              void* workspace, size_t ws_bytes, void* stream);
+/* SwiGLU backward over gu [M, ld] (the forward's input) and dy [M, lddy] into dgu [M, lddgu] (gate | up): with s = 1 / (1 + exp(-g)),
+ * dgate = dy * up * s * (1 + g (1 - s)), dup = dy * g * s.  No overflow at any g. */
+int awt_op_silu_mul_backward(awt_ctx* c, const float* gu, int64_t ld, const float* dy, int64_t lddy, float* dgu, int64_t lddgu, int M, int I, void* stream);
+/* Backward of awt_op_qk_norm_rope into dqkv [B Lq, ld] (the layout of qkv), one wave per (row, head).  Inputs: the forward's qkv (pre-norm), gains, tables and
+ * positions; dq (pitch ldq), the gradient of the rotated q; dk / dv, the gradients of the cache rows in the cache's layout (row (b, positions[r]) at
+ * dk + b kv_batch_stride + positions[r] ldkv + 128 g).  q and k heads: the transposed rotation a' = a cos + b sin, b' = b cos - a sin of the pair (i, i + 64),
+ * then the per-head RMSNorm backward with r recomputed from qkv; dv is copied (bit-identical).  dq_gamma / dk_gamma [128] (both or neither): the gains'
+ * gradients summed over rows and heads in a fixed order (slabs of 256 (row, head) pairs), with the 256-byte aligned workspace of the query below. */
+size_t awt_op_qk_norm_rope_backward_workspace_bytes(int B, int Lq, int Hq, int Hkv);
+int awt_op_qk_norm_rope_backward(awt_ctx* c, const float* qkv, int64_t ld, const float* q_gamma, const float* k_gamma, const float* cos, const float* sin,
+                                 const int32_t* positions, const float* dq, int64_t ldq, const float* dk, const float* dv, int64_t ldkv,
+                                 int64_t kv_batch_stride, float* dqkv, float* dq_gamma, float* dk_gamma, int B, int Lq, int Hq, int Hkv, float eps,
+                                 void* workspace, size_t ws_bytes, void* stream);
+
 /* Causal attention of Lq new query rows per batch over a preallocated decode cache: keys / values of batch b, position j at
  * k + b kv_batch_stride + j ldkv + 64 h (likewise v), T live positions (T >= Lq; query i sees keys j <= T - Lq + i).  q / o as in
  * awt_op_attention_small.  The cache is [rows, Tmax, 2 d] per layer, so kv_batch_stride = Tmax ldkv (csrc/decoder_ops.hip). */

@@ -140,6 +140,15 @@ _SIGNATURES = {
     "awt_op_causal_attention_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "awt_op_causal_attention": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "awt_op_silu_mul": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _vp]),
+    "awt_op_causal_attention_lse": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i64, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "awt_op_causal_attention_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "awt_op_causal_attention_backward": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "awt_op_rmsnorm_backward": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _f, _vp]),
+    "awt_op_rmsnorm_param_grad_workspace_bytes": (_sz, [_i, _i]),
+    "awt_op_rmsnorm_param_grad": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i, _i, _f, _vp, _sz, _vp]),
+    "awt_op_silu_mul_backward": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _vp]),
+    "awt_op_qk_norm_rope_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "awt_op_qk_norm_rope_backward": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "awt_op_attention_cached": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i64, _vp, _i, _i, _i, _i, _i, _vp]),
     "awt_select_tokens_workspace_bytes": (_sz, [_i, _i, _i]),
     "awt_op_select_tokens": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

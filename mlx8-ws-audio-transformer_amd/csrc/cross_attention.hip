@@ -17,6 +17,7 @@
 //   dk / dv   S = Q K^T and dP = dO V^T (32 queries x 32 keys per wave and tile), dV^T += dO^T P, dK^T += Q^T dS; 64 keys per workgroup, the two waves of a
 //             key block each form 64 of the 128 dims (k, v fragments and both 128-dim accumulators do not fit one wave's registers; S and dP are formed twice)
 // delta = rowsum(dO * O) comes from a small launch of its own into the workspace.  No atomics anywhere: two runs give the same bits.
+// CAUSAL variants of all three (awt_op_causal_attention, _lse, _backward: a decode cache with grouped KV heads, Qwen3Decoder) are compile-time branches.
 // TERMS = 3: every operand is a hi + lo bf16 pair, three MFMAs per fragment pair (a_lo b_hi + a_hi b_lo + a_hi b_hi); TERMS = 1: hi only.
 #include <algorithm>
 #include "common.h"
@@ -40,7 +41,8 @@ struct XArgs {
   int B, H, Lq, Sk;
   int64_t ldq, ldk, ldv, ldo;
   float scale;                     // 128^-1/2
-  int Hkv; int64_t kvbs;           // causal forward only: KV heads (query head h reads KV head h / (H / Hkv)) and the cache's batch stride; Sk is then T
+  int Hkv; int64_t kvbs;           // causal kernels only: KV heads (query head h reads KV head h / (H / Hkv)) and the cache's batch stride; Sk is then T
+  int64_t lddkv, dkvbs;            // causal dk / dv launch only: row pitch and batch stride of dk / dv (the cache's layout, Hkv heads)
 };
 
 template <bool LO>
@@ -293,7 +295,10 @@ __global__ __launch_bounds__(XTHREADS) void xattn_delta_kernel(XArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ dq
-template <int TERMS>
+// CAUSAL (awt_op_causal_attention_backward): the forward's addressing and bounds -- k / v are the cache, the workgroup streams key tiles up to its last query's
+// diagonal only (`Sk`: also the staging's valid-row count, so nothing at or past row T is loaded), a wave skips the tiles past its own last query, and inside the
+// tiles that remain p = 0 where key > T - Lq + query.
+template <int TERMS, bool CAUSAL = false>
 __global__ __launch_bounds__(XTHREADS) void xattn_dq_kernel(XArgs a) {
   constexpr bool LO = TERMS == 3;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -310,8 +315,20 @@ __global__ __launch_bounds__(XTHREADS) void xattn_dq_kernel(XArgs a) {
   const int q0 = qb * XLB + wave * XLW, qi = q0 + r;
   const bool live = q0 < a.Lq;
   const int qc = min(qi, a.Lq - 1);
-  const float* kbase = a.k + (int64_t)b * a.Sk * a.ldk + XD * head;
-  const float* vbase = a.v + (int64_t)b * a.Sk * a.ldv + XD * head;
+  const float *kbase, *vbase;
+  int Sk, lim = 0, wlim = 0;                                       // as in the forward
+  if constexpr (CAUSAL) {
+    const int kvh = head / (a.H / a.Hkv), off = a.Sk - a.Lq;
+    kbase = a.k + (int64_t)b * a.kvbs + XD * kvh;
+    vbase = a.v + (int64_t)b * a.kvbs + XD * kvh;
+    Sk = off + min(qb * XLB + XLB, a.Lq);
+    lim = off + qc;
+    wlim = off + min(q0 + XLW, a.Lq) - 1;
+  } else {
+    kbase = a.k + (int64_t)b * a.Sk * a.ldk + XD * head;
+    vbase = a.v + (int64_t)b * a.Sk * a.ldv + XD * head;
+    Sk = a.Sk;
+  }
 
   bf16x8 qh[8], ql[8], gh[8], gl[8];
   load_frags<LO>(a.q + ((int64_t)b * a.Lq + qc) * a.ldq + XD * head, h, qh, ql);
@@ -325,27 +342,28 @@ __global__ __launch_bounds__(XTHREADS) void xattn_dq_kernel(XArgs a) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[dt][i] = 0.f;
 
-  const int nt = (a.Sk + XKT - 1) / XKT;
+  const int nt = (Sk + XKT - 1) / XKT;
   for (int t = 0; t < nt; ++t) {
     const int k0 = t * XKT;
     __syncthreads();                                               // the previous tile's fragment reads are done
     {                                                              // one image at a time: the staging registers of all three do not fit beside the fragments
       float4 kr[XKT / 8];
-      load_rows<XKT>(kbase + (int64_t)k0 * a.ldk, a.ldk, a.Sk - k0, tid, kr);
-      write_rows<XKT, LO>(kr, a.Sk - k0, tid, kh, kl);
+      load_rows<XKT>(kbase + (int64_t)k0 * a.ldk, a.ldk, Sk - k0, tid, kr);
+      write_rows<XKT, LO>(kr, Sk - k0, tid, kh, kl);
     }
     {
       float4 vr[XKT / 8];
-      load_rows<XKT>(vbase + (int64_t)k0 * a.ldv, a.ldv, a.Sk - k0, tid, vr);
-      write_rows<XKT, LO>(vr, a.Sk - k0, tid, vh, vl);
+      load_rows<XKT>(vbase + (int64_t)k0 * a.ldv, a.ldv, Sk - k0, tid, vr);
+      write_rows<XKT, LO>(vr, Sk - k0, tid, vh, vl);
     }
     {
       float kc[XKT / 2];
-      load_cols<XKT>(kbase + (int64_t)k0 * a.ldk, a.ldk, a.Sk - k0, tid, kc);
-      write_cols<XKT, LO>(kc, a.Sk - k0, tid, kth, ktl);
+      load_cols<XKT>(kbase + (int64_t)k0 * a.ldk, a.ldk, Sk - k0, tid, kc);
+      write_cols<XKT, LO>(kc, Sk - k0, tid, kth, ktl);
     }
     __syncthreads();
     if (!live) continue;
+    if constexpr (CAUSAL) { if (k0 > wlim) continue; }           // wave-uniform: every key of the tile lies past this wave's last query
 
 #pragma unroll 1
     for (int blk = 0; blk < 2; ++blk) {                            // 32 keys at a time, not unrolled: both products of a block, then the next block
@@ -360,7 +378,8 @@ __global__ __launch_bounds__(XTHREADS) void xattn_dq_kernel(XArgs a) {
       }
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const float p = k0 + 32 * blk + acc_row(i, h) < a.Sk ? __builtin_amdgcn_exp2f(fmaf(st[i], sc2, -lse2)) : 0.f;
+        const int kj = k0 + 32 * blk + acc_row(i, h);
+        const float p = (CAUSAL ? kj <= lim : kj < Sk) ? __builtin_amdgcn_exp2f(fmaf(st[i], sc2, -lse2)) : 0.f;
         st[i] = p * (dp[i] - delta);
       }
       bf16x8 dsh[2], dsl[2];
@@ -378,7 +397,11 @@ __global__ __launch_bounds__(XTHREADS) void xattn_dq_kernel(XArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ dk / dv
-template <int TERMS>
+// CAUSAL (awt_op_causal_attention_backward): one workgroup per (batch, KV head, 64-key block) of the cache.  It walks the KV head's a.H / a.Hkv query heads in
+// ascending order and, per head, the 32-query tiles from the first one that can see the block's first key (query i sees key j iff j <= T - Lq + i; the tiles
+// wholly before the diagonal are never loaded); dk and dv stay in the accumulators across the heads -- the group sum, in a fixed order, without atomics --
+// and are stored once, in the cache's layout (a.lddkv, a.dkvbs).  p = 0 where key > T - Lq + query.
+template <int TERMS, bool CAUSAL = false>
 __global__ __launch_bounds__(XTHREADS) void xattn_dkv_kernel(XArgs a) {
   constexpr bool LO = TERMS == 3;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -395,17 +418,21 @@ __global__ __launch_bounds__(XTHREADS) void xattn_dkv_kernel(XArgs a) {
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int nkb = (a.Sk + XKB - 1) / XKB;
-  const int bh = blockIdx.x / nkb, kb = blockIdx.x - bh * nkb, b = bh / a.H, head = bh - b * a.H;
+  const int bh = blockIdx.x / nkb, kb = blockIdx.x - bh * nkb;     // CAUSAL: bh counts (batch, KV head) pairs
+  const int nhead = CAUSAL ? a.Hkv : a.H, b = bh / nhead, head = bh - b * nhead;
   const int dh = wave & 1;                                         // this wave's half of the 128 dims: two waves share 32 keys
   const int kw0 = kb * XKB + (wave >> 1) * XLW, ki = kw0 + r;
   const bool live = kw0 < a.Sk;
   const int kc = min(ki, a.Sk - 1);
-  const float* qbase = a.q + (int64_t)b * a.Lq * a.ldq + XD * head;
-  const float* gbase = a.dout + (int64_t)b * a.Lq * a.ldo + XD * head;
 
   bf16x8 kfh[8], kfl[8], vfh[8], vfl[8];
-  load_frags<LO>(a.k + ((int64_t)b * a.Sk + kc) * a.ldk + XD * head, h, kfh, kfl);
-  load_frags<LO>(a.v + ((int64_t)b * a.Sk + kc) * a.ldv + XD * head, h, vfh, vfl);
+  if constexpr (CAUSAL) {                                          // the cache: batch stride kvbs, ldk = ldv
+    load_frags<LO>(a.k + (int64_t)b * a.kvbs + (int64_t)kc * a.ldk + XD * head, h, kfh, kfl);
+    load_frags<LO>(a.v + (int64_t)b * a.kvbs + (int64_t)kc * a.ldv + XD * head, h, vfh, vfl);
+  } else {
+    load_frags<LO>(a.k + ((int64_t)b * a.Sk + kc) * a.ldk + XD * head, h, kfh, kfl);
+    load_frags<LO>(a.v + ((int64_t)b * a.Sk + kc) * a.ldv + XD * head, h, vfh, vfl);
+  }
   const float sc2 = a.scale * kLog2e;
 
   f32x16 dk[2], dv[2];
@@ -415,62 +442,79 @@ __global__ __launch_bounds__(XTHREADS) void xattn_dkv_kernel(XArgs a) {
     for (int i = 0; i < 16; ++i) { dk[dt][i] = 0.f; dv[dt][i] = 0.f; }
 
   const int nt = (a.Lq + XQT - 1) / XQT;
-  for (int t = 0; t < nt; ++t) {
-    const int q0 = t * XQT;
-    __syncthreads();                                               // the previous tile's fragment reads are done
-    {
-      float4 qr[XQT / 8], gr[XQT / 8];
-      load_rows<XQT>(qbase + (int64_t)q0 * a.ldq, a.ldq, a.Lq - q0, tid, qr);
-      load_rows<XQT>(gbase + (int64_t)q0 * a.ldo, a.ldo, a.Lq - q0, tid, gr);
-      write_rows<XQT, LO>(qr, a.Lq - q0, tid, qh, ql);
-      write_rows<XQT, LO>(gr, a.Lq - q0, tid, gh, gl);
-    }
-    {
-      float qc[XQT / 2], gc[XQT / 2];
-      load_cols<XQT>(qbase + (int64_t)q0 * a.ldq, a.ldq, a.Lq - q0, tid, qc);
-      load_cols<XQT>(gbase + (int64_t)q0 * a.ldo, a.ldo, a.Lq - q0, tid, gc);
-      write_cols<XQT, LO>(qc, a.Lq - q0, tid, qth, qtl);
-      write_cols<XQT, LO>(gc, a.Lq - q0, tid, gth, gtl);
-    }
-    if (tid < XQT) {
-      const bool ok = q0 + tid < a.Lq;
-      lse2_s[tid] = ok ? a.lse_in[(int64_t)bh * a.Lq + q0 + tid] * kLog2e : 0.f;
-      delta_s[tid] = ok ? a.delta_in[(int64_t)bh * a.Lq + q0 + tid] : 0.f;
-    }
-    __syncthreads();
-    if (!live) continue;
-
-    f32x16 st, dp;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { st[i] = 0.f; dp[i] = 0.f; }
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      const int off = r * XRP + 16 * s + 8 * h;
-      st = mma3<LO>(lds_frag(qh + off), lds_frag(ql + off), kfh[s], kfl[s], st);
-      dp = mma3<LO>(lds_frag(gh + off), lds_frag(gl + off), vfh[s], vfl[s], dp);
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int row = acc_row(i, h);
-      const float p = q0 + row < a.Lq ? __builtin_amdgcn_exp2f(fmaf(st[i], sc2, -lse2_s[row])) : 0.f;   // tail queries weigh nothing
-      st[i] = p;
-      dp[i] = p * (dp[i] - delta_s[row]);
-    }
-    bf16x8 ph[2], pl[2], dsh[2], dsl[2];
-    acc_frags<LO>(st, ph, pl);
-    acc_frags<LO>(dp, dsh, dsl);
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int off = (64 * dh + 32 * dt + r) * (XQT + 8) + 16 * s + 8 * h;
-        dv[dt] = mma3<LO>(lds_frag(gth + off), lds_frag(gtl + off), ph[s], pl[s], dv[dt]);
-        dk[dt] = mma3<LO>(lds_frag(qth + off), lds_frag(qtl + off), dsh[s], dsl[s], dk[dt]);
+  const int coff = a.Sk - a.Lq;                                    // CAUSAL: query i sees key j iff j <= coff + i
+  const int group = CAUSAL ? a.H / a.Hkv : 1;
+  const int t0 = CAUSAL ? max(kb * XKB - coff, 0) / XQT : 0;        // the first query tile that sees the block's first key (t0 < nt: key T - 1 is seen by query Lq - 1)
+  int j = 0;
+  do {                                                             // the KV head's query heads (non-causal: one pass, the condition below is a constant)
+    const int qhead = CAUSAL ? head * group + j : head, qbh = CAUSAL ? b * a.H + qhead : bh;
+    const float* qbase = a.q + (int64_t)b * a.Lq * a.ldq + XD * qhead;
+    const float* gbase = a.dout + (int64_t)b * a.Lq * a.ldo + XD * qhead;
+    for (int t = t0; t < nt; ++t) {
+      const int q0 = t * XQT;
+      __syncthreads();                                               // the previous tile's fragment reads are done
+      {
+        float4 qr[XQT / 8], gr[XQT / 8];
+        load_rows<XQT>(qbase + (int64_t)q0 * a.ldq, a.ldq, a.Lq - q0, tid, qr);
+        load_rows<XQT>(gbase + (int64_t)q0 * a.ldo, a.ldo, a.Lq - q0, tid, gr);
+        write_rows<XQT, LO>(qr, a.Lq - q0, tid, qh, ql);
+        write_rows<XQT, LO>(gr, a.Lq - q0, tid, gh, gl);
       }
-  }
+      {
+        float qc[XQT / 2], gc[XQT / 2];
+        load_cols<XQT>(qbase + (int64_t)q0 * a.ldq, a.ldq, a.Lq - q0, tid, qc);
+        load_cols<XQT>(gbase + (int64_t)q0 * a.ldo, a.ldo, a.Lq - q0, tid, gc);
+        write_cols<XQT, LO>(qc, a.Lq - q0, tid, qth, qtl);
+        write_cols<XQT, LO>(gc, a.Lq - q0, tid, gth, gtl);
+      }
+      if (tid < XQT) {
+        const bool ok = q0 + tid < a.Lq;
+        lse2_s[tid] = ok ? a.lse_in[(int64_t)qbh * a.Lq + q0 + tid] * kLog2e : 0.f;
+        delta_s[tid] = ok ? a.delta_in[(int64_t)qbh * a.Lq + q0 + tid] : 0.f;
+      }
+      __syncthreads();
+      if (!live) continue;
+      if constexpr (CAUSAL) { if (coff + q0 + XQT - 1 < kw0) continue; }   // wave-uniform: no query of the tile sees any of this wave's keys
+  
+      f32x16 st, dp;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) { st[i] = 0.f; dp[i] = 0.f; }
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const int off = r * XRP + 16 * s + 8 * h;
+        st = mma3<LO>(lds_frag(qh + off), lds_frag(ql + off), kfh[s], kfl[s], st);
+        dp = mma3<LO>(lds_frag(gh + off), lds_frag(gl + off), vfh[s], vfl[s], dp);
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int row = acc_row(i, h);
+        const bool seen = CAUSAL ? q0 + row < a.Lq && ki <= coff + q0 + row : q0 + row < a.Lq;
+        const float p = seen ? __builtin_amdgcn_exp2f(fmaf(st[i], sc2, -lse2_s[row])) : 0.f;   // tail (and, CAUSAL, masked) queries weigh nothing
+        st[i] = p;
+        dp[i] = p * (dp[i] - delta_s[row]);
+      }
+      bf16x8 ph[2], pl[2], dsh[2], dsl[2];
+      acc_frags<LO>(st, ph, pl);
+      acc_frags<LO>(dp, dsh, dsl);
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const int off = (64 * dh + 32 * dt + r) * (XQT + 8) + 16 * s + 8 * h;
+          dv[dt] = mma3<LO>(lds_frag(gth + off), lds_frag(gtl + off), ph[s], pl[s], dv[dt]);
+          dk[dt] = mma3<LO>(lds_frag(qth + off), lds_frag(qtl + off), dsh[s], dsl[s], dk[dt]);
+        }
+    }
+  } while (CAUSAL && ++j < group);
   if (live && ki < a.Sk) {
-    store_acc_t(dk, a.scale, a.dk + ((int64_t)b * a.Sk + ki) * a.ldk + XD * head + 64 * dh, h);
-    store_acc_t(dv, 1.0f, a.dv + ((int64_t)b * a.Sk + ki) * a.ldv + XD * head + 64 * dh, h);
+    if constexpr (CAUSAL) {
+      const int64_t orow = (int64_t)b * a.dkvbs + (int64_t)ki * a.lddkv + XD * head + 64 * dh;
+      store_acc_t(dk, a.scale, a.dk + orow, h);
+      store_acc_t(dv, 1.0f, a.dv + orow, h);
+    } else {
+      store_acc_t(dk, a.scale, a.dk + ((int64_t)b * a.Sk + ki) * a.ldk + XD * head + 64 * dh, h);
+      store_acc_t(dv, 1.0f, a.dv + ((int64_t)b * a.Sk + ki) * a.ldv + XD * head + 64 * dh, h);
+    }
   }
 }
 
@@ -545,6 +589,39 @@ extern "C" int awt_op_cross_attention_backward(awt_ctx* c, const float* q, int l
 }
 
 // ------------------------------------------------------------------------------------------------ causal self-attention over a decode cache (Qwen3Decoder)
+namespace {
+
+int check_causal(const char* who, const void* k, const void* v, int ldq, int ldkv, int64_t kv_batch_stride, int ldo, int B, int Hq, int Hkv, int Lq, int T, int terms) {
+  const std::string w(who);
+  AWT_REQUIRE(Hkv > 0 && Hq > 0 && Hq % Hkv == 0, AWT_ERR_INVALID, w + ": Hq must be a positive multiple of Hkv");
+  AWT_REQUIRE(Lq >= 1 && T >= Lq, AWT_ERR_INVALID, w + ": needs 1 <= Lq <= T (T live cache positions, the Lq new ones included)");
+  int rc = check_shape(who, B, Hq, Lq, T, ldq, ldq, ldq, ldo, terms); if (rc) return rc;   // the cache's pitch has Hkv heads: checked below
+  AWT_REQUIRE(ldkv >= (int64_t)Hkv * XD && ldkv % 4 == 0, AWT_ERR_INVALID, w + ": ldkv must hold Hkv * 128 columns and be a multiple of 4");
+  AWT_REQUIRE(kv_batch_stride % 4 == 0 && kv_batch_stride >= (int64_t)(T - 1) * ldkv + (int64_t)Hkv * XD, AWT_ERR_INVALID,
+              w + ": kv_batch_stride must be a multiple of 4 and hold a batch's T cache rows");
+  AWT_REQUIRE(aligned16(k) && aligned16(v), AWT_ERR_INVALID, w + ": tensors must be 16-byte aligned");
+  return AWT_OK;
+}
+
+int causal_forward(const char* who, awt_ctx* c, const float* q, int ldq, const float* k, const float* v, int ldkv, int64_t kv_batch_stride, float* o, int ldo, float* lse,
+                   int B, int Hq, int Hkv, int Lq, int T, int terms, size_t ws_bytes, void* stream) {
+  const std::string w(who);
+  AWT_REQUIRE(c && q && k && v && o, AWT_ERR_INVALID, w + ": null argument");
+  int rc = check_causal(who, k, v, ldq, ldkv, kv_batch_stride, ldo, B, Hq, Hkv, Lq, T, terms); if (rc) return rc;
+  AWT_REQUIRE(aligned16(q) && aligned16(o), AWT_ERR_INVALID, w + ": tensors must be 16-byte aligned");
+  AWT_REQUIRE(ws_bytes >= xattn_layout(nullptr, B, Hq, Lq, 0).bytes, AWT_ERR_INVALID, w + ": workspace too small");
+  XArgs a{};
+  a.q = q; a.k = k; a.v = v; a.out = o; a.lse = lse; a.B = B; a.H = Hq; a.Hkv = Hkv; a.Lq = Lq; a.Sk = T; a.ldq = ldq; a.ldk = ldkv; a.ldv = ldkv; a.ldo = ldo;
+  a.kvbs = kv_batch_stride;
+  a.scale = 0.08838834764831845f;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(c, AWT_PROF_ATTENTION, s, 2.0 * B * Hq * (double)Lq * (2.0 * T - Lq + 1) * XD * terms);   // the visible (query, key) pairs only
+  const dim3 grid(B * Hq * ((Lq + XLB - 1) / XLB)), block(XTHREADS);
+  return terms == 3 ? launch_kernel<xattn_fwd_kernel<3, true>>(grid, block, fwd_lds(3), s, a) : launch_kernel<xattn_fwd_kernel<1, true>>(grid, block, fwd_lds(1), s, a);
+}
+
+}  // namespace
+
 extern "C" size_t awt_op_causal_attention_workspace_bytes(int B, int Hq, int Lq, int T) {
   (void)T;
   if (B <= 0 || Hq <= 0 || Lq <= 0) return 0;
@@ -553,22 +630,50 @@ extern "C" size_t awt_op_causal_attention_workspace_bytes(int B, int Hq, int Lq,
 
 extern "C" int awt_op_causal_attention(awt_ctx* c, const float* q, int ldq, const float* k, const float* v, int ldkv, int64_t kv_batch_stride, float* o, int ldo,
                                        int B, int Hq, int Hkv, int Lq, int T, int terms, void* workspace, size_t ws_bytes, void* stream) {
-  AWT_REQUIRE(c && q && k && v && o, AWT_ERR_INVALID, "op_causal_attention: null argument");
-  AWT_REQUIRE(Hkv > 0 && Hq > 0 && Hq % Hkv == 0, AWT_ERR_INVALID, "op_causal_attention: Hq must be a positive multiple of Hkv");
-  AWT_REQUIRE(Lq >= 1 && T >= Lq, AWT_ERR_INVALID, "op_causal_attention: needs 1 <= Lq <= T (T live cache positions, the Lq new ones included)");
-  int rc = check_shape("op_causal_attention", B, Hq, Lq, T, ldq, ldq, ldq, ldo, terms); if (rc) return rc;   // the cache's pitch has Hkv heads: checked below
-  AWT_REQUIRE(ldkv >= (int64_t)Hkv * XD && ldkv % 4 == 0, AWT_ERR_INVALID, "op_causal_attention: ldkv must hold Hkv * 128 columns and be a multiple of 4");
-  AWT_REQUIRE(kv_batch_stride % 4 == 0 && kv_batch_stride >= (int64_t)(T - 1) * ldkv + (int64_t)Hkv * XD, AWT_ERR_INVALID,
-              "op_causal_attention: kv_batch_stride must be a multiple of 4 and hold a batch's T cache rows");
-  AWT_REQUIRE(aligned16(q) && aligned16(k) && aligned16(v) && aligned16(o), AWT_ERR_INVALID, "op_causal_attention: tensors must be 16-byte aligned");
-  AWT_REQUIRE(ws_bytes >= xattn_layout(nullptr, B, Hq, Lq, 0).bytes, AWT_ERR_INVALID, "op_causal_attention: workspace too small");
   (void)workspace;
+  return causal_forward("op_causal_attention", c, q, ldq, k, v, ldkv, kv_batch_stride, o, ldo, nullptr, B, Hq, Hkv, Lq, T, terms, ws_bytes, stream);
+}
+
+extern "C" int awt_op_causal_attention_lse(awt_ctx* c, const float* q, int ldq, const float* k, const float* v, int ldkv, int64_t kv_batch_stride, float* o, int ldo,
+                                           float* lse, int B, int Hq, int Hkv, int Lq, int T, int terms, void* workspace, size_t ws_bytes, void* stream) {
+  (void)workspace;
+  AWT_REQUIRE(lse, AWT_ERR_INVALID, "op_causal_attention_lse: null argument");
+  return causal_forward("op_causal_attention_lse", c, q, ldq, k, v, ldkv, kv_batch_stride, o, ldo, lse, B, Hq, Hkv, Lq, T, terms, ws_bytes, stream);
+}
+
+extern "C" size_t awt_op_causal_attention_backward_workspace_bytes(int B, int Hq, int Lq, int T) {
+  (void)T;
+  if (B <= 0 || Hq <= 0 || Lq <= 0) return 0;
+  return xattn_layout(nullptr, B, Hq, Lq, 1).bytes;                // delta [B, Hq, Lq]
+}
+
+extern "C" int awt_op_causal_attention_backward(awt_ctx* c, const float* q, int ldq, const float* k, const float* v, int ldkv, int64_t kv_batch_stride, const float* o,
+                                                const float* dout, int ldo, const float* lse, float* dq, float* dk, float* dv, int lddkv, int64_t dkv_batch_stride,
+                                                int B, int Hq, int Hkv, int Lq, int T, int terms, void* workspace, size_t ws_bytes, void* stream) {
+  const char* who = "op_causal_attention_backward";
+  AWT_REQUIRE(c && q && k && v && o && dout && lse && dq && dk && dv && workspace, AWT_ERR_INVALID, "op_causal_attention_backward: null argument");
+  int rc = check_causal(who, k, v, ldq, ldkv, kv_batch_stride, ldo, B, Hq, Hkv, Lq, T, terms); if (rc) return rc;
+  AWT_REQUIRE(lddkv >= (int64_t)Hkv * XD && lddkv % 4 == 0, AWT_ERR_INVALID, "op_causal_attention_backward: lddkv must hold Hkv * 128 columns and be a multiple of 4");
+  AWT_REQUIRE(dkv_batch_stride % 4 == 0 && dkv_batch_stride >= (int64_t)(T - 1) * lddkv + (int64_t)Hkv * XD, AWT_ERR_INVALID,
+              "op_causal_attention_backward: dkv_batch_stride must be a multiple of 4 and hold a batch's T rows");
+  AWT_REQUIRE(aligned16(q) && aligned16(o) && aligned16(dout) && aligned16(dq) && aligned16(dk) && aligned16(dv), AWT_ERR_INVALID,
+              "op_causal_attention_backward: tensors must be 16-byte aligned");
+  AWT_REQUIRE(((uintptr_t)workspace & 255) == 0, AWT_ERR_INVALID, "op_causal_attention_backward: workspace must be 256-byte aligned");
+  AWT_REQUIRE(ws_bytes >= xattn_layout(nullptr, B, Hq, Lq, 1).bytes, AWT_ERR_INVALID, "op_causal_attention_backward: workspace too small");
+  const XWs ws = xattn_layout(workspace, B, Hq, Lq, 1);
   XArgs a{};
-  a.q = q; a.k = k; a.v = v; a.out = o; a.lse = nullptr; a.B = B; a.H = Hq; a.Hkv = Hkv; a.Lq = Lq; a.Sk = T; a.ldq = ldq; a.ldk = ldkv; a.ldv = ldkv; a.ldo = ldo;
-  a.kvbs = kv_batch_stride;
+  a.q = q; a.k = k; a.v = v; a.o = o; a.dout = dout; a.lse_in = lse; a.delta = ws.delta; a.delta_in = ws.delta; a.dq = dq; a.dk = dk; a.dv = dv;
+  a.B = B; a.H = Hq; a.Hkv = Hkv; a.Lq = Lq; a.Sk = T; a.ldq = ldq; a.ldk = ldkv; a.ldv = ldkv; a.ldo = ldo;
+  a.kvbs = kv_batch_stride; a.lddkv = lddkv; a.dkvbs = dkv_batch_stride;
   a.scale = 0.08838834764831845f;
   hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(c, AWT_PROF_ATTENTION, s, 2.0 * B * Hq * (double)Lq * (2.0 * T - Lq + 1) * XD * terms);   // the visible (query, key) pairs only
-  const dim3 grid(B * Hq * ((Lq + XLB - 1) / XLB)), block(XTHREADS);
-  return terms == 3 ? launch_kernel<xattn_fwd_kernel<3, true>>(grid, block, fwd_lds(3), s, a) : launch_kernel<xattn_fwd_kernel<1, true>>(grid, block, fwd_lds(1), s, a);
+  ProfScope ps(c, AWT_PROF_ATTENTION_BWD, s, 5.0 * B * Hq * (double)Lq * (2.0 * T - Lq + 1) * XD * terms);   // the visible (query, key) pairs only
+  const dim3 block(XTHREADS);
+  const int64_t waves = (int64_t)B * Lq * Hq;
+  hipLaunchKernelGGL(xattn_delta_kernel, dim3((unsigned)((waves + 3) / 4)), block, 0, s, a);
+  AWT_HIP_CHECK(hipGetLastError());
+  const dim3 gq(B * Hq * ((Lq + XLB - 1) / XLB)), gk(B * Hkv * ((T + XKB - 1) / XKB));
+  rc = terms == 3 ? launch_kernel<xattn_dq_kernel<3, true>>(gq, block, dq_lds(3), s, a) : launch_kernel<xattn_dq_kernel<1, true>>(gq, block, dq_lds(1), s, a);
+  if (rc) return rc;
+  return terms == 3 ? launch_kernel<xattn_dkv_kernel<3, true>>(gk, block, dkv_lds(3), s, a) : launch_kernel<xattn_dkv_kernel<1, true>>(gk, block, dkv_lds(1), s, a);
 }

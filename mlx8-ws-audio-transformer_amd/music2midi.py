@@ -26,9 +26,12 @@ autograd_ops.py, shared with the classifiers; `_CrossAttention` here):
 The two residual adds, the dtype casts and the row slices of `in_proj_weight` are element-wise / view ops of torch under autograd.  There is no
 torch fallback for any operator above: without libawt or without a GPU the first call raises.
 
-`Qwen3Decoder` and `MusicTranscriptionModel` (further down) are the stock Qwen decoder and the model around all three pieces,
-inference only: teacher-forced loss and logits, and `generate` with a KV cache, on awt_op_rmsnorm / awt_op_qk_norm_rope / awt_op_causal_attention /
-awt_op_silu_mul and the packed-weight GEMMs.
+`Qwen3Decoder` and `MusicTranscriptionModel` (further down; DESIGN.md sections 4.12 and 4.13) are the stock Qwen decoder and the model around all three
+pieces: teacher-forced loss and logits, and `generate` with a KV cache, on awt_op_rmsnorm / awt_op_qk_norm_rope / awt_op_causal_attention / awt_op_silu_mul
+and the packed-weight GEMMs.  Built with `trainable_layers=K` the decoder also trains, under the reference's rule (the top K layers, the final norm, the
+output head), and passes the gradient of `inputs_embeds` down through every layer to the adapter: `_Qwen3Graph` is one autograd node whose backward is
+libawt calls (awt_op_causal_attention_backward, awt_op_qk_norm_rope_backward, awt_op_rmsnorm_backward / _param_grad, awt_op_silu_mul_backward,
+awt_linear_backward_input, awt_op_weight_grad, awt_op_embed_backward).
 
 `encode_audio(audio_features)` returns the projected key / value buffer `audio_kv` [B, Sa, 2 text_dim]; `forward(text, audio_kv=audio_kv)` reuses it.
 The reference's `generate` recomputes the projection for every new token (model.py:314-341); a caller of this module computes it once per clip.
@@ -188,12 +191,21 @@ class Qwen3Decoder(nn.Module):
 
     Parameters carry HF's names (`model.embed_tokens.weight`, `model.layers.N.self_attn.q_proj.weight`, ..., `model.norm.weight`, `lm_head.weight` when
     untied), fp32; a bf16 checkpoint is upcast by `load_state_dict`.  The packed GEMM operands are built on first use and again after `load_state_dict`,
-    `resize_token_embeddings` or a move to another device.  Everything runs under `torch.no_grad()`; asked for an autograd graph it raises
-    NotImplementedError (training through the decoder is DESIGN.md section 8's next item).  There is no torch fallback: without libawt or a GPU it raises."""
+    `resize_token_embeddings` or a move to another device.  There is no torch fallback: without libawt or a GPU it raises.
 
-    def __init__(self, config: Qwen3Config, precision: str = "bf16x3"):
+    trainable_layers=None (the default) is the inference-only decoder: every parameter frozen, everything under `torch.no_grad()`, and asked for an autograd
+    graph it raises NotImplementedError.  trainable_layers=K, an int in [0, num_hidden_layers], is the reference's fine-tuning rule (.charles/music2midi/
+    model.py:242-261): requires_grad on every parameter of the last K layers, on `model.norm.weight` and on the output head -- `lm_head.weight`, or with tied
+    embeddings `model.embed_tokens.weight`, the one tensor HF holds under both names -- and nothing else.  `forward` then builds a graph when grad is enabled
+    (`_Qwen3Graph`): gradients reach `inputs_embeds` through all layers and every trainable parameter; the packed operands carry their transpose planes and
+    follow the parameters after an optimizer step (only what changed is packed again, `PackedLinear.update`).  `prefill` / `step` stay inference only."""
+
+    def __init__(self, config: Qwen3Config, precision: str = "bf16x3", trainable_layers: Optional[int] = None):
         super().__init__()
         c = config
+        if trainable_layers is not None and (isinstance(trainable_layers, bool) or not isinstance(trainable_layers, int)
+                                             or not 0 <= trainable_layers <= c.num_hidden_layers):
+            raise ValueError(f"trainable_layers must be None or an int in [0, {c.num_hidden_layers}] (num_hidden_layers), got {trainable_layers!r}")
         if c.head_dim != HEAD_DIM:
             raise ValueError(f"head_dim must be {HEAD_DIM}, the native kernels' head_dim (got {c.head_dim})")
         if precision not in ("bf16", "bf16x3"):
@@ -202,7 +214,7 @@ class Qwen3Decoder(nn.Module):
             raise ValueError("num_attention_heads must be a positive multiple of num_key_value_heads")
         if c.hidden_size <= 0 or c.hidden_size % 128 or c.intermediate_size <= 0 or c.intermediate_size % 64:
             raise ValueError("hidden_size must be a multiple of 128 and intermediate_size of 64 (the MFMA GEMM's N tile and K step)")
-        self.config, self.precision = c, precision
+        self.config, self.precision, self.trainable_layers = c, precision, trainable_layers
         d, I, Hq, Hkv = c.hidden_size, c.intermediate_size, c.num_attention_heads, c.num_key_value_heads
         self.model = nn.Module()
         self.model.embed_tokens = nn.Embedding(c.vocab_size, d)
@@ -222,9 +234,21 @@ class Qwen3Decoder(nn.Module):
         if not c.tie_word_embeddings:
             self.lm_head = _Weight(c.vocab_size, d)
         self._packed = None
+        self._versions = None
         self._rope = None
+        if trainable_layers is not None:
+            for p in self._reference_trainable():
+                p.requires_grad_(True)
 
     # ---- parameters
+    def _head_weight(self) -> nn.Parameter:
+        return self.model.embed_tokens.weight if self.config.tie_word_embeddings else self.lm_head.weight
+
+    def _reference_trainable(self) -> list:
+        """The parameters the reference trains: the last `trainable_layers` layers, the final norm, the output head."""
+        first = self.config.num_hidden_layers - self.trainable_layers
+        return [p for layer in self.model.layers[first:] for p in layer.parameters()] + [self.model.norm.weight, self._head_weight()]
+
     def get_input_embeddings(self) -> nn.Embedding:
         return self.model.embed_tokens
 
@@ -237,7 +261,7 @@ class Qwen3Decoder(nn.Module):
             out = torch.empty((n, w.shape[1]), dtype=w.dtype, device=w.device)
             nn.init.normal_(out, std=0.02)
             out[: min(n, w.shape[0])] = w[: min(n, w.shape[0])]
-            return nn.Parameter(out, requires_grad=False)
+            return nn.Parameter(out, requires_grad=w.requires_grad)
 
         emb = nn.Embedding(n, old.shape[1], device=old.device, dtype=old.dtype)
         emb.weight = resized(old)
@@ -261,17 +285,33 @@ class Qwen3Decoder(nn.Module):
         return super()._apply(fn, *a, **kw)
 
     def _pack(self) -> dict:
-        if self._packed is None:
-            from .native_decoder import PackedLinear
-            mk = lambda w: PackedLinear(w, None, self.precision, backward=False)
-            layers = []
-            for layer in self.model.layers:
-                att, mlp = layer.self_attn, layer.mlp
-                layers.append({"qkv": mk(torch.cat([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])), "o": mk(att.o_proj.weight),
-                               "gu": mk(torch.cat([mlp.gate_proj.weight, mlp.up_proj.weight])), "down": mk(mlp.down_proj.weight)})
-            head = self.model.embed_tokens.weight if self.config.tie_word_embeddings else self.lm_head.weight
-            self._packed = {"layers": layers, "lm_head": mk(head)}
-        return self._packed
+        """The fused q | k | v, o, gate | up and down projections of every layer and the output head as `awt_weight` handles.  Inference only: packed once.
+        Trainable: with the transpose planes of `backward_input`, and brought up to date when a parameter changed -- the same Parameter objects at new versions
+        (an optimizer step) re-pack only the handles made of a changed parameter, in place; anything else builds every handle."""
+        train = self.trainable_layers is not None
+        vers = tuple((id(p), p._version) for p in self.parameters()) if train else None      # identity too: a replaced Parameter starts at version 0 again
+        if self._packed is not None and self._versions == vers:
+            return self._packed
+        from .native_decoder import PackedLinear
+        plan = []                                                          # (slot, key, the parameters it is made of, what to pack)
+        fresh = self._packed is None or tuple(i for i, _ in self._versions) != tuple(i for i, _ in vers)
+        pk = {"layers": [{} for _ in self.model.layers]} if fresh else self._packed
+        for layer, slot in zip(self.model.layers, pk["layers"]):
+            att, mlp = layer.self_attn, layer.mlp
+            plan += [(slot, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), lambda att=att: torch.cat([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])),
+                     (slot, "o", (att.o_proj.weight,), lambda att=att: att.o_proj.weight),
+                     (slot, "gu", (mlp.gate_proj.weight, mlp.up_proj.weight), lambda mlp=mlp: torch.cat([mlp.gate_proj.weight, mlp.up_proj.weight])),
+                     (slot, "down", (mlp.down_proj.weight,), lambda mlp=mlp: mlp.down_proj.weight)]
+        plan.append((pk, "lm_head", (self._head_weight(),), self._head_weight))
+        changed = set() if fresh else {i for (i, v), (_, v0) in zip(vers, self._versions) if v != v0}
+        with torch.no_grad():
+            for slot, key, sources, make in plan:
+                if fresh:
+                    slot[key] = PackedLinear(make(), None, self.precision, backward=train)
+                elif any(id(p) in changed for p in sources):
+                    slot[key].update(make(), None)
+        self._packed, self._versions = pk, vers
+        return pk
 
     def _rope_tables(self, device):
         """cos / sin [max_position_embeddings, 64] fp32 as HF's Qwen3RotaryEmbedding forms them: fp32 inv_freq, fp32 outer product, then cos / sin."""
@@ -283,13 +323,18 @@ class Qwen3Decoder(nn.Module):
         return self._rope
 
     # ---- the layers
-    def _check_input(self, x: torch.Tensor) -> None:
+    def _check_input(self, x: torch.Tensor, graph_ok: bool = False) -> bool:
+        """Validates inputs_embeds; True when the call has to build an autograd graph (a trainable decoder's `forward` with grad enabled)."""
         if x.dim() != 3 or x.shape[-1] != self.config.hidden_size:
             raise ValueError(f"inputs_embeds must be [B, L, {self.config.hidden_size}], got {tuple(x.shape)}")
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        graph = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if graph and self.trainable_layers is None:
             raise NotImplementedError("Qwen3Decoder is inference only: there is no backward through the decoder (call it under torch.no_grad(), with its "
-                                      "parameters frozen); training is DESIGN.md section 8's next item")
+                                      "parameters frozen), or build it with trainable_layers=K to train it")
+        if graph and not graph_ok:
+            raise NotImplementedError("Qwen3Decoder.prefill / step are inference only (call them under torch.no_grad()); `forward` is what builds a graph")
         _lib.ctx(x.device)                                                 # raises without a GPU: no CPU fallback
+        return graph
 
     @staticmethod
     def _check_mask(m: Optional[torch.Tensor], B: int, L: int) -> None:
@@ -350,26 +395,187 @@ class Qwen3Decoder(nn.Module):
     def forward(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None):
         """logits [B, L, vocab], and with labels (logits, loss): HF's causal-LM loss -- the logits at t against the label at t + 1, ignore_index -100, mean over
         the counted positions (awt_op_cross_entropy).  attention_mask: rows of ones followed by zeros (right padding) or None.  Under causality a live position
-        never sees a padded one, so the mask changes nothing at live positions and is only validated; the outputs at padded positions are unspecified."""
-        self._check_input(inputs_embeds)
+        never sees a padded one, so the mask changes nothing at live positions and is only validated; the outputs at padded positions are unspecified.
+        A decoder built with `trainable_layers`, called with grad enabled, returns them with a graph (`_Qwen3Graph`): the loss is differentiable when labels
+        are given (the logits beside it are then detached), else the logits are."""
+        graph = self._check_input(inputs_embeds, graph_ok=True)
         B, L, _ = inputs_embeds.shape
         self._check_mask(attention_mask, B, L)
         if labels is not None and tuple(labels.shape) != (B, L):
             raise ValueError(f"labels must be [{B}, {L}], got {tuple(labels.shape)}")
+        if graph:
+            return self._forward_graph(inputs_embeds, labels)
         padded = self._run(inputs_embeds, Qwen3Cache(self.config, B, L, inputs_embeds.device), False)
         logits = padded.view(B, L, -1)[:, :, : self.config.vocab_size]
         if labels is None:
             return logits
         from .native_decoder import cross_entropy
-        shifted = torch.full((B, L), -100, dtype=torch.int64, device=padded.device)
-        shifted[:, :-1] = labels[:, 1:].to(padded.device)
-        return logits, cross_entropy(padded, shifted.reshape(-1), self.config.vocab_size)[0]
+        return logits, cross_entropy(padded, self._shifted(labels, padded.device).reshape(-1), self.config.vocab_size)[0]
+
+    @staticmethod
+    def _shifted(labels: torch.Tensor, device) -> torch.Tensor:
+        """HF's causal-LM targets: position t is scored against the label at t + 1, the last position against nothing."""
+        B, L = labels.shape
+        shifted = torch.full((B, L), -100, dtype=torch.int64, device=device)
+        shifted[:, :-1] = labels[:, 1:].to(device)
+        return shifted
+
+    def _forward_graph(self, inputs_embeds: torch.Tensor, labels: Optional[torch.Tensor]):
+        B, L, _ = inputs_embeds.shape
+        if L > self.config.max_position_embeddings:                        # the rotary tables' rows (the inference path checks it in Qwen3Cache)
+            raise ValueError(f"inputs_embeds holds {L} positions, more than max_position_embeddings ({self.config.max_position_embeddings})")
+        trained = [p for p in self.parameters() if p.requires_grad]
+        holder: list = []
+        shifted = None if labels is None else self._shifted(labels, inputs_embeds.device)
+        out = _Qwen3Graph.apply(inputs_embeds, self, shifted, holder, *trained)
+        if labels is None:
+            return out.view(B, L, -1)[:, :, : self.config.vocab_size]
+        return holder[0].view(B, L, -1)[:, :, : self.config.vocab_size], out
+
+
+class _Qwen3Graph(torch.autograd.Function):
+    """The decoder, its head and (with labels) HF's shifted cross-entropy as ONE autograd node with a hand-written native backward (the `_DecoderLoss`
+    pattern of native_decoder.py): d / d(inputs_embeds) through every layer, and the gradient of every trainable parameter, each formed where its dY is live.
+
+    Saved per layer (fp32, M = B L rows): the layer's input x0 and the stream after the attention half x1 [M, d] each, the pre-norm qkv [M, (Hq + 2 Hkv) 128],
+    the rotated q and the attention output o [M, Hq 128] each, the layer's k / v cache [B, L, Hkv 128] each, lse [B, Hq, L], and gate | up [M, 2 I].  The two
+    RMSNorm outputs h and the SwiGLU output act are NOT saved: the backward recomputes them (one row pass each), and only in trained layers, whose weight
+    gradients are their only readers.  Without a gradient for inputs_embeds the layers below the first trained one save nothing and are not walked back.
+
+    Returns the loss (labels given; the padded logits go to `holder`) or the padded logits [M, Np]."""
+
+    @staticmethod
+    def forward(ctx, inputs_embeds, dec: "Qwen3Decoder", shifted, holder, *trained):
+        from .native_decoder import cross_entropy
+        c, dev = dec.config, inputs_embeds.device
+        B, L, d = inputs_embeds.shape
+        Hq, Hkv, I, eps = c.num_attention_heads, c.num_key_value_heads, c.intermediate_size, c.rms_norm_eps
+        M, wq, wkv = B * L, Hq * HEAD_DIM, Hkv * HEAD_DIM
+        packed, (cos, sin) = dec._pack(), dec._rope_tables(dev)
+        positions = torch.arange(L, dtype=torch.int32, device=dev).repeat(B)
+        first_saved = 0 if inputs_embeds.requires_grad else c.num_hidden_layers - dec.trainable_layers
+        x = inputs_embeds.detach().float().reshape(M, d).contiguous()
+        if x.data_ptr() == inputs_embeds.data_ptr() and first_saved > 0:
+            x = x.clone()                                                  # the unsaved layers' residual GEMMs write x in place
+        h = torch.empty_like(x)
+        act = torch.empty((M, I), dtype=torch.float32, device=dev)
+        ws = _lib.workspace(ops.causal_attention_workspace_bytes(B, Hq, L, L), dev)
+        saved = []
+        for i, (layer, pk) in enumerate(zip(dec.model.layers, packed["layers"])):
+            keep = i >= first_saved
+            ops.rmsnorm((x, 0), d, layer.input_layernorm.weight, M, d, eps, y=(h, 0), ldy=d)
+            qkv = pk["qkv"].forward(h)
+            q, o = torch.empty((M, wq), dtype=torch.float32, device=dev), torch.empty((M, wq), dtype=torch.float32, device=dev)
+            kc, vc = torch.empty((B, L, wkv), dtype=torch.float32, device=dev), torch.empty((B, L, wkv), dtype=torch.float32, device=dev)
+            ops.qk_norm_rope((qkv, 0), pk["qkv"].Np, layer.self_attn.q_norm.weight, layer.self_attn.k_norm.weight, cos, sin, positions, (q, 0), wq,
+                             (kc, 0), (vc, 0), wkv, L * wkv, B, L, Hq, Hkv, eps)
+            _, lse = ops.causal_attention_lse((q, 0), wq, (kc, 0), (vc, 0), wkv, L * wkv, B, Hq, Hkv, L, L, dec.precision, o=(o, 0), ldo=wq, workspace=ws)
+            x1 = pk["o"].forward(o, resid=x, out=torch.empty_like(x) if keep else x)
+            ops.rmsnorm((x1, 0), d, layer.post_attention_layernorm.weight, M, d, eps, y=(h, 0), ldy=d)
+            gu = pk["gu"].forward(h)
+            ops.silu_mul((gu, 0), pk["gu"].Np, M, I, y=(act, 0), ldy=I)
+            x2 = pk["down"].forward(act, resid=x1, out=torch.empty_like(x) if keep else x1)
+            if keep:
+                saved.append((x, qkv, q, kc, vc, o, lse, x1, gu))
+            x = x2
+        xf = ops.rmsnorm((x, 0), d, dec.model.norm.weight, M, d, eps)
+        logits = packed["lm_head"].forward(xf)                             # [M, Np]
+        ctx.dec, ctx.saved, ctx.first_saved, ctx.x_last, ctx.xf, ctx.shape, ctx.positions = dec, saved, first_saved, x, xf, (B, L), positions
+        ctx.trained_ids = [id(p) for p in trained]
+        if shifted is None:
+            ctx.dlogits = None
+            return logits
+        loss, ctx.dlogits = cross_entropy(logits, shifted.reshape(-1), c.vocab_size)
+        holder.append(logits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dec, (B, L) = ctx.dec, ctx.shape
+        c, prec = dec.config, dec.precision
+        d, Hq, Hkv, I, eps = c.hidden_size, c.num_attention_heads, c.num_key_value_heads, c.intermediate_size, c.rms_norm_eps
+        M, wq, wkv = B * L, Hq * HEAD_DIM, Hkv * HEAD_DIM
+        pk, (cos, sin) = dec._pack(), dec._rope_tables(g.device)
+        grads = {}                                                         # id(parameter) -> gradient
+
+        # head: logits = RMSNorm(x) W^T.  The padding columns of dlogits are zero, so dW runs on the vocabulary rounded up to the weight-gradient GEMM's 8.
+        dlogits = (g.contiguous() if ctx.dlogits is None else ctx.dlogits * g).float()
+        dxf = pk["lm_head"].backward_input(dlogits)
+        norm = dec.model.norm.weight
+        grads[id(dec._head_weight())] = ops.weight_grad(dlogits, ctx.xf, n=ops.pad_to(c.vocab_size, 8), precision=prec)[: c.vocab_size]
+        grads[id(norm)] = ops.rmsnorm_param_grad((dxf, 0), d, (ctx.x_last, 0), d, M, d, eps)
+        dx = ops.rmsnorm_backward((dxf, 0), d, (ctx.x_last, 0), d, norm, M, d, eps)
+        del dxf, dlogits
+
+        first_trained = c.num_hidden_layers - dec.trainable_layers
+        ws = _lib.workspace(ops.causal_attention_backward_workspace_bytes(B, Hq, L, L), dx.device)
+        for i in range(c.num_hidden_layers - 1, ctx.first_saved - 1, -1):
+            layer, p, trained = dec.model.layers[i], pk["layers"][i], i >= first_trained
+            att, mlp = layer.self_attn, layer.mlp
+            x0, qkv, q, kc, vc, o, lse, x1, gu = ctx.saved[i - ctx.first_saved]
+            # MLP half: x2 = x1 + down(silu(gate) * up), gate | up = gu(RMSNorm(x1))
+            dact = p["down"].backward_input(dx)
+            dgu = ops.silu_mul_backward((gu, 0), p["gu"].Np, (dact, 0), I, M, I)
+            dh = p["gu"].backward_input(dgu)
+            if trained:
+                grads[id(mlp.down_proj.weight)] = ops.weight_grad(dx, ops.silu_mul((gu, 0), p["gu"].Np, M, I), precision=prec)
+                hn = ops.rmsnorm((x1, 0), d, layer.post_attention_layernorm.weight, M, d, eps)
+                grads[id(mlp.gate_proj.weight)] = ops.weight_grad(dgu, hn, n=I, ycol=0, precision=prec)
+                grads[id(mlp.up_proj.weight)] = ops.weight_grad(dgu, hn, n=I, ycol=I, precision=prec)
+                grads[id(layer.post_attention_layernorm.weight)] = ops.rmsnorm_param_grad((dh, 0), d, (x1, 0), d, M, d, eps)
+            ops.rmsnorm_backward((dh, 0), d, (x1, 0), d, layer.post_attention_layernorm.weight, M, d, eps, dres=(dx, 0), dx=(dx, 0), lddx=d)
+            del dact, dgu, dh
+            # attention half: x1 = x0 + o_proj(attention(qk_norm_rope(qkv(RMSNorm(x0)))))
+            do = p["o"].backward_input(dx)
+            dq = torch.empty_like(q)
+            dkc, dvc = torch.empty_like(kc), torch.empty_like(vc)       # every element of all three is written
+            ops.causal_attention_backward((q, 0), wq, (kc, 0), (vc, 0), wkv, L * wkv, (o, 0), (do, 0), wq, lse, (dq, 0), (dkc, 0), (dvc, 0), wkv, L * wkv,
+                                          B, Hq, Hkv, L, L, prec, workspace=ws)
+            dqkv = torch.empty_like(qkv)
+            gains = ops.qk_norm_rope_backward((qkv, 0), p["qkv"].Np, att.q_norm.weight, att.k_norm.weight, cos, sin, ctx.positions, (dq, 0), wq, (dkc, 0), (dvc, 0),
+                                              wkv, L * wkv, (dqkv, 0), B, L, Hq, Hkv, eps, want_gains=trained)
+            dh = p["qkv"].backward_input(dqkv)
+            if trained:
+                grads[id(att.o_proj.weight)] = ops.weight_grad(dx, o, precision=prec)
+                hn = ops.rmsnorm((x0, 0), d, layer.input_layernorm.weight, M, d, eps)
+                for proj, n, col in ((att.q_proj, wq, 0), (att.k_proj, wkv, wq), (att.v_proj, wkv, wq + wkv)):      # the fused gradient, split by column
+                    grads[id(proj.weight)] = ops.weight_grad(dqkv, hn, n=n, ycol=col, precision=prec)
+                grads[id(att.q_norm.weight)], grads[id(att.k_norm.weight)] = gains
+                grads[id(layer.input_layernorm.weight)] = ops.rmsnorm_param_grad((dh, 0), d, (x0, 0), d, M, d, eps)
+            ops.rmsnorm_backward((dh, 0), d, (x0, 0), d, layer.input_layernorm.weight, M, d, eps, dres=(dx, 0), dx=(dx, 0), lddx=d)
+            del do, dq, dkc, dvc, dqkv, dh
+            ctx.saved[i - ctx.first_saved] = None
+        ctx.saved = ctx.dlogits = ctx.xf = ctx.x_last = None
+        dx_in = dx.view(B, L, d) if ctx.needs_input_grad[0] else None
+        return (dx_in, None, None, None, *(grads[i] for i in ctx.trained_ids))
+
+
+class _EmbedLookup(torch.autograd.Function):
+    """weight[ids] whose backward ADDS the rows' gradients into a zeroed table with awt_op_embed_backward (one workgroup per table row, ascending order, no
+    atomics) instead of torch's atomic scatter: the lookup side of the tied embedding's gradient.  autograd adds it to the head's side."""
+
+    @staticmethod
+    def forward(ctx, weight, ids):
+        ctx.ids, ctx.rows = ids, weight.shape[0]
+        return weight.detach()[ids]
+
+    @staticmethod
+    def backward(ctx, g):
+        from .native_decoder import embed_backward
+        B, L = ctx.ids.shape
+        d = g.shape[-1]
+        dtok = torch.zeros((ctx.rows, d), dtype=torch.float32, device=g.device)
+        dpos = torch.zeros((L, d), dtype=torch.float32, device=g.device)          # the operator's position table: not wanted here, thrown away
+        embed_backward(ctx.ids, g.float().reshape(B * L, d).contiguous(), dtok, dpos)
+        return dtok, None
 
 
 class MusicTranscriptionModel(nn.Module):
     """The reference's MusicTranscriptionModel (model.py:190-344) from its three pieces: an audio tower (`WhisperAudioEncoder`, or any callable
-    (waveforms, sampling_rate) -> [B, Sa, audio_dim]), the `CrossAttentionAdapter` and a `Qwen3Decoder`.  Inference only: `forward` returns the
-    teacher-forced loss under `torch.no_grad()`, `generate` decodes with a KV cache."""
+    (waveforms, sampling_rate) -> [B, Sa, audio_dim]), the `CrossAttentionAdapter` and a `Qwen3Decoder`.  `forward` returns the teacher-forced loss,
+    `generate` decodes with a KV cache.  With an inference-only decoder `forward` runs under `torch.no_grad()` only; with a decoder built with
+    `trainable_layers` and grad enabled the loss is differentiable: the adapter, the decoder's trainable parameters and (tied) the embedding train, the
+    audio tower runs under `no_grad` as in the reference (model.py:242-261)."""
 
     def __init__(self, audio_encoder, adapter: CrossAttentionAdapter, decoder: Qwen3Decoder, tokenizer=None):
         super().__init__()
@@ -379,17 +585,27 @@ class MusicTranscriptionModel(nn.Module):
 
     def _embed(self, ids: torch.Tensor) -> torch.Tensor:
         emb = self.text_decoder.get_input_embeddings()
-        return emb(ids.to(emb.weight.device))
+        ids = ids.to(emb.weight.device)
+        if torch.is_grad_enabled() and emb.weight.requires_grad:           # the tied embedding trains: its lookup's backward is awt_op_embed_backward
+            return _EmbedLookup.apply(emb.weight, ids)
+        return emb(ids)
 
     def forward(self, waveforms, sampling_rate: int, target_token_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The teacher-forced loss of model.py:263-288 (labels = target_token_ids, shifted inside).  The reference leaves the labels at padded positions as
-        they are; so does this: pass -100 there through `target_token_ids`' own padding convention if they are to be ignored."""
-        if torch.is_grad_enabled():
-            raise NotImplementedError("MusicTranscriptionModel.forward is inference only: the adapter's gradient needs a backward through the decoder "
-                                      "(call it under torch.no_grad())")
-        audio = self.audio_encoder(waveforms, sampling_rate)
+        they are; so does this: pass -100 there through `target_token_ids`' own padding convention if they are to be ignored.  With grad enabled and a
+        decoder built with `trainable_layers` the loss carries a graph; the audio tower runs under `no_grad` either way."""
+        if torch.is_grad_enabled() and self.text_decoder.trainable_layers is None:
+            raise NotImplementedError("MusicTranscriptionModel.forward is inference only with an inference-only decoder: the adapter's gradient needs a "
+                                      "backward through the decoder (call it under torch.no_grad(), or build the decoder with trainable_layers=K)")
+        with torch.no_grad():
+            audio = self.audio_encoder(waveforms, sampling_rate)
         fused = self.cross_attention_adapter(self._embed(target_token_ids.clamp_min(0)), audio.float())
         return self.text_decoder(fused, attention_mask=attention_mask, labels=target_token_ids)[1]
+
+    def trainable_state_dict(self) -> dict:
+        """The requires_grad entries under the reference's names, `cross_attention_adapter.*` and `text_decoder.*` (train.py:285-288), detached;
+        `load_state_dict(..., strict=False)` takes it back."""
+        return {n: p.detach() for n, p in self.named_parameters() if p.requires_grad and n.startswith(("cross_attention_adapter.", "text_decoder."))}
 
     @torch.no_grad()
     def generate(self, waveform, sampling_rate: int, max_new_tokens: int = 256, temperature: float = 0.7, do_sample: bool = True,

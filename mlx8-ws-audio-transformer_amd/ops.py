@@ -306,3 +306,98 @@ def silu_mul(gu, ld: int, M: int, I: int, y=None, ldy: Optional[int] = None):
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().awt_op_silu_mul(_lib.ctx(dev), _at(gu), int(ld), _at(y), int(ldy), int(M), int(I), _lib.stream_handle()))
     return y[0]
+
+
+# ---- their backward (include/awt.h): what music2midi.Qwen3Decoder's training pass is chained from
+def causal_attention_lse(q, ldq: int, k, v, ldkv: int, kv_batch_stride: int, B: int, Hq: int, Hkv: int, Lq: int, T: int, precision="bf16x3", o=None,
+                         ldo: Optional[int] = None, lse: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """`causal_attention` that also writes the log-sum-exp (awt_op_causal_attention_lse).  Returns (o's tensor, lse [B, Hq, Lq])."""
+    terms = precision if isinstance(precision, int) else _terms(precision)
+    dev = q[0].device
+    if o is None:
+        o, ldo = (torch.empty((B * Lq, Hq * 128), dtype=torch.float32, device=dev), 0), Hq * 128
+    if lse is None:
+        lse = torch.empty((B, Hq, Lq), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_op_causal_attention_workspace_bytes(B, Hq, Lq, T), dev) if workspace is None else workspace
+    with torch.cuda.device(dev):
+        _lib.check(L.awt_op_causal_attention_lse(_lib.ctx(dev), _at(q), int(ldq), _at(k), _at(v), int(ldkv), int(kv_batch_stride), _at(o), int(ldo), _lib.ptr(lse),
+                                                 int(B), int(Hq), int(Hkv), int(Lq), int(T), int(terms), _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
+    return o[0], lse
+
+
+def causal_attention_backward_workspace_bytes(B: int, Hq: int, Lq: int, T: int) -> int:
+    """Workspace of `causal_attention_backward`; answers without a GPU."""
+    return int(_lib.lib().awt_op_causal_attention_backward_workspace_bytes(int(B), int(Hq), int(Lq), int(T)))
+
+
+def causal_attention_backward(q, ldq: int, k, v, ldkv: int, kv_batch_stride: int, o, dout, ldo: int, lse: torch.Tensor, dq, dk, dv, lddkv: int,
+                              dkv_batch_stride: int, B: int, Hq: int, Hkv: int, Lq: int, T: int, precision="bf16x3",
+                              workspace: Optional[torch.Tensor] = None) -> None:
+    """Writes dq (laid out like q) and dk / dv (the cache's layout at pitch lddkv and batch stride dkv_batch_stride) of `causal_attention_lse`
+    (awt_op_causal_attention_backward).  Every tensor argument but lse is a (tensor, element offset) pair."""
+    terms = precision if isinstance(precision, int) else _terms(precision)
+    dev = q[0].device
+    L = _lib.lib()
+    ws = _lib.workspace(L.awt_op_causal_attention_backward_workspace_bytes(B, Hq, Lq, T), dev) if workspace is None else workspace
+    with torch.cuda.device(dev):
+        _lib.check(L.awt_op_causal_attention_backward(_lib.ctx(dev), _at(q), int(ldq), _at(k), _at(v), int(ldkv), int(kv_batch_stride), _at(o), _at(dout), int(ldo),
+                                                      _lib.ptr(lse), _at(dq), _at(dk), _at(dv), int(lddkv), int(dkv_batch_stride), int(B), int(Hq), int(Hkv),
+                                                      int(Lq), int(T), int(terms), _lib.ptr(ws), ws.numel(), _lib.stream_handle()))
+
+
+def rmsnorm_backward(dy, lddy: int, x, ldx: int, gamma: torch.Tensor, M: int, d: int, eps: float, dres=None, dx=None, lddx: Optional[int] = None):
+    """dx = [dres +] d(RMSNorm(x) gamma)/dx . dy (awt_op_rmsnorm_backward).  dy, x (and dres / dx, both at pitch lddx): (tensor, element offset) pairs.
+    Returns dx's tensor ([M, d] unless given; dx may be dres)."""
+    dev = x[0].device
+    if dx is None:
+        dx, lddx = (torch.empty((M, d), dtype=torch.float32, device=dev), 0), d
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().awt_op_rmsnorm_backward(_lib.ctx(dev), _at(dy), int(lddy), _at(x), int(ldx), _at((gamma, 0)), None if dres is None else _at(dres),
+                                                      _at(dx), int(lddx), int(M), int(d), float(eps), _lib.stream_handle()))
+    return dx[0]
+
+
+def rmsnorm_param_grad(dy, lddy: int, x, ldx: int, M: int, d: int, eps: float) -> torch.Tensor:
+    """dgamma [d] = sum_m dy[m] * x[m] * rsqrt(mean(x[m]^2) + eps) (awt_op_rmsnorm_param_grad)."""
+    dev = x[0].device
+    L = _lib.lib()
+    dg = torch.empty(d, dtype=torch.float32, device=dev)
+    ws = _lib.workspace(L.awt_op_rmsnorm_param_grad_workspace_bytes(M, d), dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.awt_op_rmsnorm_param_grad(_lib.ctx(dev), _at(dy), int(lddy), _at(x), int(ldx), _lib.ptr(dg), int(M), int(d), float(eps), _lib.ptr(ws),
+                                               ws.numel(), _lib.stream_handle()))
+    return dg
+
+
+def silu_mul_backward(gu, ld: int, dy, lddy: int, M: int, I: int, dgu=None, lddgu: Optional[int] = None):
+    """dgu [M, 2 I] (gate | up) of `silu_mul` under dy [M, I] (awt_op_silu_mul_backward).  Returns dgu's tensor ([M, 2 I] unless given)."""
+    dev = gu[0].device
+    if dgu is None:
+        dgu, lddgu = (torch.empty((M, 2 * I), dtype=torch.float32, device=dev), 0), 2 * I
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().awt_op_silu_mul_backward(_lib.ctx(dev), _at(gu), int(ld), _at(dy), int(lddy), _at(dgu), int(lddgu), int(M), int(I), _lib.stream_handle()))
+    return dgu[0]
+
+
+def qk_norm_rope_backward_workspace_bytes(B: int, Lq: int, Hq: int, Hkv: int) -> int:
+    """Workspace of `qk_norm_rope_backward`'s gain gradients; answers without a GPU."""
+    return int(_lib.lib().awt_op_qk_norm_rope_backward_workspace_bytes(int(B), int(Lq), int(Hq), int(Hkv)))
+
+
+def qk_norm_rope_backward(qkv, ld: int, q_gamma: torch.Tensor, k_gamma: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, positions: torch.Tensor, dq, ldq: int,
+                          dk, dv, ldkv: int, kv_batch_stride: int, dqkv, B: int, Lq: int, Hq: int, Hkv: int, eps: float, want_gains: bool = False):
+    """Backward of `qk_norm_rope` into dqkv (laid out like qkv) from dq and the cache-layout dk / dv (awt_op_qk_norm_rope_backward).  With want_gains returns
+    (dq_gamma, dk_gamma) [128] each, else None."""
+    dev = qkv[0].device
+    if positions.dtype != torch.int32 or positions.numel() != B * Lq or not positions.is_contiguous():
+        raise ValueError("qk_norm_rope_backward: positions must be a contiguous int32 tensor of B * Lq elements")
+    L = _lib.lib()
+    gains = (torch.empty(128, dtype=torch.float32, device=dev), torch.empty(128, dtype=torch.float32, device=dev)) if want_gains else (None, None)
+    ws = _lib.workspace(L.awt_op_qk_norm_rope_backward_workspace_bytes(B, Lq, Hq, Hkv), dev) if want_gains else None
+    with torch.cuda.device(dev):
+        _lib.check(L.awt_op_qk_norm_rope_backward(_lib.ctx(dev), _at(qkv), int(ld), _at((q_gamma, 0)), _at((k_gamma, 0)), _at((cos, 0)), _at((sin, 0)),
+                                                  _lib.ptr(positions), _at(dq), int(ldq), _at(dk), _at(dv), int(ldkv), int(kv_batch_stride), _at(dqkv),
+                                                  _lib.ptr(gains[0]), _lib.ptr(gains[1]), int(B), int(Lq), int(Hq), int(Hkv), float(eps), _lib.ptr(ws),
+                                                  0 if ws is None else ws.numel(), _lib.stream_handle()))
+    return gains if want_gains else None
