@@ -362,6 +362,14 @@ size_t awt_linear_workspace_bytes(const awt_weight* w, int M, int backward);   /
 /* y [M, Np] = x [M, K] W^T + bias (+ resid [M, Np], may alias y)      F.linear / the residual adds of HF:modeling_whisper.py:468-500 */
 int awt_linear_forward(awt_ctx* c, const awt_weight* w, const float* x, const float* resid, float* y, int M, void* workspace,
                        size_t ws_bytes, void* stream);
+/* The same product for the rows of incremental decoding, 1 <= M <= 8 (any other M: AWT_ERR_INVALID): y [M, Np] = x [M, K] W^T + bias (+ resid [M, Np] or
+ * NULL, may alias y).  The output side is awt_linear_forward's: pitch Np, columns N .. Np - 1 come out as 0 + resid, the bias is the handle's, the launch goes
+ * to the caller's stream without synchronisation.  It takes NO workspace and has no plane-split launch in front: one weight-streaming kernel (csrc/gemv.hip)
+ * reads the hi / lo planes the handle already owns (there is no second copy of a weight; awt_weight_update stays all a trained weight needs) and splits the
+ * fp32 rows of x itself, hi = rne_bf16(x), lo = rne_bf16(x - hi).  Precisions 1 and 3; the products are the GEMM's (a_hi w_hi + a_hi w_lo + a_lo w_hi in
+ * fp32), summed over K in an order that depends on (Np, K, precision) only: the result is bit-reproducible, and row m of an M-row call is bit-identical to
+ * the M = 1 call on that row.  Nothing past row M - 1 of x is read, nothing past row M - 1 of y is written.  x must be 16-byte aligned. */
+int awt_linear_decode(awt_ctx* c, const awt_weight* w, const float* x, const float* resid, float* y, int M, void* stream);
 /* dx [M, K] = dy [M, Np] W                                             (frozen weight: no weight gradient) */
 int awt_linear_backward_input(awt_ctx* c, const awt_weight* w, const float* dy, float* dx, int M, void* workspace, size_t ws_bytes,
                               void* stream);

@@ -108,6 +108,7 @@ _SIGNATURES = {
     "awt_op_embed_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "awt_linear_workspace_bytes": (_sz, [_vp, _i, _i]),
     "awt_linear_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "awt_linear_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "awt_linear_backward_input": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "awt_encoder_set_grad_scale_log2": (_i, [_vp, _i]),
     "awt_bmm_packed_bytes": (_sz, [_i, _i, _i]),

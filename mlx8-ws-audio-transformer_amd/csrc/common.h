@@ -248,6 +248,15 @@ __device__ __forceinline__ void store_act4(const Act& o, int64_t off, const floa
   }
 }
 
+// ---------------------------------------------------------------- packed nn.Linear weights (awt_weight_create, decoder_ops.hip; read by gemm.hip's GEMM and gemv.hip)
+struct awt_weight {
+  awt_ctx* ctx = nullptr;
+  int N = 0, K = 0, Np = 0, prec = PREC_BF16X3;
+  bf16_t *hi = nullptr, *lo = nullptr;        // [Np, K] fragment-major (w_frag_index)
+  bf16_t *t_hi = nullptr, *t_lo = nullptr;    // [K, Np] fragment-major: the weight of dx = dy W
+  float* bias = nullptr;                      // [Np] (zero-padded) or null
+};
+
 // ---------------------------------------------------------------- wave reductions (device): all 64 lanes get the result, fixed order
 __device__ __forceinline__ float wave_max(float x) {
 #pragma unroll

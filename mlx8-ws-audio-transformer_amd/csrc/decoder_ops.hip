@@ -17,13 +17,7 @@
 #include "wgrad.h"
 
 // ------------------------------------------------------------------------------------------------ packed frozen weights
-struct awt_weight {
-  awt_ctx* ctx = nullptr;
-  int N = 0, K = 0, Np = 0, prec = PREC_BF16X3;
-  bf16_t *hi = nullptr, *lo = nullptr;        // [Np, K] fragment-major (w_frag_index)
-  bf16_t *t_hi = nullptr, *t_lo = nullptr;    // [K, Np] fragment-major: the weight of dx = dy W
-  float* bias = nullptr;                      // [Np] (zero-padded) or null
-};
+// (struct awt_weight: common.h -- gemv.hip reads the same planes)
 
 namespace {
 int dmalloc0(void** p, size_t bytes) {

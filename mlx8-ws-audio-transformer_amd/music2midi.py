@@ -49,6 +49,7 @@ from .autograd_ops import AlignedLinear, Gelu, LayerNorm
 
 HEAD_DIM = 128            # csrc/cross_attention.hip
 MAX_TEXT_DIM = 1280       # the LayerNorm kernels' row limit
+DECODE_ROWS = 8           # awt_linear_decode's row limit (csrc/gemv.hip): `step` up to this batch, and the group size of `generate_batch`
 
 
 class _CrossAttention(torch.autograd.Function):
@@ -342,9 +343,10 @@ class Qwen3Decoder(nn.Module):
             raise ValueError("attention_mask must be [B, L] rows of ones followed by zeros (right padding); other masks are not supported")
 
     @torch.no_grad()
-    def _run(self, inputs_embeds: torch.Tensor, cache: Qwen3Cache, last_only: bool) -> torch.Tensor:
+    def _run(self, inputs_embeds: torch.Tensor, cache: Qwen3Cache, last_only: bool, decode: bool = False) -> torch.Tensor:
         """Appends the L positions of inputs_embeds [B, L, hidden] to the cache; the lm_head GEMM's output [B * L, Np] (Np = vocab padded to the GEMM's N
-        tile), or [B, Np] for the last position of each row with last_only."""
+        tile), or [B, Np] for the last position of each row with last_only.  decode (`step` at B <= DECODE_ROWS): the five linears run on the
+        weight-streaming `awt_linear_decode` (`PackedLinear.forward_decode`) instead of the GEMM -- the same products, summed over K in another order."""
         c, dev = self.config, inputs_embeds.device
         B, L, d = inputs_embeds.shape
         if B != cache.batch or cache.length + L > cache.max_length:
@@ -354,6 +356,7 @@ class Qwen3Decoder(nn.Module):
         packed, (cos, sin) = self._pack(), self._rope_tables(dev)
         positions = cache.ramp[cache.length:T]
         positions = positions if B == 1 else positions.repeat(B)
+        linear = (lambda pl: pl.forward_decode) if decode else (lambda pl: pl.forward)
         x = inputs_embeds.float().reshape(M, d).contiguous()
         if x.data_ptr() == inputs_embeds.data_ptr():
             x = x.clone()                                                  # the residual GEMMs write x in place
@@ -364,21 +367,21 @@ class Qwen3Decoder(nn.Module):
         ws = _lib.workspace(ops.causal_attention_workspace_bytes(B, Hq, L, T), dev)
         for i, (layer, pk) in enumerate(zip(self.model.layers, packed["layers"])):
             ops.rmsnorm((x, 0), d, layer.input_layernorm.weight, M, d, eps, y=(h, 0), ldy=d)
-            qkv = pk["qkv"].forward(h)
+            qkv = linear(pk["qkv"])(h)
             ops.qk_norm_rope((qkv, 0), pk["qkv"].Np, layer.self_attn.q_norm.weight, layer.self_attn.k_norm.weight, cos, sin, positions, (q, 0), Hq * HEAD_DIM,
                              (cache.k[i], 0), (cache.v[i], 0), wkv, cache.max_length * wkv, B, L, Hq, Hkv, eps)
             ops.causal_attention((q, 0), Hq * HEAD_DIM, (cache.k[i], 0), (cache.v[i], 0), wkv, cache.max_length * wkv, B, Hq, Hkv, L, T, self.precision,
                                  o=(o, 0), ldo=Hq * HEAD_DIM, workspace=ws)
-            pk["o"].forward(o, resid=x, out=x)
+            linear(pk["o"])(o, resid=x, out=x)
             ops.rmsnorm((x, 0), d, layer.post_attention_layernorm.weight, M, d, eps, y=(h, 0), ldy=d)
-            gu = pk["gu"].forward(h)
+            gu = linear(pk["gu"])(h)
             ops.silu_mul((gu, 0), pk["gu"].Np, M, I, y=(act, 0), ldy=I)
-            pk["down"].forward(act, resid=x, out=x)
+            linear(pk["down"])(act, resid=x, out=x)
         cache.length = T
         if last_only:
             x = x.view(B, L, d)[:, -1].contiguous()
         hn = ops.rmsnorm((x, 0), d, self.model.norm.weight, x.shape[0], d, eps)
-        return packed["lm_head"].forward(hn)
+        return linear(packed["lm_head"])(hn)
 
     def prefill(self, inputs_embeds: torch.Tensor, cache: Qwen3Cache) -> torch.Tensor:
         """Appends L positions to the cache (from position cache.length on); returns the last position's logits [B, vocab] (a view of the padded GEMM output)."""
@@ -386,11 +389,12 @@ class Qwen3Decoder(nn.Module):
         return self._run(inputs_embeds, cache, True)[:, : self.config.vocab_size]
 
     def step(self, inputs_embeds: torch.Tensor, cache: Qwen3Cache) -> torch.Tensor:
-        """One new position per row: inputs_embeds [B, 1, hidden] -> logits [B, vocab]; the lm_head GEMM has B rows."""
+        """One new position per row: inputs_embeds [B, 1, hidden] -> logits [B, vocab].  Up to DECODE_ROWS rows the linears of the step, the lm_head among
+        them, are weight-streaming launches (`awt_linear_decode`); beyond, the GEMM with B rows."""
         self._check_input(inputs_embeds)
         if inputs_embeds.shape[1] != 1:
             raise ValueError(f"step takes one position per row, got {inputs_embeds.shape[1]} (use prefill)")
-        return self._run(inputs_embeds, cache, True)[:, : self.config.vocab_size]
+        return self._run(inputs_embeds, cache, True, decode=inputs_embeds.shape[0] <= DECODE_ROWS)[:, : self.config.vocab_size]
 
     def forward(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None):
         """logits [B, L, vocab], and with labels (logits, loss): HF's causal-LM loss -- the logits at t against the label at t + 1, ignore_index -100, mean over
@@ -608,15 +612,22 @@ class MusicTranscriptionModel(nn.Module):
         return {n: p.detach() for n, p in self.named_parameters() if p.requires_grad and n.startswith(("cross_attention_adapter.", "text_decoder."))}
 
     @torch.no_grad()
-    def generate(self, waveform, sampling_rate: int, max_new_tokens: int = 256, temperature: float = 0.7, do_sample: bool = True,
-                 generator: Optional[torch.Generator] = None, bos_token_id=None, eos_token_id: Optional[int] = None):
-        """model.py:293-344 with a KV cache: the audio is projected once (`encode_audio`), and each step runs the adapter on the NEW token's embedding only --
-        the adapter is position-wise in the text and causal decoding over a cache equals full recomputation, so this is the reference's computation, not an
-        approximation of it.  bos_token_id: the start token, or a sequence of prompt ids; with a tokenizer both ids default to its bos (else eos) / eos ids
-        and the decoded string is returned, without one the ids are required and the generated ids are returned (EOS excluded, as the reference does).
-        do_sample: torch.multinomial(softmax(logits / temperature)) with `generator`, the reference's expression; else argmax (awt_op_select_tokens)."""
+    def generate_batch(self, waveforms, sampling_rate: int, max_new_tokens: int = 256, temperature: float = 0.7, do_sample: bool = True,
+                       generator: Optional[torch.Generator] = None, bos_token_id=None, eos_token_id: Optional[int] = None) -> list:
+        """model.py:293-344 with a KV cache, for a non-empty list of clips; one entry per clip: the decoded string with a tokenizer, else the generated ids
+        (EOS excluded, as the reference does).  The clips are decoded in groups of at most DECODE_ROWS: per group the audio tower runs once on the group's
+        list, the audio is projected once (`encode_audio`), and each step runs the adapter on the NEW tokens' embeddings [B, 1] only -- the adapter is
+        position-wise in the text and causal decoding over a cache equals full recomputation, so this is the reference's computation, not an approximation
+        of it -- then `prefill` (the prompt) or `step`, the token choice on [B, vocab], and ONE host read of the B ids.  Every row starts from the same
+        prompt.  A row that has produced EOS is finished: it is fed the EOS id from then on and what it produces is dropped; the loop ends when every row
+        is finished or at max_new_tokens.  bos_token_id: the start token, or a sequence of prompt ids; with a tokenizer both ids default to its bos (else
+        eos) / eos ids, without one they are required.  do_sample: torch.multinomial(softmax(logits / temperature)) with `generator`, the reference's
+        expression; else argmax (awt_op_select_tokens)."""
         from .generation import select_tokens
         tok, dec = self.tokenizer, self.text_decoder
+        waveforms = list(waveforms)
+        if not waveforms:
+            raise ValueError("generate_batch needs at least one clip")
         if bos_token_id is None and tok is not None:
             bos_token_id = tok.bos_token_id if tok.bos_token_id is not None else tok.eos_token_id
         if eos_token_id is None and tok is not None:
@@ -629,20 +640,36 @@ class MusicTranscriptionModel(nn.Module):
         if not prompt or max_new_tokens < 1:
             raise ValueError("generate needs at least one prompt token and max_new_tokens >= 1")
         dev, vocab = dec.get_input_embeddings().weight.device, dec.config.vocab_size
-        audio = self.audio_encoder([waveform], sampling_rate)
-        audio_kv = self.cross_attention_adapter.encode_audio(audio.float().to(dev))
-        cache = Qwen3Cache(dec.config, 1, len(prompt) + max_new_tokens - 1, dev)
-        ids = torch.tensor([prompt], dtype=torch.long, device=dev)
-        out = []
-        for n in range(max_new_tokens):
-            fused = self.cross_attention_adapter(self._embed(ids), audio_kv=audio_kv)
-            logits = dec.prefill(fused, cache) if n == 0 else dec.step(fused, cache)
-            if do_sample:
-                ids = torch.multinomial(torch.softmax(logits / temperature, dim=-1), 1, generator=generator)
-            else:
-                ids = select_tokens(logits, vocab)[1][:, :1]
-            nxt = int(ids.item())
-            if nxt == eos_token_id:
-                break
-            out.append(nxt)
-        return tok.decode(out, skip_special_tokens=True) if tok is not None else out
+        results = []
+        for g0 in range(0, len(waveforms), DECODE_ROWS):
+            group = waveforms[g0:g0 + DECODE_ROWS]
+            B = len(group)
+            audio = self.audio_encoder(group, sampling_rate)
+            audio_kv = self.cross_attention_adapter.encode_audio(audio.float().to(dev))
+            cache = Qwen3Cache(dec.config, B, len(prompt) + max_new_tokens - 1, dev)
+            ids = torch.tensor([prompt] * B, dtype=torch.long, device=dev)
+            out, done = [[] for _ in range(B)], [False] * B
+            for n in range(max_new_tokens):
+                fused = self.cross_attention_adapter(self._embed(ids), audio_kv=audio_kv)
+                logits = dec.prefill(fused, cache) if n == 0 else dec.step(fused, cache)
+                if do_sample:
+                    ids = torch.multinomial(torch.softmax(logits / temperature, dim=-1), 1, generator=generator)
+                else:
+                    ids = select_tokens(logits, vocab)[1][:, :1]
+                for b, nxt in enumerate(ids[:, 0].tolist()):               # the step's one host read
+                    if not done[b]:
+                        done[b] = nxt == eos_token_id
+                        if not done[b]:
+                            out[b].append(nxt)
+                if all(done):
+                    break
+                if any(done):
+                    ids = torch.where(torch.tensor(done, device=dev)[:, None], torch.full_like(ids, eos_token_id), ids)
+            results += out
+        return [tok.decode(o, skip_special_tokens=True) for o in results] if tok is not None else results
+
+    def generate(self, waveform, sampling_rate: int, max_new_tokens: int = 256, temperature: float = 0.7, do_sample: bool = True,
+                 generator: Optional[torch.Generator] = None, bos_token_id=None, eos_token_id: Optional[int] = None):
+        """`generate_batch` for one clip: the decoded string with a tokenizer, else the generated ids (EOS excluded)."""
+        return self.generate_batch([waveform], sampling_rate, max_new_tokens=max_new_tokens, temperature=temperature, do_sample=do_sample, generator=generator,
+                                   bos_token_id=bos_token_id, eos_token_id=eos_token_id)[0]

@@ -73,6 +73,15 @@ class PackedLinear:
                                             _lib.stream_handle()))
         return y
 
+    def forward_decode(self, x: torch.Tensor, resid: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`forward` for the 1 <= M <= 8 rows of incremental decoding (`awt_linear_decode`): one weight-streaming launch, no workspace, no plane split;
+        any other M raises.  Row m of the result does not depend on M."""
+        M = x.shape[0]
+        y = torch.empty((M, self.Np), dtype=torch.float32, device=x.device) if out is None else out
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().awt_linear_decode(_lib.ctx(x.device), self.handle, _lib.ptr(x), _lib.ptr(resid), _lib.ptr(y), M, _lib.stream_handle()))
+        return y
+
     def backward_input(self, dy: torch.Tensor) -> torch.Tensor:
         """dx [M, K] = dy [M, Np] W."""
         L = _lib.lib()

@@ -4,11 +4,15 @@
 what the reference does -- per generated token the audio is re-projected, the adapter runs over the whole text and all 28 layers run over the whole
 sequence without a cache (.charles/music2midi/model.py:314-341).  GPU box only.
 
-    python tools/music2midi_generate_bench.py [--tokens 256] [--rounds 3] [--precision bf16x3] [--out profiles/music2midi_generate_bench.json]
+    python tools/music2midi_generate_bench.py [--tokens 256] [--rounds 3] [--precision bf16x3] [--batch 1,8] [--parent-json FILE]
+                                              [--out profiles/music2midi_generate_bench.json]
     python tools/music2midi_generate_bench.py --trace-run      # the native generate alone, 64 tokens: the run to put under a kernel tracer
 
   generate   ms per generated token at batch 1 over `tokens` greedy tokens from one start token (EOS never matches, so every run has the full length)
+  batch      `--batch 1,8` (the default): beside batch 1, `generate_batch` of 8 clips (distinct audio, the same start token) as ms per step and clips x tokens / s
   prefill    ms for a 512-token prefill at B = 4: native `prefill` (last position's logits) / the torch decoder's full forward
+  parent     `--parent-json FILE`: the output line of the same command on the parent commit, on the same GPU; it is copied into the result, and the batch-1
+             figure is judged against it: lower by more than the larger max / min window spread of the two runs, or not
 Every figure is the median over `rounds` windows; native and torch windows alternate.  Where the time goes at Lq = 1 comes from the library's own event
 timing of its kernel classes (awt_prof_enable) over 16 further steps at the end of a 256-position cache, as ms per token and launches per token.
 """
@@ -87,6 +91,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--precision", default="bf16x3", choices=["bf16x3", "bf16"])
     ap.add_argument("--trace-run", action="store_true")
+    ap.add_argument("--batch", default="1,8", help="batch sizes of the native generate: 1 is always run; each further size B runs generate_batch on B clips")
+    ap.add_argument("--parent-json", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.manual_seed(0)
@@ -97,7 +103,10 @@ def main():
     adapter = CrossAttentionAdapter(AUDIO_DIM, cfg.hidden_size, 8, precision=a.precision).to(dev).eval()
     adapter.load_state_dict(ref_adapter.state_dict())
     audio = torch.randn(1, SA, AUDIO_DIM, device=dev)
-    model = MusicTranscriptionModel(lambda w, sr: audio, adapter, dec)
+    batches = sorted({int(b) for b in a.batch.split(",")} - {1})
+    more = torch.randn(max(batches + [1]) - 1, SA, AUDIO_DIM, device=dev, generator=torch.Generator(device=dev).manual_seed(1))   # the other clips' audio: its own generator
+    clips = torch.cat([audio, more])
+    model = MusicTranscriptionModel(lambda w, sr: clips[:len(w)], adapter, dec)
     sd = dict(dec.state_dict())
     start = 1
     native_gen = lambda n=a.tokens: model.generate(None, 16000, max_new_tokens=n, do_sample=False, bos_token_id=start, eos_token_id=-1)
@@ -117,6 +126,10 @@ def main():
 
     fns = {"native_generate_ms_per_token": (native_gen, a.tokens), "torch_fp32_full_recompute_generate_ms_per_token": (lambda: torch_generate(sd, cfg, ref_adapter, audio, start, a.tokens), a.tokens),
            "native_prefill_ms": (native_prefill, 1), "torch_fp32_prefill_ms": (torch_prefill, 1)}
+    batch_gen = lambda B, n=a.tokens: model.generate_batch([None] * B, 16000, max_new_tokens=n, do_sample=False, bos_token_id=start, eos_token_id=-1)
+    for B in batches:
+        fns[f"native_generate_batch{B}_ms_per_step"] = (lambda B=B: batch_gen(B), a.tokens)
+        batch_gen(B, 8)
     native_gen(8), torch_generate(sd, cfg, ref_adapter, audio, start, 8), native_prefill(), torch_prefill()          # warm-up of every timed shape ...
     outs, times = {}, {k: [] for k in fns}
     for r in range(a.rounds + 1):                                          # ... and one untimed round at full length
@@ -149,6 +162,18 @@ def main():
     _lib.prof_enable(False)
     state = bench.read_power_sysfs(pci=bench.device_pci_address(torch, torch.cuda.current_device()))
 
+    batch = {f"batch{B}": {"ms_per_step": res[f"native_generate_batch{B}_ms_per_step"],
+                           "clips_x_tokens_per_s": round(B * 1e3 / res[f"native_generate_batch{B}_ms_per_step"], 1),
+                           "clip_0_tokens_equal_batch_1": bool(outs[f"native_generate_batch{B}_ms_per_step"][0] == outs["native_generate_ms_per_token"])}
+             for B in batches}
+    parent, verdict = None, None
+    if a.parent_json:
+        parent = json.loads(open(a.parent_json).read())
+        key = "native_generate_ms_per_token"
+        p_ms, t_ms = parent["results"][key], res[key]
+        margin = max(parent["max_over_min_of_windows"][key], spread[key])
+        verdict = {"parent_ms_per_token": p_ms, "this_ms_per_token": t_ms, "parent_over_this": round(p_ms / t_ms, 3), "larger_max_over_min_of_the_two_runs": margin,
+                   "condition": "this < parent / larger spread", "met": bool(t_ms < p_ms / margin)}
     same = sum(int(p == q) for p, q in zip(outs["native_generate_ms_per_token"], outs["torch_fp32_full_recompute_generate_ms_per_token"]))
     pre_err = float((outs["native_prefill_ms"] - outs["torch_fp32_prefill_ms"]).abs().max())
     line = json.dumps({"metric": f"music2midi inference at Qwen3-0.6B's shape (28 layers, hidden 1024, 16 / 8 heads, vocab 151936; adapter audio_dim {AUDIO_DIM}, {SA} encoder "
@@ -156,6 +181,7 @@ def main():
                                  f"L {PREFILL_L}) beside a torch fp32 restatement of the reference's full-recompute loop on the same GPU; medians of alternating windows, host clock "
                                  "around a device synchronise",
                        "results": res, "max_over_min_of_windows": spread, "rounds": a.rounds, "tokens": a.tokens,
+                       "native_generate_batch": batch, "batch_1_against_the_parent_commit": verdict, "parent_commit": parent,
                        "native_kernel_classes_per_step_at_cache_length_240_to_256": classes,
                        "note_kernel_classes": "gemm = the 4 layer GEMMs x 28 + lm_head + the adapter's linears; attention = awt_op_causal_attention x 28 + the adapter's "
                                               "cross-attention; layernorm = RMSNorm x 57 + the adapter's LayerNorms; other = qk_norm_rope, silu_mul x 28, GELU, argmax",
