@@ -288,15 +288,14 @@ int launch_t(const AttnArgs& a, hipStream_t s) {
 static int g_attn_qt = 0;   // awt_tuning_set("attn_qt"): 0 = the grid rule below, 1 / 2 = that many query tiles per wave
 void awt_attn_force_qt(int v) { g_attn_qt = v; }
 
-int launch_attention(awt_ctx* c, const bf16_t* q_hi, const bf16_t* q_lo, const bf16_t* k_hi, const bf16_t* k_lo,
-                     const bf16_t* v_hi, const bf16_t* v_lo, bf16_t* o_hi, bf16_t* o_lo, float* o_f32, float* lse, int B, int H,
+int launch_attention(awt_ctx* c, const PlanePair& q, const PlanePair& k, const PlanePair& v, const PlanePair& o, float* o_f32, float* lse, int B, int H,
                      int S, int prec, hipStream_t s) {
   AWT_REQUIRE(B > 0 && H > 0 && S > 0, AWT_ERR_INVALID, "attention: bad shape");
   AWT_REQUIRE(prec == PREC_BF16 || prec == PREC_F16 || prec == PREC_BF16X3 || prec == PREC_F16X3, AWT_ERR_INVALID, "attention: precision must be bf16 (1), fp16 (2), bf16x3 (3) or fp16x3 (4) here");
   const int terms = prec_products(prec);
-  AWT_REQUIRE(q_hi && k_hi && v_hi && (o_hi || o_f32), AWT_ERR_INVALID, "attention: null plane");
-  AWT_REQUIRE(terms == 1 || (q_lo && k_lo && v_lo), AWT_ERR_INVALID, "attention: lo planes required for terms == 3");
-  AttnArgs a{q_hi, q_lo, k_hi, k_lo, v_hi, v_lo, o_hi, o_lo, o_f32, lse, B, H, S};
+  AWT_REQUIRE(q.hi && k.hi && v.hi && (o.hi || o_f32), AWT_ERR_INVALID, "attention: null plane");
+  AWT_REQUIRE(terms == 1 || (q.lo && k.lo && v.lo), AWT_ERR_INVALID, "attention: lo planes required for terms == 3");
+  AttnArgs a{q.hi, q.lo, k.hi, k.lo, v.hi, v.lo, o.hi, o.lo, o_f32, lse, B, H, S};
   ProfScope prof(c, AWT_PROF_ATTENTION, s, 4.0 * (double)B * H * (double)S * S * 64);
   // 512 workgroup slots (256 CUs x 2): a launch lasts ceil(workgroups / 512) rounds.  One query tile per wave doubles the
   // workgroups at ~0.55 of the duration each (less K / V amortisation); take it when that is fewer round-equivalents --

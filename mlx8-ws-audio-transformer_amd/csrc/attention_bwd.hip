@@ -277,18 +277,16 @@ int launch_mode(const BwdArgs& a, hipStream_t s) {
 
 }  // namespace
 
-int launch_attention_bwd(awt_ctx* c, const bf16_t* q_hi, const bf16_t* q_lo, const bf16_t* k_hi, const bf16_t* k_lo,
-                         const bf16_t* v_hi, const bf16_t* v_lo, const bf16_t* o_hi, const bf16_t* o_lo, const bf16_t* do_hi,
-                         const bf16_t* do_lo, const float* lse2, float* delta, bf16_t* g_hi, bf16_t* g_lo, int B, int H, int S,
-                         float qscale, int terms, int grad_terms, hipStream_t s) {
+int launch_attention_bwd(awt_ctx* c, const PlanePair& q, const PlanePair& k, const PlanePair& v, const PlanePair& o, const PlanePair& d_o, const float* lse2,
+                         float* delta, const PlanePair& g, int B, int H, int S, float qscale, int terms, int grad_terms, hipStream_t s) {
   AWT_REQUIRE(B > 0 && H > 0 && S > 0, AWT_ERR_INVALID, "attention_bwd: bad shape");
   AWT_REQUIRE(grad_terms == terms || (terms == 3 && grad_terms == 1), AWT_ERR_INVALID, "attention_bwd: grad_terms must equal terms, or be 1 with terms 3");
   AWT_REQUIRE(terms == 1 || terms == 3, AWT_ERR_INVALID, "attention_bwd: terms must be 1 or 3");
-  AWT_REQUIRE(q_hi && k_hi && v_hi && o_hi && do_hi && lse2 && delta && g_hi, AWT_ERR_INVALID, "attention_bwd: null argument");
-  AWT_REQUIRE(terms == 1 || (q_lo && k_lo && v_lo && o_lo && do_lo && g_lo), AWT_ERR_INVALID, "attention_bwd: lo planes required");
+  AWT_REQUIRE(q.hi && k.hi && v.hi && o.hi && d_o.hi && lse2 && delta && g.hi, AWT_ERR_INVALID, "attention_bwd: null argument");
+  AWT_REQUIRE(terms == 1 || (q.lo && k.lo && v.lo && o.lo && d_o.lo && g.lo), AWT_ERR_INVALID, "attention_bwd: lo planes required");
   ProfScope prof(c, AWT_PROF_ATTENTION_BWD, s, 14.0 * (double)B * H * (double)S * S * 64);   // 7 products (s and dp are formed twice)
   // delta = rowsum(dO * O) is formed by the dq launch (its lanes hold the dO rows already) and read back by the dk / dv launch that follows it on the stream
-  BwdArgs a{q_hi, q_lo, k_hi, k_lo, v_hi, v_lo, do_hi, do_lo, lse2, delta, o_hi, terms == 3 ? o_lo : nullptr, g_hi, terms == 3 ? g_lo : nullptr, B, H, S, qscale};
+  BwdArgs a{q.hi, q.lo, k.hi, k.lo, v.hi, v.lo, d_o.hi, d_o.lo, lse2, delta, o.hi, terms == 3 ? o.lo : nullptr, g.hi, terms == 3 ? g.lo : nullptr, B, H, S, qscale};
   int rc = terms == 1 ? launch_mode<1, MODE_DQ, 1>(a, s) : (grad_terms == 3 ? launch_mode<3, MODE_DQ, 3>(a, s) : launch_mode<3, MODE_DQ, 1>(a, s));
   if (rc) return rc;
   return terms == 1 ? launch_mode<1, MODE_DKV, 1>(a, s) : (grad_terms == 3 ? launch_mode<3, MODE_DKV, 3>(a, s) : launch_mode<3, MODE_DKV, 1>(a, s));

@@ -603,15 +603,14 @@ void awt_attn_force_shape(int v) { g_attn_shape = v; }
 // whether v's e4m3 planes must be written: the form reads them (which does not depend on the shape), or the call is a training one
 bool attention_f16f8_reads_v8(bool with_lse) { return with_lse || f16f8_form(with_lse, 1, 1, 1).pv8; }
 
-int launch_attention_f16f8(awt_ctx* c, const F8Planes& q, const F8Planes& k, const F8Planes& v, const F8Planes& o, float* o_f32,
-                           float* lse, int B, int H, int S, hipStream_t s, char* o_ilv) {
+int launch_attention_f16f8(awt_ctx* c, const Act& q, const Act& k, const Act& v, const Act& o, float* o_f32, float* lse, int B, int H, int S, hipStream_t s) {
   AWT_REQUIRE(B > 0 && H > 0 && S > 0, AWT_ERR_INVALID, "attention: bad shape");
   AWT_REQUIRE(q.p16 && q.hi8 && q.lo8 && k.p16 && k.hi8 && k.lo8 && v.p16 && v.hi8 && v.lo8, AWT_ERR_INVALID, "attention (f16f8): null plane");
   // (v.hi8 / v.lo8 are only dereferenced by the forms attention_f16f8_reads_v8() names; the encoder does not fill them otherwise)
-  AWT_REQUIRE(o_f32 || o_ilv || (o.p16 && o.lo8), AWT_ERR_INVALID, "attention (f16f8): null output plane (hi8 may be null: not consumed)");
-  AWT_REQUIRE(!o_ilv || (H * 64) % 64 == 0, AWT_ERR_INVALID, "attention (f16f8): split-line output needs whole 64-element line pairs per row");
+  AWT_REQUIRE(o_f32 || o.ilv || (o.p16 && o.lo8), AWT_ERR_INVALID, "attention (f16f8): null output plane (hi8 may be null: not consumed)");
+  AWT_REQUIRE(!o.ilv || (H * 64) % 64 == 0, AWT_ERR_INVALID, "attention (f16f8): split-line output needs whole 64-element line pairs per row");
   Attn8Args a{q.p16, k.p16, v.p16, q.hi8, q.lo8, k.hi8, k.lo8, v.hi8, v.lo8, o.p16, o.hi8, o.lo8, o_f32, lse, B, H, S};
-  a.o_ilv = o_f32 ? nullptr : o_ilv;
+  a.o_ilv = o_f32 ? nullptr : o.ilv;
   ProfScope prof(c, AWT_PROF_ATTENTION, s, 4.0 * (double)B * H * (double)S * S * 64);
   const F8Form f = f16f8_form(lse != nullptr, B, H, S);
   if (f.pv8) return f.nw == 8 ? launch_pipe<8, true>(a, s) : launch_pipe<4, true>(a, s);

@@ -249,6 +249,9 @@ struct awt_encoder {
   struct GradEntry { std::string name; size_t offset; int64_t shape[3]; int rank; };
   std::vector<GradEntry> glayout;  // the flat gradient buffer: the non-layer parameters, then one contiguous block per layer, layers in order
   size_t g_head = 0, g_per_layer = 0;
+  // where the backward pass writes, filled with glayout by build_grad_layout: the head's entries from the buffer's start (lnf: layer_norm.weight, its
+  // bias follows), a layer's from the start of its block (qkvw: q | k | v weights; ln1 / ln2: weight, then bias)
+  struct GradOffsets { size_t c1w, c1b, c2w, c2b, lnf, qkvw, qb, vb, ow, ob, ln1, f1w, f1b, f2w, f2b, ln2; } goff{};
 };
 
 namespace {
@@ -259,11 +262,12 @@ int dev_alloc(awt_encoder* e, void** p, size_t bytes) {
   e->allocs.push_back(*p);
   return AWT_OK;
 }
-int alloc_planes(awt_encoder* e, Planes* pl, int64_t rows, int64_t ld) {
+// the planes of a [rows, ld] weight in the operand format of `prec` (the forward's, or PREC_F16F8 for the f16f8 MLP of a split-bf16 training step)
+int alloc_planes(awt_encoder* e, Planes* pl, int64_t rows, int64_t ld, int prec) {
   pl->rows = rows; pl->ld = ld;
   int rc = dev_alloc(e, (void**)&pl->hi, (size_t)rows * ld * 2); if (rc) return rc;
-  if (e->planes == 2) { rc = dev_alloc(e, (void**)&pl->lo, (size_t)rows * ld * 2); if (rc) return rc; }
-  if (e->prec == PREC_F16F8) {
+  if (prec_products(prec) == 3) { rc = dev_alloc(e, (void**)&pl->lo, (size_t)rows * ld * 2); if (rc) return rc; }
+  if (prec == PREC_F16F8) {
     pl->x8 = (uint8_t*)pl->lo + (size_t)rows * ld;
     pl->s_rows = (rows + 255) / 256 * 256;
     rc = dev_alloc(e, (void**)&pl->s16, (size_t)pl->s_rows * ld * 2); if (rc) return rc;
@@ -271,68 +275,86 @@ int alloc_planes(awt_encoder* e, Planes* pl, int64_t rows, int64_t ld) {
   }
   return AWT_OK;
 }
-int alloc_planes_f8(awt_encoder* e, Planes* pl, int64_t rows, int64_t ld) {   // fp16 plane + the two e4m3 planes, whatever the forward precision
-  pl->rows = rows; pl->ld = ld;
-  int rc = dev_alloc(e, (void**)&pl->hi, (size_t)rows * ld * 2); if (rc) return rc;
-  rc = dev_alloc(e, (void**)&pl->lo, (size_t)rows * ld * 2); if (rc) return rc;
-  pl->x8 = (uint8_t*)pl->lo + (size_t)rows * ld;
-  pl->s_rows = (rows + 255) / 256 * 256;
-  rc = dev_alloc(e, (void**)&pl->s16, (size_t)pl->s_rows * ld * 2); if (rc) return rc;
-  rc = dev_alloc(e, (void**)&pl->s8, (size_t)pl->s_rows * ld * 2); if (rc) return rc;
-  return AWT_OK;
-}
 int alloc_linear(awt_encoder* e, Linear* l, int N, int K) {
   l->N = N; l->K = K;
-  int rc = alloc_planes(e, &l->w, N, K); if (rc) return rc;
+  int rc = alloc_planes(e, &l->w, N, K, e->prec); if (rc) return rc;
   return dev_alloc(e, (void**)&l->bias, (size_t)N * 4);
 }
 int alloc_lora(awt_encoder* e, LoraGroup* g, int slots, int K_in, int N_out) {
   g->active = true;
   g->kp = (int)(((int64_t)slots * e->cfg.lora_rank + 63) / 64 * 64);
-  int rc = alloc_planes(e, &g->a, 128, K_in); if (rc) return rc;
-  rc = alloc_planes(e, &g->b, N_out, g->kp); if (rc) return rc;
+  int rc = alloc_planes(e, &g->a, 128, K_in, e->prec); if (rc) return rc;
+  rc = alloc_planes(e, &g->b, N_out, g->kp, e->prec); if (rc) return rc;
   if (e->cfg.training) {
-    rc = alloc_planes(e, &g->bT, 128, N_out); if (rc) return rc;
-    rc = alloc_planes(e, &g->aT, K_in, g->kp); if (rc) return rc;
+    rc = alloc_planes(e, &g->bT, 128, N_out, e->prec); if (rc) return rc;
+    rc = alloc_planes(e, &g->aT, K_in, g->kp, e->prec); if (rc) return rc;
   }
   return AWT_OK;
 }
+// src [N, C, taps] fp32 into rows row_off .., columns col_off .. of `pl` in the operand format of `prec` (launch_pack_weight); flag: see probe_exact16
+int pack(awt_ctx* c, const float* src, Planes& pl, int N, int C, int taps, int row_off, int col_off, int prec, hipStream_t s, int* flag = nullptr) {
+  return launch_pack_weight(c, src, N, C, taps, pl.ld, row_off, col_off, 1.0f, pl.hi, pl.lo, pl.x8, prec, s, flag, pl.s16, pl.s8);
+}
+// pack() of a plain [N, K] block that also finds out whether the matrix is fp16-exact (checkpoints stored in half precision), which lets the GEMM drop one
+// cross term: device flag `which` of `flags` is reset, the pack sets it at the first weight that is not, and pl.exact16 = none of the `nflags` flags
+// (one per separately uploaded row block) is set.  Synchronises the stream: upload time only.  `who` names the caller in the error texts.
+int probe_exact16(awt_ctx* c, const char* who, const float* src, Planes& pl, int N, int K, int row_off, int prec, int* flags, int which, int nflags, hipStream_t s) {
+  int host[4] = {0, 0, 0, 0};
+  if (hipMemsetAsync(flags + which, 0, sizeof(int), s) != hipSuccess) return awt_fail(AWT_ERR_HIP, std::string(who) + ": flag reset failed");
+  int rc = pack(c, src, pl, N, K, 1, row_off, 0, prec, s, flags + which); if (rc) return rc;
+  if (hipMemcpyAsync(host, flags, nflags * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return awt_fail(AWT_ERR_HIP, std::string(who) + ": flag read-back failed");
+  pl.exact16 = !(host[0] | host[1] | host[2] | host[3]);
+  return AWT_OK;
+}
+
+// conv-phase planes for Mt = clips x frames rows: the im2col rows [Mt, conv1_k], conv1's output [Mt, d] and, for train_base (`keep_pre1`), conv1's
+// pre-activation [Mt, d].  The one carve of them: the inference workspace, its compact-stem form and the training buffer all call it.
+struct ConvPlanes { PlanePair a1, h1, pre1; };
+ConvPlanes take_conv_planes(const awt_encoder* e, Carver& cv, size_t Mt, bool keep_pre1) {
+  const size_t d = e->cfg.d_model;
+  ConvPlanes p;
+  p.a1 = take_planes(cv, Mt * conv1_k(e->cfg.n_mels), e->planes);
+  p.h1 = take_planes(cv, Mt * d, e->planes);
+  if (keep_pre1) p.pre1 = take_planes(cv, Mt * d, e->planes);
+  return p;
+}
 
 struct Workspace {  // per-chunk buffers carved from the caller's workspace
-  float* x; bf16_t *ln[2], *qkv[2], *att[2], *ff[2], *u[2], *a1[2], *h1[2];
+  float* x; PlanePair ln, qkv, att, ff, u; ConvPlanes conv;
   size_t bytes;
 };
 
 Workspace carve(const awt_encoder* e, char* base, int Bc) {
   const awt_encoder_cfg& c = e->cfg;
-  const size_t P = e->planes, S = c.n_ctx, T = 2 * S, d = c.d_model, f = c.ffn_dim;
+  const size_t S = c.n_ctx, T = 2 * S, d = c.d_model, f = c.ffn_dim;
   const size_t M = (size_t)Bc * S, Mt = (size_t)Bc * T;
+  const int P = e->planes;
   Workspace w{};
   Carver cv(base);
   w.x = cv.take<float>(M * d * 4);
-  for (size_t p = 0; p < P; ++p) w.ln[p] = cv.take<bf16_t>(M * d * 2);
-  for (size_t p = 0; p < P; ++p) w.u[p] = cv.take<bf16_t>(M * 128 * 2);
+  w.ln = take_planes(cv, M * d, P);
+  w.u = take_planes(cv, M * 128, P);
   // layer-phase buffers; the conv-phase buffers (im2col rows and conv1 output) alias the same region
   const size_t layer_start = cv.off;
-  for (size_t p = 0; p < P; ++p) w.qkv[p] = cv.take<bf16_t>(3 * M * d * 2);
-  for (size_t p = 0; p < P; ++p) w.att[p] = cv.take<bf16_t>(M * d * 2);
-  for (size_t p = 0; p < P; ++p) w.ff[p] = cv.take<bf16_t>(M * f * 2);
+  w.qkv = take_planes(cv, 3 * M * d, P);
+  w.att = take_planes(cv, M * d, P);
+  w.ff = take_planes(cv, M * f, P);
   const size_t layer_end = cv.off;
   cv.off = layer_start;
-  for (size_t p = 0; p < P; ++p) w.a1[p] = cv.take<bf16_t>(Mt * conv1_k(c.n_mels) * 2);
-  for (size_t p = 0; p < P; ++p) w.h1[p] = cv.take<bf16_t>(Mt * d * 2);
+  w.conv = take_conv_planes(e, cv, Mt, false);
   w.bytes = std::max(cv.off, layer_end);
   // the ping-pong GEMM reads whole 256-row panels of its activation: up to 255 rows past the last buffer's end (never stored)
   if (e->prec == PREC_F16F8 && !c.training) w.bytes += align_up((size_t)256 * std::max(f, (size_t)conv1_k(c.n_mels)) * 4);
   return w;
 }
 
-// the two 2-byte planes of an activation buffer of `elems` elements as operand planes of precision `prec`
-Act make_act(bf16_t* p0, bf16_t* p1, size_t elems, int prec) {
+// the one view of a buffer's plane pair (`elems` elements) as operand planes of precision `prec`; made once where the buffer is named
+Act make_act(const PlanePair& p, size_t elems, int prec) {
   Act a;
-  a.p16 = p0;
-  if (prec == PREC_F16F8) { a.hi8 = (uint8_t*)p1; a.lo8 = a.hi8 ? a.hi8 + elems : nullptr; }
-  else a.lo16 = p1;
+  a.p16 = p.hi;
+  if (prec == PREC_F16F8) { a.hi8 = (uint8_t*)p.lo; a.lo8 = a.hi8 ? a.hi8 + elems : nullptr; }
+  else a.lo16 = p.lo;
   return a;
 }
 Act act_offset(const Act& a, int64_t elems) {
@@ -345,7 +367,7 @@ Act act_offset(const Act& a, int64_t elems) {
 }
 void set_out(GemmOut& o, const Act& a) { o.hi = a.p16; o.lo = a.lo16; o.hi8 = a.hi8; o.lo8 = a.lo8; o.ilv = a.ilv; }
 // the same buffer pair as one split-line image (Act::ilv): the two 2-byte planes are adjacent, 4 bytes per element in all
-Act make_ilv(bf16_t* p0) { Act a; a.ilv = (char*)p0; return a; }
+Act make_ilv(const PlanePair& p) { Act a; a.ilv = (char*)p.hi; return a; }
 
 GemmSeg seg_plain(const Act& a, int64_t lda, const Planes& w, int64_t wcol, int K, int M) {
   GemmSeg s = gemm_seg_plain(a.p16, a.lo16, lda, w.hi, w.lo, (int)(w.ld / 32), (int)(wcol / 32), K, M);
@@ -355,22 +377,16 @@ GemmSeg seg_plain(const Act& a, int64_t lda, const Planes& w, int64_t wcol, int 
   s.ws16 = w.s16; s.ws8 = w.s8; s.ws_rows = (int)w.s_rows;
   return s;
 }
-GemmSeg seg_plain(const bf16_t* a_hi, const bf16_t* a_lo, int64_t lda, const Planes& w, int64_t wcol, int K, int M) {   // bf16 planes (backward pass)
-  Act a; a.p16 = const_cast<bf16_t*>(a_hi); a.lo16 = const_cast<bf16_t*>(a_lo);
-  return seg_plain(a, lda, w, wcol, K, M);
-}
 
-// y = x W^T (+ LoRA: [x | u] [W | B]^T with u = (alpha / r) x A^T) with the given epilogue
-int linear_with_lora(awt_encoder* e, bf16_t* const u[2], bf16_t* const in[2], int64_t ld_in, const Linear& lin, const LoraGroup& lg,
+// y = x W^T (+ LoRA: [x | u] [W | B]^T with u = (alpha / r) x A^T) with the given epilogue; ain: x [M, ld_in], au: the adapter group's u [M, 128]
+int linear_with_lora(awt_encoder* e, const Act& au, const Act& ain, int64_t ld_in, const Linear& lin, const LoraGroup& lg,
                      int M, GemmEpilogue epi, GemmOut out, hipStream_t s) {
   const int terms = e->prec;
-  const Act ain = make_act(in[0], in[1], (size_t)M * ld_in, terms);
   GemmSeg segs[2];
   int nseg = 1;
   segs[0] = seg_plain(ain, ld_in, lin.w, 0, lin.K, M);
   if (lg.active) {
     GemmSeg us = seg_plain(ain, ld_in, lg.a, 0, lin.K, M);
-    const Act au = make_act(u[0], u[1], (size_t)M * 128, terms);
     GemmOut uo{};
     set_out(uo, au); uo.ldo = lg.kp; uo.n_valid = lg.kp;
     uo.scale = e->cfg.lora_alpha / (float)e->cfg.lora_rank;
@@ -383,9 +399,20 @@ int linear_with_lora(awt_encoder* e, bf16_t* const u[2], bf16_t* const in[2], in
   return launch_gemm(e->ctx, M, lin.N, segs, nseg, terms, epi, out, s);
 }
 
+// The mirror image in the backward pass: dX [M, N] = dY W (+ the adapter term: [dY | du] [W^T | (alpha / r) A^T]), dY [M, ld] against wT = W^T [N, ld];
+// du is the group's gradient as group_backward left it.  `prec`: the products of the gradient contractions.
+int linear_backward_input(awt_encoder* e, const Act& dY, int64_t ld, const Planes& wT, const LoraGroup& lg, const Act& du, int N, GemmEpilogue epi, GemmOut out,
+                          int M, int prec, hipStream_t s) {
+  GemmSeg sg[2];
+  sg[0] = seg_plain(dY, ld, wT, 0, (int)ld, M);
+  if (lg.active) sg[1] = seg_plain(du, lg.kp, lg.aT, 0, lg.kp, M);
+  out.ldo = N; out.n_valid = N;
+  return launch_gemm(e->ctx, M, N, sg, lg.active ? 2 : 1, prec, epi, out, s);
+}
+
 // y = x W^T on the persistent ping-pong kernel: x as split lines (make_ilv), W's packed image; no adapter
-int linear_pp(awt_encoder* e, bf16_t* in0, const Linear& lin, int M, GemmEpilogue epi, GemmOut out, hipStream_t s) {
-  GemmSeg sg = seg_plain(make_ilv(in0), lin.K, lin.w, 0, lin.K, M);
+int linear_pp(awt_encoder* e, const Act& in_ilv, const Linear& lin, int M, GemmEpilogue epi, GemmOut out, hipStream_t s) {
+  GemmSeg sg = seg_plain(in_ilv, lin.K, lin.w, 0, lin.K, M);
   out.bias = lin.bias;
   out.n_valid = lin.N;
   return launch_gemm_pp(e->ctx, M, lin.N, sg, epi, out, s);
@@ -407,29 +434,30 @@ bool use_pp(const awt_encoder* e, const Linear& lin, const LoraGroup& lg, int M,
 // Training: one set per layer, kept for awt_encoder_backward.
 struct LayerBufs {
   float *x_in, *x_mid, *x_out;            // residual stream before the layer, after attention, after the MLP
-  bf16_t *ln1[2], *qkv[2], *att[2], *ln2[2], *pre[2], *ff[2], *u[2];
-  bf16_t *uo[2], *u1[2], *u2[2];          // u = (alpha / r) x A^T of the out_proj / fc1 / fc2 adapters (inference: alias u; training: kept)
+  PlanePair ln1, qkv, att, ln2, pre, ff, u;
+  PlanePair uo, u1, u2;                   // u = (alpha / r) x A^T of the out_proj / fc1 / fc2 adapters (inference: alias u; training: kept)
   float* lse;                             // [B, H, S] or null
 };
 
 struct TrainWs {   // carved from the caller's `saved` buffer
   std::vector<LayerBufs> layer;
-  bf16_t *a1[2], *h1[2], *ff[2];          // conv-phase scratch, MLP hidden (not needed by the q/k/v-adapter backward)
-  bf16_t* pre1[2];                        // train_base: conv1's pre-activation [B * T, d] (a1 and h1 then outlive the forward as well)
+  // conv-phase scratch (train_base: with conv1's pre-activation pre1 [B * T, d]; a1 and h1 then outlive the forward as well)
+  ConvPlanes conv;
+  PlanePair ff;                           // MLP hidden (not needed by the q/k/v-adapter backward)
   float* x_final;
   // backward scratch
   float *dx_a, *dx_b, *dln, *delta, *partial;
-  bf16_t *dxp[2], *dpre[2], *datt[2], *dqkv[2], *du[2];
+  PlanePair dxp, dpre, datt, dqkv, du;
   size_t partial_bytes, bytes;
 };
 
 TrainWs carve_train(const awt_encoder* e, char* base, int B) {
   const awt_encoder_cfg& c = e->cfg;
-  const size_t P = e->planes, S = c.n_ctx, T = 2 * S, d = c.d_model, f = c.ffn_dim, H = c.n_heads;
+  const size_t S = c.n_ctx, T = 2 * S, d = c.d_model, f = c.ffn_dim, H = c.n_heads;
   const size_t M = (size_t)B * S, Mt = (size_t)B * T;
   TrainWs w{};
   Carver cv(base);
-  auto planes = [&](bf16_t* (&dst)[2], size_t elems) { dst[0] = dst[1] = nullptr; for (size_t p = 0; p < P; ++p) dst[p] = cv.take<bf16_t>(elems * 2); };
+  auto planes = [&](size_t elems) { return take_planes(cv, elems, e->planes); };
   w.layer.resize(c.n_layers);
   float* x = cv.take<float>(M * d * 4);
   for (int li = 0; li < c.n_layers; ++li) {
@@ -438,28 +466,27 @@ TrainWs carve_train(const awt_encoder* e, char* base, int B) {
     L.x_mid = cv.take<float>(M * d * 4);
     L.x_out = cv.take<float>(M * d * 4);
     x = L.x_out;
-    planes(L.ln1, M * d); planes(L.qkv, 3 * M * d); planes(L.att, M * d); planes(L.ln2, M * d); planes(L.pre, M * f);
-    planes(L.u, M * 128);
+    L.ln1 = planes(M * d); L.qkv = planes(3 * M * d); L.att = planes(M * d); L.ln2 = planes(M * d); L.pre = planes(M * f);
+    L.u = planes(M * 128);
     const bool has_o = e->layers[li].lo_.active, has_1 = e->layers[li].l1.active, has_2 = e->layers[li].l2.active;
-    if (has_o) planes(L.uo, M * 128); else { L.uo[0] = L.u[0]; L.uo[1] = L.u[1]; }
-    if (has_1) planes(L.u1, M * 128); else { L.u1[0] = L.u[0]; L.u1[1] = L.u[1]; }
-    if (has_2) { planes(L.u2, M * 128); planes(L.ff, M * f); } else { L.u2[0] = L.u[0]; L.u2[1] = L.u[1]; L.ff[0] = L.ff[1] = nullptr; }
-    if (e->train_base) planes(L.ff, M * f);   // fc2's weight gradient contracts d(x_out) with the fc2 input of this layer
+    L.uo = has_o ? planes(M * 128) : L.u;
+    L.u1 = has_1 ? planes(M * 128) : L.u;
+    L.u2 = has_2 ? planes(M * 128) : L.u;
+    if (has_2) L.ff = planes(M * f);
+    if (e->train_base) L.ff = planes(M * f);   // fc2's weight gradient contracts d(x_out) with the fc2 input of this layer
     L.lse = cv.take<float>((size_t)B * H * S * 4);
   }
   w.x_final = x;
-  if (e->train_base) w.ff[0] = w.ff[1] = nullptr;   // every layer keeps its own fc2 input in this mode
-  else planes(w.ff, M * f);
+  if (!e->train_base) w.ff = planes(M * f);   // train_base: every layer keeps its own fc2 input
   // conv-phase scratch aliases the backward scratch (disjoint in time); train_base: the conv stem's backward reads it, so it is kept
-  w.pre1[0] = w.pre1[1] = nullptr;
-  if (e->train_base) { planes(w.a1, Mt * conv1_k(e->cfg.n_mels)); planes(w.h1, Mt * d); planes(w.pre1, Mt * d); }
+  if (e->train_base) w.conv = take_conv_planes(e, cv, Mt, true);
   const size_t mark = cv.off;
-  if (!e->train_base) { planes(w.a1, Mt * conv1_k(e->cfg.n_mels)); planes(w.h1, Mt * d); }
+  if (!e->train_base) w.conv = take_conv_planes(e, cv, Mt, false);
   const size_t conv_end = cv.off;
   cv.off = mark;
   w.dx_a = cv.take<float>(M * d * 4); w.dx_b = cv.take<float>(M * d * 4); w.dln = cv.take<float>(M * d * 4);
   w.delta = cv.take<float>((size_t)B * H * S * 4);
-  planes(w.dxp, M * d); planes(w.dpre, M * f); planes(w.datt, M * d); planes(w.dqkv, 3 * M * d); planes(w.du, M * 128);
+  w.dxp = planes(M * d); w.dpre = planes(M * f); w.datt = planes(M * d); w.dqkv = planes(3 * M * d); w.du = planes(M * 128);
   w.partial_bytes = outer_reduce_partial_bytes((int)M, c.lora_rank > 0 ? c.lora_rank : 1, 1024);   // Y blocks are reduced in chunks of <= 1024 columns
   if (e->train_base) {   // slab partials of the weight-gradient GEMMs (qkv, out_proj, fc1, fc2, a conv2 tap, a conv1 tap) and of the bias / LayerNorm reductions
     const int Mi = (int)M, Mti = (int)Mt, di = (int)d, fi = (int)f;
@@ -469,7 +496,7 @@ TrainWs carve_train(const awt_encoder* e, char* base, int B) {
   }
   w.partial = cv.take<float>(w.partial_bytes);
   w.bytes = std::max(cv.off, conv_end);
-  for (int li = 0; li < c.n_layers; ++li) for (int p = 0; p < 2; ++p) if (!w.layer[li].ff[p]) w.layer[li].ff[p] = w.ff[p];   // kept per layer only under an fc2 adapter
+  for (LayerBufs& L : w.layer) if (!L.ff.hi) L.ff = w.ff;   // kept per layer only under an fc2 adapter (or train_base)
   return w;
 }
 
@@ -479,21 +506,22 @@ TrainWs carve_train(const awt_encoder* e, char* base, int B) {
 // g's last two rows over positions Sc - 1 .. S - 1 while it adds the positional table.  a1 / h1 are then planes of Bc * Tc rows.  Bit-identical to the full
 // stem: the same kernels run (GemmOut::m_pick: chosen as for the full row count), a row's dot products do not depend on the tile it lands in, conv2's
 // epilogue adds a zero row (rows_pos = 1) where the full stem adds pos -- gelu + 0 is gelu -- and the expand kernel makes that same fp32 add afterwards.
-int conv_stem(awt_encoder* e, const float* mel, int Bc, bf16_t* const a1[2], bf16_t* const h1[2], float* x, hipStream_t s, bf16_t* const* pre1 = nullptr,
-              int Sc = 0, float* g = nullptr) {
+// cp: the conv planes carved for those rows (take_conv_planes); with cp.pre1 (train_base) conv1's pre-activation is kept there.
+int conv_stem(awt_encoder* e, const float* mel, int Bc, const ConvPlanes& cp, float* x, hipStream_t s, int Sc = 0, float* g = nullptr) {
   const awt_encoder_cfg& c = e->cfg;
   const int S = c.n_ctx, T = 2 * S, d = c.d_model, terms = e->prec;
-  const bool compact = Sc > 0 && Sc < S && g && !pre1;
+  const bool keep_pre1 = cp.pre1.hi != nullptr;
+  const bool compact = Sc > 0 && Sc < S && g && !keep_pre1;
   const int So = compact ? Sc : S, To = 2 * So;       // positions and frames computed per clip
   const int M = Bc * So, Mt = Bc * To;
   const int k1 = conv1_k(c.n_mels);
-  const Act aa1 = make_act(a1[0], a1[1], (size_t)Mt * k1, terms), ah1 = make_act(h1[0], h1[1], (size_t)Mt * d, terms);
+  const Act aa1 = make_act(cp.a1, (size_t)Mt * k1, terms), ah1 = make_act(cp.h1, (size_t)Mt * d, terms);
   int rc = launch_im2col_conv1(e->ctx, mel, Bc, c.n_mels, T, To, k1, aa1, terms, s); if (rc) return rc;
   {
     GemmSeg sg = seg_plain(aa1, k1, e->conv1.w, 0, k1, Mt);
     GemmOut o{}; set_out(o, ah1); o.ldo = d; o.bias = e->conv1.bias; o.n_valid = d; o.m_pick = Bc * T;
-    if (pre1) { o.hi2 = pre1[0]; o.lo2 = pre1[1]; }   // train_base: conv1's pre-activation is kept for its GELU' in the backward pass
-    rc = launch_gemm(e->ctx, Mt, d, &sg, 1, terms, pre1 ? EPI_BF16_GELU_SAVE : EPI_BF16_GELU, o, s); if (rc) return rc;
+    if (keep_pre1) { o.hi2 = cp.pre1.hi; o.lo2 = cp.pre1.lo; }   // train_base: kept for its GELU' in the backward pass
+    rc = launch_gemm(e->ctx, Mt, d, &sg, 1, terms, keep_pre1 ? EPI_BF16_GELU_SAVE : EPI_BF16_GELU, o, s); if (rc) return rc;
   }
   GemmSeg sg[3];
   for (int dt = 0; dt < 3; ++dt) {
@@ -518,82 +546,74 @@ int encoder_layer(awt_encoder* e, Layer& L, const LayerBufs& b, int Bc, bool sav
   const bool pp_fc1 = !save && (g_pp_mask & 4) && use_pp(e, L.fc1, L.l1, M, EPI_BF16_GELU), pp_fc2 = pp_fc1 && (g_pp_mask & 8) && use_pp(e, L.fc2, L.l2, M, EPI_F32_RESID);
   // an activation whose only consumer is a GEMM on fp16-exact weights (gemm.hip, WX) needs no hi8 image: the producers skip that plane
   auto feeds = [&](Act a, const Linear& lin, const LoraGroup& lg) { if (terms == PREC_F16F8 && lin.w.exact16 && !lg.active) a.hi8 = nullptr; return a; };
-  const Act aqkv = make_act(b.qkv[0], b.qkv[1], 3 * (size_t)plane, terms);
-  const Act aatt = pp_out ? make_ilv(b.att[0]) : feeds(make_act(b.att[0], b.att[1], (size_t)plane, terms), L.out, L.lo_);
-  int rc = launch_layernorm(e->ctx, b.x_in, L.ln1_g, L.ln1_b, M, d, 1e-5f, nullptr,
-                            pp_qkv ? make_ilv(b.ln1[0]) : feeds(make_act(b.ln1[0], b.ln1[1], (size_t)plane, terms), L.qkv, L.lq), terms, s); if (rc) return rc;
+  // The layer's buffers as operand planes, each viewed once: ln1, att, ln2, ff as the GEMM that consumes them reads them, and `*_w` as their producer
+  // writes them (split lines for a ping-pong consumer, else the same planes without the image no consumer reads).  backward_terms = 5 runs the MLP
+  // of the training step in the f16f8 operand format (no fc1 / fc2 adapters in this mode), so its two inputs are f16f8 planes whatever the forward's are.
+  const bool mlp8 = save && e->mlp_f8;
+  const int mprec = mlp8 ? PREC_F16F8 : terms;
+  const Act qkv = make_act(b.qkv, 3 * (size_t)plane, terms), u = make_act(b.u, (size_t)M * 128, terms), uo = make_act(b.uo, (size_t)M * 128, terms);
+  const Act u1 = make_act(b.u1, (size_t)M * 128, terms), u2 = make_act(b.u2, (size_t)M * 128, terms);
+  const Act ln1 = make_act(b.ln1, (size_t)plane, terms), ln1_w = pp_qkv ? make_ilv(b.ln1) : feeds(ln1, L.qkv, L.lq);
+  const Act att = make_act(b.att, (size_t)plane, terms), att_w = pp_out ? make_ilv(b.att) : feeds(att, L.out, L.lo_);
+  const Act ln2 = make_act(b.ln2, (size_t)plane, mprec), ln2_w = pp_fc1 ? make_ilv(b.ln2) : feeds(ln2, L.fc1, L.l1);
+  const Act ff = make_act(b.ff, (size_t)M * f, mprec), ff_w = pp_fc2 ? make_ilv(b.ff) : feeds(ff, L.fc2, L.l2);
+  int rc = launch_layernorm(e->ctx, b.x_in, L.ln1_g, L.ln1_b, M, d, 1e-5f, nullptr, ln1_w, terms, s); if (rc) return rc;
   {
-    GemmOut o{}; set_out(o, aqkv); o.scale = 0.125f * 1.4426950408889634f;   // head_dim^-1/2 and log2(e): see attention.hip
+    GemmOut o{}; set_out(o, qkv); o.scale = 0.125f * 1.4426950408889634f;   // head_dim^-1/2 and log2(e): see attention.hip
     o.S = S; o.H = H; o.plane_stride = plane;
     o.skip_v8 = terms == PREC_F16F8 && !attention_f16f8_reads_v8(save);
-    rc = pp_qkv ? linear_pp(e, b.ln1[0], L.qkv, M, EPI_QKV, o, s) : linear_with_lora(e, b.u, b.ln1, d, L.qkv, L.lq, M, EPI_QKV, o, s);
+    rc = pp_qkv ? linear_pp(e, ln1_w, L.qkv, M, EPI_QKV, o, s) : linear_with_lora(e, u, ln1, d, L.qkv, L.lq, M, EPI_QKV, o, s);
     if (rc) return rc;
   }
-  if (terms == PREC_F16F8) {
-    const Act ak = act_offset(aqkv, plane), av = act_offset(aqkv, 2 * plane);
-    rc = launch_attention_f16f8(e->ctx, F8Planes{aqkv.p16, aqkv.hi8, aqkv.lo8}, F8Planes{ak.p16, ak.hi8, ak.lo8}, F8Planes{av.p16, av.hi8, av.lo8},
-                                F8Planes{aatt.p16, aatt.hi8, aatt.lo8}, nullptr, save ? b.lse : nullptr, Bc, H, S, s, aatt.ilv);
-  } else {
-    rc = launch_attention(e->ctx, b.qkv[0], b.qkv[1], b.qkv[0] + plane, b.qkv[1] ? b.qkv[1] + plane : nullptr, b.qkv[0] + 2 * plane,
-                          b.qkv[1] ? b.qkv[1] + 2 * plane : nullptr, b.att[0], b.att[1], nullptr, save ? b.lse : nullptr, Bc, H, S, terms, s);
-  }
+  float* const lse = save ? b.lse : nullptr;
+  rc = terms == PREC_F16F8 ? launch_attention_f16f8(e->ctx, qkv, act_offset(qkv, plane), act_offset(qkv, 2 * plane), att_w, nullptr, lse, Bc, H, S, s)
+                           : launch_attention(e->ctx, b.qkv, b.qkv.at(plane), b.qkv.at(2 * plane), b.att, nullptr, lse, Bc, H, S, terms, s);
   if (rc) return rc;
   {
     GemmOut o{}; o.f32 = b.x_mid; o.resid = b.x_in; o.ldo = d;
-    rc = pp_out ? linear_pp(e, b.att[0], L.out, M, EPI_F32_RESID, o, s) : linear_with_lora(e, b.uo, b.att, d, L.out, L.lo_, M, EPI_F32_RESID, o, s);
+    rc = pp_out ? linear_pp(e, att_w, L.out, M, EPI_F32_RESID, o, s) : linear_with_lora(e, uo, att, d, L.out, L.lo_, M, EPI_F32_RESID, o, s);
     if (rc) return rc;
   }
-  if (save && e->mlp_f8) {   // backward_terms = 5: the MLP of the training step in the f16f8 operand format (no fc1 / fc2 adapters in this mode)
-    const Act aln2 = make_act(b.ln2[0], b.ln2[1], (size_t)plane, PREC_F16F8), aff = make_act(b.ff[0], b.ff[1], (size_t)M * f, PREC_F16F8);
-    rc = launch_layernorm(e->ctx, b.x_mid, L.ln2_g, L.ln2_b, M, d, 1e-5f, nullptr, aln2, PREC_F16F8, s); if (rc) return rc;
-    GemmSeg s1 = seg_plain(aln2, d, L.fc1_8, 0, d, M);
-    GemmOut o1{}; set_out(o1, aff); o1.ldo = f; o1.n_valid = f; o1.bias = L.fc1.bias; o1.hi2 = b.pre[0]; o1.lo2 = b.pre[1]; o1.scale = 1.0f;
+  rc = launch_layernorm(e->ctx, b.x_mid, L.ln2_g, L.ln2_b, M, d, 1e-5f, nullptr, ln2_w, mprec, s); if (rc) return rc;
+  if (mlp8) {
+    GemmSeg s1 = seg_plain(ln2, d, L.fc1_8, 0, d, M);
+    GemmOut o1{}; set_out(o1, ff); o1.ldo = f; o1.n_valid = f; o1.bias = L.fc1.bias; o1.hi2 = b.pre.hi; o1.lo2 = b.pre.lo; o1.scale = 1.0f;
     rc = launch_gemm(e->ctx, M, f, &s1, 1, PREC_F16F8, EPI_BF16_GELU_SAVE, o1, s); if (rc) return rc;
-    GemmSeg s2 = seg_plain(aff, f, L.fc2_8, 0, f, M);
+    GemmSeg s2 = seg_plain(ff, f, L.fc2_8, 0, f, M);
     GemmOut o2{}; o2.f32 = b.x_out; o2.resid = b.x_mid; o2.ldo = d; o2.n_valid = d; o2.bias = L.fc2.bias;
     return launch_gemm(e->ctx, M, d, &s2, 1, PREC_F16F8, EPI_F32_RESID, o2, s);
   }
-  rc = launch_layernorm(e->ctx, b.x_mid, L.ln2_g, L.ln2_b, M, d, 1e-5f, nullptr,
-                        pp_fc1 ? make_ilv(b.ln2[0]) : feeds(make_act(b.ln2[0], b.ln2[1], (size_t)plane, terms), L.fc1, L.l1), terms, s); if (rc) return rc;
   {
-    GemmOut o{}; set_out(o, pp_fc2 ? make_ilv(b.ff[0]) : feeds(make_act(b.ff[0], b.ff[1], (size_t)M * f, terms), L.fc2, L.l2)); o.ldo = f; o.hi2 = b.pre[0]; o.lo2 = b.pre[1];
-    rc = pp_fc1 ? linear_pp(e, b.ln2[0], L.fc1, M, EPI_BF16_GELU, o, s)
-                : linear_with_lora(e, b.u1, b.ln2, d, L.fc1, L.l1, M, save ? EPI_BF16_GELU_SAVE : EPI_BF16_GELU, o, s);
+    GemmOut o{}; set_out(o, ff_w); o.ldo = f; o.hi2 = b.pre.hi; o.lo2 = b.pre.lo;
+    rc = pp_fc1 ? linear_pp(e, ln2_w, L.fc1, M, EPI_BF16_GELU, o, s)
+                : linear_with_lora(e, u1, ln2, d, L.fc1, L.l1, M, save ? EPI_BF16_GELU_SAVE : EPI_BF16_GELU, o, s);
     if (rc) return rc;
   }
   GemmOut o{}; o.f32 = b.x_out; o.resid = b.x_mid; o.ldo = d;
-  return pp_fc2 ? linear_pp(e, b.ff[0], L.fc2, M, EPI_F32_RESID, o, s) : linear_with_lora(e, b.u2, b.ff, f, L.fc2, L.l2, M, EPI_F32_RESID, o, s);
+  return pp_fc2 ? linear_pp(e, ff_w, L.fc2, M, EPI_F32_RESID, o, s) : linear_with_lora(e, u2, ff, f, L.fc2, L.l2, M, EPI_F32_RESID, o, s);
 }
 
 // Sc: positions per clip the conv stem has to compute (conv_stem_positions; 0 or >= n_ctx: all of them)
 int forward_chunk(awt_encoder* e, const float* mel, int Bc, float* hidden, char* ws_base, hipStream_t s, int Sc = 0) {
   const awt_encoder_cfg& c = e->cfg;
   const int M = Bc * c.n_ctx, d = c.d_model;
-  const bool two = e->planes == 2;
   Workspace w = carve(e, ws_base, Bc);
-  bf16_t* a1[2] = {w.a1[0], two ? w.a1[1] : nullptr};
-  bf16_t* h1[2] = {w.h1[0], two ? w.h1[1] : nullptr};
+  ConvPlanes cp = w.conv;
   float* g = nullptr;
   if (Sc > 0 && Sc < c.n_ctx) {
     // the compact stem's planes (Bc * 2 Sc rows) and its output g [Bc * Sc, d] share the region the full-length conv planes and the layer buffers
     // alias; a shape whose region has no room for g beside the shorter planes (none of Whisper's) keeps the full stem
-    char* const base = (char*)w.a1[0];
-    const size_t room = (size_t)(ws_base + w.bytes - base), Mt = (size_t)Bc * 2 * Sc;
+    char* const base = (char*)w.conv.a1.hi;
+    const size_t room = (size_t)(ws_base + w.bytes - base);
     Carver cv(base);
-    bf16_t *ca1[2] = {nullptr, nullptr}, *ch1[2] = {nullptr, nullptr};
-    for (int p = 0; p < e->planes; ++p) ca1[p] = cv.take<bf16_t>(Mt * conv1_k(c.n_mels) * 2);
-    for (int p = 0; p < e->planes; ++p) ch1[p] = cv.take<bf16_t>(Mt * d * 2);
+    const ConvPlanes ccp = take_conv_planes(e, cv, (size_t)Bc * 2 * Sc, false);
     float* cg = cv.take<float>((size_t)Bc * Sc * d * 4);
-    if (cv.bytes() <= room) { g = cg; for (int p = 0; p < 2; ++p) { a1[p] = ca1[p]; h1[p] = ch1[p]; } }
+    if (cv.bytes() <= room) { g = cg; cp = ccp; }
   }
-  int rc = conv_stem(e, mel, Bc, a1, h1, w.x, s, nullptr, g ? Sc : 0, g); if (rc) return rc;
+  int rc = conv_stem(e, mel, Bc, cp, w.x, s, g ? Sc : 0, g); if (rc) return rc;
   LayerBufs b{};
   b.x_in = b.x_mid = b.x_out = w.x;
-  for (int p = 0; p < 2; ++p) {
-    const bool on = p == 0 || two;
-    b.ln1[p] = b.ln2[p] = on ? w.ln[p] : nullptr; b.qkv[p] = on ? w.qkv[p] : nullptr; b.att[p] = on ? w.att[p] : nullptr;
-    b.ff[p] = on ? w.ff[p] : nullptr; b.u[p] = b.uo[p] = b.u1[p] = b.u2[p] = on ? w.u[p] : nullptr; b.pre[p] = nullptr;
-  }
+  b.ln1 = b.ln2 = w.ln; b.qkv = w.qkv; b.att = w.att; b.ff = w.ff; b.u = b.uo = b.u1 = b.u2 = w.u;   // one set, reused by every layer; no pre-activation kept
   for (int li = 0; li < c.n_layers; ++li) { rc = encoder_layer(e, e->layers[li], b, Bc, false, s); if (rc) return rc; }
   return launch_layernorm(e->ctx, w.x, e->lnf_g, e->lnf_b, M, d, 1e-5f, hidden, Act{}, e->prec, s);
 }
@@ -635,26 +655,29 @@ namespace {
 void build_grad_layout(awt_encoder* e) {
   const awt_encoder_cfg& c = e->cfg;
   const int64_t d = c.d_model, f = c.ffn_dim;
-  size_t off = 0;
-  auto add = [&](const std::string& name, std::initializer_list<int64_t> shape) {
+  size_t off = 0, block = 0;
+  auto add = [&](const std::string& name, std::initializer_list<int64_t> shape) {   // returns the entry's offset from `block`
     awt_encoder::GradEntry g{name, off, {1, 1, 1}, (int)shape.size()};
     int i = 0; size_t n = 1;
     for (int64_t v : shape) { g.shape[i++] = v; n *= (size_t)v; }
     e->glayout.push_back(g);
     off += n;
+    return g.offset - block;
   };
-  add("conv1.weight", {d, c.n_mels, 3}); add("conv1.bias", {d}); add("conv2.weight", {d, d, 3}); add("conv2.bias", {d});
-  add("layer_norm.weight", {d}); add("layer_norm.bias", {d});
+  awt_encoder::GradOffsets& o = e->goff;
+  o.c1w = add("conv1.weight", {d, c.n_mels, 3}); o.c1b = add("conv1.bias", {d}); o.c2w = add("conv2.weight", {d, d, 3}); o.c2b = add("conv2.bias", {d});
+  o.lnf = add("layer_norm.weight", {d}); add("layer_norm.bias", {d});
   e->g_head = off;
-  for (int li = 0; li < c.n_layers; ++li) {
+  for (int li = 0; li < c.n_layers; ++li) {   // every block has the same layout: each layer writes the same offsets
     const std::string p = "layers." + std::to_string(li) + ".";
-    add(p + "self_attn.q_proj.weight", {d, d}); add(p + "self_attn.k_proj.weight", {d, d}); add(p + "self_attn.v_proj.weight", {d, d});
-    add(p + "self_attn.q_proj.bias", {d}); add(p + "self_attn.v_proj.bias", {d});
-    add(p + "self_attn.out_proj.weight", {d, d}); add(p + "self_attn.out_proj.bias", {d});
-    add(p + "self_attn_layer_norm.weight", {d}); add(p + "self_attn_layer_norm.bias", {d});
-    add(p + "fc1.weight", {f, d}); add(p + "fc1.bias", {f}); add(p + "fc2.weight", {d, f}); add(p + "fc2.bias", {d});
-    add(p + "final_layer_norm.weight", {d}); add(p + "final_layer_norm.bias", {d});
-    if (li == 0) e->g_per_layer = off - e->g_head;
+    block = off;
+    o.qkvw = add(p + "self_attn.q_proj.weight", {d, d}); add(p + "self_attn.k_proj.weight", {d, d}); add(p + "self_attn.v_proj.weight", {d, d});
+    o.qb = add(p + "self_attn.q_proj.bias", {d}); o.vb = add(p + "self_attn.v_proj.bias", {d});
+    o.ow = add(p + "self_attn.out_proj.weight", {d, d}); o.ob = add(p + "self_attn.out_proj.bias", {d});
+    o.ln1 = add(p + "self_attn_layer_norm.weight", {d}); add(p + "self_attn_layer_norm.bias", {d});
+    o.f1w = add(p + "fc1.weight", {f, d}); o.f1b = add(p + "fc1.bias", {f}); o.f2w = add(p + "fc2.weight", {d, f}); o.f2b = add(p + "fc2.bias", {d});
+    o.ln2 = add(p + "final_layer_norm.weight", {d}); add(p + "final_layer_norm.bias", {d});
+    e->g_per_layer = off - block;
   }
 }
 }  // namespace
@@ -704,7 +727,7 @@ extern "C" int awt_encoder_create(awt_ctx* c, const awt_encoder_cfg* cfg, awt_en
   int rc = alloc_linear(e, &e->conv1, d, conv1_k(cfg->n_mels));
   if (!rc && e->mlp_f8) rc = dev_alloc(e, (void**)&e->wt_tmp, (size_t)f * d * 4);
   if (!rc && e->train_base) rc = dev_alloc(e, (void**)&e->wt_tmp, (size_t)d * d * 4);
-  for (int dt = 0; dt < 3 && !rc && e->train_base; ++dt) rc = alloc_planes(e, &e->conv2T[dt], d, d);
+  for (int dt = 0; dt < 3 && !rc && e->train_base; ++dt) rc = alloc_planes(e, &e->conv2T[dt], d, d, e->prec);
   if (!rc) rc = alloc_linear(e, &e->conv2, d, 3 * d);
   if (!rc) rc = dev_alloc(e, (void**)&e->pos, (size_t)cfg->n_ctx * d * 4);
   if (!rc) rc = dev_alloc(e, (void**)&e->zero_row, (size_t)d * 4);
@@ -724,14 +747,14 @@ extern "C" int awt_encoder_create(awt_ctx* c, const awt_encoder_cfg* cfg, awt_en
       for (Linear* lin : {&L.qkv, &L.out, &L.fc1, &L.fc2})
         if (!rc && lin->N % 256 == 0 && lin->K % 64 == 0 && lin->K >= 128) rc = dev_alloc(e, (void**)&lin->w.pp, gemm_pp_weight_bytes(lin->N, lin->K));
     if (cfg->training) {
-      if (!rc) rc = alloc_planes(e, &L.qkvT, d, 3 * d);
-      if (!rc) rc = alloc_planes(e, &L.outT, d, d);
-      if (!rc) rc = alloc_planes(e, &L.fc1T, d, f);
-      if (!rc) rc = alloc_planes(e, &L.fc2T, f, d);
-      if (!rc && e->mlp_f8) rc = alloc_planes_f8(e, &L.fc1T8, d, f);
-      if (!rc && e->mlp_f8) rc = alloc_planes_f8(e, &L.fc2T8, f, d);
-      if (!rc && e->mlp_f8) rc = alloc_planes_f8(e, &L.fc1_8, f, d);
-      if (!rc && e->mlp_f8) rc = alloc_planes_f8(e, &L.fc2_8, d, f);
+      if (!rc) rc = alloc_planes(e, &L.qkvT, d, 3 * d, e->prec);
+      if (!rc) rc = alloc_planes(e, &L.outT, d, d, e->prec);
+      if (!rc) rc = alloc_planes(e, &L.fc1T, d, f, e->prec);
+      if (!rc) rc = alloc_planes(e, &L.fc2T, f, d, e->prec);
+      if (!rc && e->mlp_f8) rc = alloc_planes(e, &L.fc1T8, d, f, PREC_F16F8);
+      if (!rc && e->mlp_f8) rc = alloc_planes(e, &L.fc2T8, f, d, PREC_F16F8);
+      if (!rc && e->mlp_f8) rc = alloc_planes(e, &L.fc1_8, f, d, PREC_F16F8);
+      if (!rc && e->mlp_f8) rc = alloc_planes(e, &L.fc2_8, d, f, PREC_F16F8);
     }
     float** lnp[4] = {&L.ln1_g, &L.ln1_b, &L.ln2_g, &L.ln2_b};
     for (int k = 0; k < 4 && !rc; ++k) rc = dev_alloc(e, (void**)lnp[k], (size_t)d * 4);
@@ -759,17 +782,18 @@ extern "C" int awt_encoder_set_weight(awt_encoder* e, const char* name, const fl
   const awt_encoder_cfg& c = e->cfg;
   const int d = c.d_model, f = c.ffn_dim, r = c.lora_rank;
   int rc = AWT_ERR_INVALID;
-  auto pack = [&](const Planes& pl, int N, int C, int taps, int row_off, int col_off) {
-    return launch_pack_weight(e->ctx, data, N, C, taps, pl.ld, row_off, col_off, 1.0f, pl.hi, pl.lo, pl.x8, e->prec, s, nullptr, pl.s16, pl.s8);
+  // dst(row_off + c, col_off + n) = scale * src[n, c]: the transposed copies the backward pass multiplies by
+  auto pack_t = [&](const float* src, const Planes& pl, int N, int C, int row_off, int col_off, float scale) {
+    return launch_pack_weight_t(e->ctx, src, N, C, pl.ld, row_off, col_off, scale, PlanePair{pl.hi, pl.lo}, s);
   };
   std::string nm(name);
-  if (nm == "conv1.weight") { rc = check_shape(name, shape, rank, {d, c.n_mels, 3}); if (!rc) rc = pack(e->conv1.w, d, c.n_mels, 3, 0, 0); }
+  if (nm == "conv1.weight") { rc = check_shape(name, shape, rank, {d, c.n_mels, 3}); if (!rc) rc = pack(e->ctx, data, e->conv1.w, d, c.n_mels, 3, 0, 0, e->prec, s); }
   else if (nm == "conv1.bias") { rc = check_shape(name, shape, rank, {d}); if (!rc) rc = copy_f32(e->conv1.bias, data, d, s); }
   else if (nm == "conv2.weight") {
-    rc = check_shape(name, shape, rank, {d, d, 3}); if (!rc) rc = pack(e->conv2.w, d, d, 3, 0, 0);
+    rc = check_shape(name, shape, rank, {d, d, 3}); if (!rc) rc = pack(e->ctx, data, e->conv2.w, d, d, 3, 0, 0, e->prec, s);
     for (int dt = 0; dt < 3 && !rc && e->train_base; ++dt) {   // per tap: W[:, :, dt]^T, the weight of d h1 = d pre2 W2
       rc = launch_conv_tap(e->ctx, data, d, d, dt, e->wt_tmp, s);
-      if (!rc) rc = launch_pack_weight_t(e->ctx, e->wt_tmp, d, d, e->conv2T[dt].ld, 0, 0, 1.0f, e->conv2T[dt].hi, e->conv2T[dt].lo, s);
+      if (!rc) rc = pack_t(e->wt_tmp, e->conv2T[dt], d, d, 0, 0, 1.0f);
     }
   }
   else if (nm == "conv2.bias") { rc = check_shape(name, shape, rank, {d}); if (!rc) rc = copy_f32(e->conv2.bias, data, d, s); }
@@ -793,24 +817,15 @@ extern "C" int awt_encoder_set_weight(awt_encoder* e, const char* name, const fl
       const std::string key(p.key);
       if (rs == key + ".weight") {
         found = true; rc = check_shape(name, shape, rank, {p.N, p.K});
-        if (!rc && (e->prec == PREC_F16F8 || e->prec == PREC_F16X3) && !c.training && p.lin->w.d_inexact) {
-          // fp16-exact weights (checkpoints stored in half precision) let the GEMM drop one cross term: find out now, at upload time
-          Planes& pl = p.lin->w;
-          int* flag = pl.d_inexact + p.row_off / p.N;
-          int host[4] = {0, 0, 0, 0};
-          if (hipMemsetAsync(flag, 0, sizeof(int), s) != hipSuccess) rc = awt_fail(AWT_ERR_HIP, "set_weight: flag reset failed");
-          if (!rc) rc = launch_pack_weight(e->ctx, data, p.N, p.K, 1, pl.ld, p.row_off, 0, 1.0f, pl.hi, pl.lo, pl.x8, e->prec, s, flag, pl.s16, pl.s8);
-          if (!rc && (hipMemcpyAsync(host, pl.d_inexact, sizeof(host), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess))
-            rc = awt_fail(AWT_ERR_HIP, "set_weight: flag read-back failed");
-          if (!rc) pl.exact16 = !(host[0] | host[1] | host[2] | host[3]);
-        } else if (!rc) rc = pack(p.lin->w, p.N, p.K, 1, p.row_off, 0);
+        if (!rc && (e->prec == PREC_F16F8 || e->prec == PREC_F16X3) && !c.training && p.lin->w.d_inexact)   // one flag per row block q | k | v: find out now, at upload time
+          rc = probe_exact16(e->ctx, "set_weight", data, p.lin->w, p.N, p.K, p.row_off, e->prec, p.lin->w.d_inexact, p.row_off / p.N, 4, s);
+        else if (!rc) rc = pack(e->ctx, data, p.lin->w, p.N, p.K, 1, p.row_off, 0, e->prec, s);
         if (!rc && p.lin->w.pp) rc = launch_pack_weight_pp(e->ctx, data, p.N, p.K, p.row_off, p.lin->w.pp, s);
-        if (!rc && c.training)   // W^T: [K, N_total], this projection's columns start at row_off
-          rc = launch_pack_weight_t(e->ctx, data, p.N, p.K, p.wT->ld, 0, p.row_off, 1.0f, p.wT->hi, p.wT->lo, s);
+        if (!rc && c.training) rc = pack_t(data, *p.wT, p.N, p.K, 0, p.row_off, 1.0f);   // W^T: [K, N_total], this projection's columns start at row_off
         if (!rc && e->mlp_f8 && p.wT8) {   // the same W^T [K, N] in the f16f8 weight format: transposed into the scratch matrix, then packed like a forward weight
           rc = launch_transpose_f32(e->ctx, data, p.N, p.K, e->wt_tmp, s);
-          if (!rc) rc = launch_pack_weight(e->ctx, e->wt_tmp, p.K, p.N, 1, p.wT8->ld, 0, 0, 1.0f, p.wT8->hi, p.wT8->lo, p.wT8->x8, PREC_F16F8, s, nullptr, p.wT8->s16, p.wT8->s8);
-          if (!rc) rc = launch_pack_weight(e->ctx, data, p.N, p.K, 1, p.w8->ld, 0, 0, 1.0f, p.w8->hi, p.w8->lo, p.w8->x8, PREC_F16F8, s, nullptr, p.w8->s16, p.w8->s8);
+          if (!rc) rc = pack(e->ctx, e->wt_tmp, *p.wT8, p.K, p.N, 1, 0, 0, PREC_F16F8, s);
+          if (!rc) rc = pack(e->ctx, data, *p.w8, p.N, p.K, 1, 0, 0, PREC_F16F8, s);
         }
       }
       else if (rs == key + ".bias") {
@@ -822,11 +837,11 @@ extern "C" int awt_encoder_set_weight(awt_encoder* e, const char* name, const fl
         if (r == 0 || !(c.lora_targets & p.bit) || !p.lg->active)
           return awt_fail(AWT_ERR_STATE, std::string("set_weight: ") + name + " given but this adapter is not enabled in awt_encoder_cfg");
         if (rs.back() == 'A') {
-          rc = check_shape(name, shape, rank, {r, p.K}); if (!rc) rc = pack(p.lg->a, r, p.K, 1, p.slot * r, 0);
-          if (!rc && c.training) rc = launch_pack_weight_t(e->ctx, data, r, p.K, p.lg->aT.ld, 0, p.slot * r, lscale, p.lg->aT.hi, p.lg->aT.lo, s);
+          rc = check_shape(name, shape, rank, {r, p.K}); if (!rc) rc = pack(e->ctx, data, p.lg->a, r, p.K, 1, p.slot * r, 0, e->prec, s);
+          if (!rc && c.training) rc = pack_t(data, p.lg->aT, r, p.K, 0, p.slot * r, lscale);
         } else {
-          rc = check_shape(name, shape, rank, {p.N, r}); if (!rc) rc = pack(p.lg->b, p.N, r, 1, p.row_off, p.slot * r);
-          if (!rc && c.training) rc = launch_pack_weight_t(e->ctx, data, p.N, r, p.lg->bT.ld, p.slot * r, p.row_off, 1.0f, p.lg->bT.hi, p.lg->bT.lo, s);
+          rc = check_shape(name, shape, rank, {p.N, r}); if (!rc) rc = pack(e->ctx, data, p.lg->b, p.N, r, 1, p.row_off, p.slot * r, e->prec, s);
+          if (!rc && c.training) rc = pack_t(data, p.lg->bT, p.N, r, p.slot * r, p.row_off, 1.0f);
         }
       }
       if (found) break;
@@ -950,23 +965,16 @@ OpLinearWs op_linear_layout(void* base, int M, int N, int K) { return op_linear_
 // w [N, K] fp32 as the operand planes of `terms` in the workspace's w pieces (fragment-major; f16f8: also the 16-row copies)
 int op_linear_pack_weight(awt_ctx* c, const float* w, int N, int K, int terms, const OpLinearWs& ws, Planes& pw, hipStream_t s) {
   pw.hi = ws.w.hi; pw.lo = ws.w.lo; pw.x8 = (uint8_t*)pw.lo + (size_t)N * K; pw.rows = N; pw.ld = K;
-  if (terms == PREC_F16F8 || terms == PREC_F16X3) {   // as awt_encoder_set_weight does: fp16-exact weights take the GEMM without the x_hi w_lo product
-    int host = 1;
-    if (hipMemsetAsync(ws.flag, 0, sizeof(int), s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear: flag reset failed");
-    if (terms == PREC_F16F8) {
-      pw.s_rows = ((int64_t)N + 255) / 256 * 256;
-      pw.s16 = ws.s16; pw.s8 = ws.s8;
-      if (N % 256 != 0) {   // the rows beyond N are read by the last column tile (never stored): keep them finite
-        if (hipMemsetAsync(ws.s16, 0, ws.s_bytes, s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear: weight copy reset failed");
-      }
+  if (terms == PREC_F16F8) {
+    pw.s_rows = ((int64_t)N + 255) / 256 * 256;
+    pw.s16 = ws.s16; pw.s8 = ws.s8;
+    if (N % 256 != 0) {   // the rows beyond N are read by the last column tile (never stored): keep them finite
+      if (hipMemsetAsync(ws.s16, 0, ws.s_bytes, s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear: weight copy reset failed");
     }
-    int rc = launch_pack_weight(c, w, N, K, 1, K, 0, 0, 1.0f, pw.hi, pw.lo, pw.x8, terms, s, ws.flag, pw.s16, pw.s8); if (rc) return rc;
-    if (hipMemcpyAsync(&host, ws.flag, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-      return awt_fail(AWT_ERR_HIP, "op_linear: flag read-back failed");
-    pw.exact16 = host == 0;
-    return AWT_OK;
   }
-  return launch_pack_weight(c, w, N, K, 1, K, 0, 0, 1.0f, pw.hi, pw.lo, pw.x8, terms, s);     // fragment-major
+  // as awt_encoder_set_weight does: fp16-exact weights take the GEMM without the x_hi w_lo product
+  if (terms == PREC_F16F8 || terms == PREC_F16X3) return probe_exact16(c, "op_linear", w, pw, N, K, 0, terms, ws.flag, 0, 1, s);
+  return pack(c, w, pw, N, K, 1, 0, 0, terms, s);     // fragment-major
 }
 // awt_op_attention's workspace: the two 2-byte planes of q, of k and of v
 struct OpAttentionWs { PlanePair q, k, v; size_t bytes; };
@@ -1005,7 +1013,7 @@ extern "C" int awt_op_linear(awt_ctx* c, const float* x, const float* w, const f
     GemmOut op{}; op.f32 = y; op.ldo = N; op.bias = bias; op.n_valid = N;
     return launch_gemm_pp(c, M, N, sgp, EPI_F32, op, s);
   }
-  const Act ax = make_act(ws.x.hi, ws.x.lo, (size_t)M * K, terms);
+  const Act ax = make_act(ws.x, (size_t)M * K, terms);
   int rc = launch_split_planes(c, x, (int64_t)M * K, 1.0f, terms, kF8Act, ws.x.hi, ws.x.lo, ax.hi8, ax.lo8, s); if (rc) return rc;
   Planes pw;
   rc = op_linear_pack_weight(c, w, N, K, terms, ws, pw, s); if (rc) return rc;
@@ -1072,7 +1080,7 @@ extern "C" int awt_op_linear_fused(awt_ctx* c, const awt_linear_fused_args* a, v
     Planes pwp; pwp.pp = ws.w_pp(); pwp.rows = N; pwp.ld = K;
     return launch_gemm_pp(c, M, N, seg_plain(ai, K, pwp, 0, K, M), (GemmEpilogue)epi, o, s);
   }
-  const Act ax = make_act(ws.x.hi, ws.x.lo, (size_t)nx, terms);
+  const Act ax = make_act(ws.x, (size_t)nx, terms);
   int rc = launch_split_planes(c, a->x, nx, 1.0f, terms, kF8Act, ws.x.hi, ws.x.lo, ax.hi8, ax.lo8, s); if (rc) return rc;
   Planes pw;
   rc = op_linear_pack_weight(c, a->w, N, a->ldw, terms, ws, pw, s); if (rc) return rc;
@@ -1104,7 +1112,6 @@ int op_attention_planes(awt_ctx* c, const float* q, const float* k, const float*
   }
   return AWT_OK;
 }
-F8Planes op_attention_f8(const PlanePair& p, int64_t n) { return F8Planes{p.hi, (uint8_t*)p.lo, (uint8_t*)p.lo + n}; }
 }  // namespace
 
 extern "C" size_t awt_op_attention_workspace_bytes(int B, int H, int S) { return op_attention_layout(nullptr, B, H, S).bytes; }
@@ -1118,8 +1125,8 @@ extern "C" int awt_op_attention(awt_ctx* c, const float* q, const float* k, cons
   const OpAttentionWs ws = op_attention_layout(workspace, B, H, S);
   int rc = op_attention_planes(c, q, k, v, n, terms, ws, true, s); if (rc) return rc;
   if (terms == PREC_F16F8)
-    return launch_attention_f16f8(c, op_attention_f8(ws.q, n), op_attention_f8(ws.k, n), op_attention_f8(ws.v, n), F8Planes{nullptr, nullptr, nullptr}, o, nullptr, B, H, S, s);
-  return launch_attention(c, ws.q.hi, ws.q.lo, ws.k.hi, ws.k.lo, ws.v.hi, ws.v.lo, nullptr, nullptr, o, nullptr, B, H, S, terms, s);
+    return launch_attention_f16f8(c, make_act(ws.q, n, terms), make_act(ws.k, n, terms), make_act(ws.v, n, terms), Act{}, o, nullptr, B, H, S, s);
+  return launch_attention(c, ws.q, ws.k, ws.v, PlanePair{}, o, nullptr, B, H, S, terms, s);
 }
 
 // awt_op_attention with the output forms and the log-sum-exp the encoder layer asks of the same launchers (encoder_layer): everything either launcher
@@ -1143,11 +1150,12 @@ extern "C" int awt_op_attention_ex(awt_ctx* c, const float* q, const float* k, c
   const int64_t n = (int64_t)B * H * S * 64;
   const OpAttentionWs ws = op_attention_layout(workspace, B, H, S);
   int rc = op_attention_planes(c, q, k, v, n, terms, ws, !f8 || attention_f16f8_reads_v8(lse2 != nullptr), s); if (rc) return rc;
-  if (f8)
-    return launch_attention_f16f8(c, op_attention_f8(ws.q, n), op_attention_f8(ws.k, n), op_attention_f8(ws.v, n),
-                                  F8Planes{(bf16_t*)o_hi, (uint8_t*)o_hi8, (uint8_t*)o_lo8}, o_f32, lse2, B, H, S, s, (char*)o_ilv);
-  bf16_t* const olo = prec_products(terms) == 3 ? (bf16_t*)o_lo : nullptr;     // one plane with a single product, as the encoder's buffers have then
-  return launch_attention(c, ws.q.hi, ws.q.lo, ws.k.hi, ws.k.lo, ws.v.hi, ws.v.lo, (bf16_t*)o_hi, olo, o_f32, lse2, B, H, S, terms, s);
+  if (f8) {
+    Act ao; ao.p16 = (bf16_t*)o_hi; ao.hi8 = (uint8_t*)o_hi8; ao.lo8 = (uint8_t*)o_lo8; ao.ilv = (char*)o_ilv;
+    return launch_attention_f16f8(c, make_act(ws.q, n, terms), make_act(ws.k, n, terms), make_act(ws.v, n, terms), ao, o_f32, lse2, B, H, S, s);
+  }
+  const PlanePair po{(bf16_t*)o_hi, prec_products(terms) == 3 ? (bf16_t*)o_lo : nullptr};     // one plane with a single product, as the encoder's buffers have then
+  return launch_attention(c, ws.q, ws.k, ws.v, po, o_f32, lse2, B, H, S, terms, s);
 }
 
 // What one encoder layer's training pass runs around its attention, on caller tensors: the operand planes, the training form of the forward
@@ -1171,13 +1179,11 @@ extern "C" int awt_op_attention_backward(awt_ctx* c, const float* q, const float
     int rc = launch_split_planes(c, src[i], n, i == 0 ? 1.4426950408889634f : 1.0f, terms, 0, pl[i].hi, pl[i].lo, nullptr, nullptr, s);
     if (rc) return rc;
   }
-  bf16_t* const olo = terms == 3 ? (bf16_t*)o_lo : nullptr;   // terms 1: one plane each, as the encoder's buffers have then
-  bf16_t* const glo = terms == 3 ? (bf16_t*)g_lo : nullptr;
-  const auto lo = [&](const PlanePair& p) { return terms == 3 ? p.lo : nullptr; };
-  int rc = launch_attention(c, ws.q.hi, lo(ws.q), ws.k.hi, lo(ws.k), ws.v.hi, lo(ws.v), (bf16_t*)o_hi, olo, nullptr, lse2, B, H, S, terms, s);
+  const auto planes = [&](const PlanePair& p) { return PlanePair{p.hi, terms == 3 ? p.lo : nullptr}; };   // terms 1: one plane each, as the encoder's buffers have then
+  const PlanePair po = planes({(bf16_t*)o_hi, (bf16_t*)o_lo}), pg = planes({(bf16_t*)g_hi, (bf16_t*)g_lo});
+  int rc = launch_attention(c, planes(ws.q), planes(ws.k), planes(ws.v), po, nullptr, lse2, B, H, S, terms, s);
   if (rc) return rc;
-  return launch_attention_bwd(c, ws.q.hi, lo(ws.q), ws.k.hi, lo(ws.k), ws.v.hi, lo(ws.v), (bf16_t*)o_hi, olo, ws.d_o.hi, lo(ws.d_o), lse2, delta,
-                              (bf16_t*)g_hi, glo, B, H, S, qscale, terms, grad_terms, s);
+  return launch_attention_bwd(c, planes(ws.q), planes(ws.k), planes(ws.v), po, planes(ws.d_o), lse2, delta, pg, B, H, S, qscale, terms, grad_terms, s);
 }
 
 // ------------------------------------------------------------------------------------------------ LoRA fine-tune step
@@ -1194,20 +1200,28 @@ extern "C" size_t awt_encoder_train_workspace_bytes(const awt_encoder* e, int B)
 }
 
 namespace {
-// elements of one layer's adapter gradients: for every enabled target in the order q, k, v, out, fc1, fc2: dA [r, K_in] then dB [N_out, r]
-size_t lora_grads_per_layer(const awt_encoder_cfg& c) {
+// One layer's block of adapter gradients: for every enabled target in the order q, k, v, out, fc1, fc2: dA [r, K_in] then dB [N_out, r].
+// dA[t] / dB[t]: element offsets of target t (that order) inside the block, meaningful for the enabled targets; total: the block's elements.
+enum { T_Q, T_K, T_V, T_OUT, T_FC1, T_FC2, T_COUNT };
+struct LoraGradSlots { size_t dA[T_COUNT], dB[T_COUNT], total; };
+LoraGradSlots lora_grad_slots(const awt_encoder_cfg& c) {
   const size_t r = c.lora_rank, d = c.d_model, f = c.ffn_dim;
-  size_t n = 0;
-  for (uint32_t bit : {AWT_LORA_Q, AWT_LORA_K, AWT_LORA_V, AWT_LORA_OUT}) if (c.lora_targets & bit) n += 2 * r * d;
-  if (c.lora_targets & AWT_LORA_FC1) n += r * d + f * r;
-  if (c.lora_targets & AWT_LORA_FC2) n += r * f + d * r;
-  return n;
+  const struct { uint32_t bit; size_t k_in, n_out; } target[T_COUNT] = {{AWT_LORA_Q, d, d},   {AWT_LORA_K, d, d},   {AWT_LORA_V, d, d},
+                                                                       {AWT_LORA_OUT, d, d}, {AWT_LORA_FC1, d, f}, {AWT_LORA_FC2, f, d}};
+  LoraGradSlots g{};
+  for (int t = 0; t < T_COUNT; ++t) {
+    if (!(c.lora_targets & target[t].bit)) continue;
+    g.dA[t] = g.total;
+    g.dB[t] = g.dA[t] + r * target[t].k_in;
+    g.total = g.dB[t] + target[t].n_out * r;
+  }
+  return g;
 }
 }  // namespace
 
 extern "C" size_t awt_encoder_lora_grad_count(const awt_encoder* e) {
   if (!e || e->cfg.lora_rank <= 0) return 0;
-  return (size_t)e->cfg.n_layers * lora_grads_per_layer(e->cfg);
+  return (size_t)e->cfg.n_layers * lora_grad_slots(e->cfg).total;
 }
 
 extern "C" int awt_encoder_forward_train(awt_encoder* e, const float* mel, int B, int n_frames, float* hidden, void* saved,
@@ -1223,7 +1237,7 @@ extern "C" int awt_encoder_forward_train(awt_encoder* e, const float* mel, int B
   AWT_REQUIRE(((uintptr_t)saved & 255) == 0, AWT_ERR_INVALID, "encoder_forward_train: saved buffer must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   TrainWs w = carve_train(e, (char*)saved, B);
-  rc = conv_stem(e, mel, B, w.a1, w.h1, w.layer[0].x_in, s, e->train_base ? w.pre1 : nullptr); if (rc) return rc;
+  rc = conv_stem(e, mel, B, w.conv, w.layer[0].x_in, s); if (rc) return rc;
   for (int li = 0; li < e->cfg.n_layers; ++li) { rc = encoder_layer(e, e->layers[li], w.layer[li], B, true, s); if (rc) return rc; }
   return launch_layernorm(e->ctx, w.x_final, e->lnf_g, e->lnf_b, B * e->cfg.n_ctx, e->cfg.d_model, 1e-5f, hidden, Act{}, e->prec, s);
 }
@@ -1266,143 +1280,122 @@ extern "C" int awt_encoder_backward_ex(awt_encoder* e, const float* d_hidden, in
   const int64_t plane = (int64_t)M * d;
   const float lscale = r > 0 ? c.lora_alpha / (float)r : 0.f;
   TrainWs w = carve_train(e, (char*)saved, B);
-  const size_t per_layer = tb ? e->g_per_layer : lora_grads_per_layer(c);
-  float* const layer_grads = lora_grads + (tb ? e->g_head : 0);     // train_base: the non-layer parameters come first (build_grad_layout)
+  const LoraGradSlots gslots = lora_grad_slots(c);
+  const awt_encoder::GradOffsets& go = e->goff;     // train_base: where each base parameter's gradient goes (build_grad_layout)
+  const size_t per_layer = tb ? e->g_per_layer : gslots.total;
+  float* const layer_grads = lora_grads + (tb ? e->g_head : 0);     // train_base: the non-layer parameters come first
+  // the gradient buffers, each as the plane pair the row kernels take (p) and as the GEMM operand / output it also is (a)
+  struct Grad { PlanePair p; Act a; };
+  auto grad = [&](const PlanePair& p, size_t elems) { return Grad{p, make_act(p, elems, PREC_BF16X3)}; };
+  const Grad dxp = grad(w.dxp, (size_t)M * d), dpre = grad(w.dpre, (size_t)M * f), datt = grad(w.datt, (size_t)M * d), dqkv = grad(w.dqkv, 3 * (size_t)M * d);
+  const Grad du = grad(w.du, (size_t)M * 128);
   int rc;
 
   // ---- cfg.train_base: gradients of the base parameters, each formed where its dY is live.  dW = dY^T X on the weight-gradient GEMM (wgrad.hip), bias and
   //      LayerNorm gradients on the column-reduction row kernels; all of them leave divided by the pass' gradient scale.
   const int wterms = (gterms == PREC_BF16 || e->planes == 1) ? 1 : 3;   // three products need the lo planes of the saved activations
   float* const partial = w.partial;
-  auto dW = [&](const bf16_t* y0, const bf16_t* y1, int64_t ldy, int ycol, int N, bf16_t* const x[2], int64_t ldx, int xcol, int K, int rows, const WgradRowMap* map,
+  auto dW = [&](const PlanePair& y, int64_t ldy, int ycol, int N, const PlanePair& x, int64_t ldx, int xcol, int K, int rows, const WgradRowMap* map,
                 float* out, int64_t sn, int64_t sk) -> int {
-    const WgradOperand yo{y0, wterms == 3 ? y1 : nullptr, ldy, ycol}, xo{x[0], wterms == 3 ? x[1] : nullptr, ldx, xcol};
+    const WgradOperand yo{y.hi, wterms == 3 ? y.lo : nullptr, ldy, ycol}, xo{x.hi, wterms == 3 ? x.lo : nullptr, ldx, xcol};
     return launch_wgrad(e->ctx, yo, N, xo, K, rows, map, wterms, inv_gscale, out, sn, sk, accumulate, partial, w.partial_bytes, s);
   };
-  auto dBias = [&](const bf16_t* y0, const bf16_t* y1, int64_t ldy, int ycol, int N, int rows, float* out) -> int {   // column sums of dY, <= 1024 columns per launch
+  auto dBias = [&](const PlanePair& y, int64_t ldy, int ycol, int N, int rows, float* out) -> int {   // column sums of dY, <= 1024 columns per launch
     for (int c0 = 0; c0 < N; c0 += 1024) {
       const int n = std::min(1024, N - c0);
-      int rc2 = launch_param_grad(e->ctx, nullptr, y0 + ycol + c0, y1 ? y1 + ycol + c0 : nullptr, ldy, nullptr, rows, n, 0.f, inv_gscale, accumulate, nullptr, out + c0,
-                                  partial, s);
+      int rc2 = launch_param_grad(e->ctx, nullptr, y.at(ycol + c0), ldy, nullptr, rows, n, 0.f, inv_gscale, accumulate, nullptr, out + c0, partial, s);
       if (rc2) return rc2;
     }
     return AWT_OK;
   };
   auto dLN = [&](const float* dy, const float* x, float scale, float* dgamma) -> int {   // dgamma [d] then dbeta [d]
-    return launch_param_grad(e->ctx, dy, nullptr, nullptr, 0, x, M, d, 1e-5f, scale, accumulate, dgamma, dgamma + d, partial, s);
+    return launch_param_grad(e->ctx, dy, PlanePair{}, 0, x, M, d, 1e-5f, scale, accumulate, dgamma, dgamma + d, partial, s);
   };
-  // offsets inside a layer's block (build_grad_layout)
-  const size_t dd = (size_t)d * d, o_qkvw = 0, o_qb = 3 * dd, o_vb = o_qb + d, o_ow = o_vb + d, o_ob = o_ow + dd, o_ln1 = o_ob + d, o_f1w = o_ln1 + 2 * d,
-               o_f1b = o_f1w + (size_t)f * d, o_f2w = o_f1b + f, o_f2b = o_f2w + (size_t)d * f, o_ln2 = o_f2b + d;
-  if (tb) { rc = dLN(d_hidden, w.x_final, 1.0f, lora_grads + e->g_head - 2 * d); if (rc) return rc; }   // the final layer_norm sees the unscaled gradient
+  if (tb) { rc = dLN(d_hidden, w.x_final, 1.0f, lora_grads + go.lnf); if (rc) return rc; }   // the final layer_norm sees the unscaled gradient
 
-  // One adapter group (adapters that share an input): du = dy B into w.du, then per adapter dA = lscale du^T x_in and dB = dy^T u at
-  // `gp` (advanced).  Forward: u = lscale x_in A^T (saved), y = x_in W^T + b + u B^T.  The group's du stays in w.du for the caller's
-  // dX product, which takes it as a second K-segment against (lscale A)^T.
-  struct Slot { uint32_t bit; int col; int n_out; };
-  auto group_backward = [&](LoraGroup& lg, const bf16_t* dy0, const bf16_t* dy1, int ld_dy, int n_out_total, const Slot* slots, int nslot, bf16_t* const xin[2],
-                            int k_in, bf16_t* const u[2], float*& gp) -> int {
+  // One adapter group (adapters that share an input): du = dy B into w.du, then per adapter dA = lscale du^T x_in and dB = dy^T u into the adapter's
+  // slots of the layer's block `gl` (lora_grad_slots).  Forward: u = lscale x_in A^T (saved), y = x_in W^T + b + u B^T.  The group's du stays in w.du
+  // for the caller's dX product, which takes it as a second K-segment against (lscale A)^T.
+  struct Slot { uint32_t bit; int target; int col; int n_out; };
+  auto group_backward = [&](LoraGroup& lg, const Grad& dy, int ld_dy, int n_out_total, const Slot* slots, int nslot, const PlanePair& xin, int k_in, const PlanePair& u,
+                            float* gl) -> int {
     if (!lg.active) return AWT_OK;
     {
-      GemmSeg sg = seg_plain(dy0, dy1, ld_dy, lg.bT, 0, n_out_total, M);
-      GemmOut o{}; o.hi = w.du[0]; o.lo = w.du[1]; o.ldo = lg.kp; o.n_valid = lg.kp; o.scale = 1.0f;
+      GemmSeg sg = seg_plain(dy.a, ld_dy, lg.bT, 0, n_out_total, M);
+      GemmOut o{}; set_out(o, du.a); o.ldo = lg.kp; o.n_valid = lg.kp; o.scale = 1.0f;
       int rc2 = launch_gemm(e->ctx, M, 128, &sg, 1, gterms, EPI_BF16, o, s); if (rc2) return rc2;
     }
     for (int i = 0; i < nslot; ++i) {          // adapter i of the group owns rows / columns i r .. i r + r - 1 of A / B, u and du (set_weight)
       if (!(c.lora_targets & slots[i].bit)) continue;
-      float* dA = gp;
-      float* dB = dA + (size_t)r * k_in;
-      int rc2 = launch_outer_reduce(e->ctx, w.du[0], w.du[1], lg.kp, i * r, r, xin[0], xin[1], k_in, 0, k_in, M, lscale * inv_gscale, dA, k_in, 1,
+      int rc2 = launch_outer_reduce(e->ctx, du.p, lg.kp, i * r, r, xin, k_in, 0, k_in, M, lscale * inv_gscale, gl + gslots.dA[slots[i].target], k_in, 1,
                                     w.partial, w.partial_bytes, accumulate, s);
       if (rc2) return rc2;
-      rc2 = launch_outer_reduce(e->ctx, u[0], u[1], lg.kp, i * r, r, dy0, dy1, ld_dy, slots[i].col, slots[i].n_out, M, inv_gscale, dB, 1, r,
+      rc2 = launch_outer_reduce(e->ctx, u, lg.kp, i * r, r, dy.p, ld_dy, slots[i].col, slots[i].n_out, M, inv_gscale, gl + gslots.dB[slots[i].target], 1, r,
                                 w.partial, w.partial_bytes, accumulate, s);
       if (rc2) return rc2;
-      gp = dB + (size_t)slots[i].n_out * r;
     }
     return AWT_OK;
   };
   // slot order inside a group follows the order the forward packs A rows / B columns: the enabled targets of the group, in order
-  const Slot qkv_slots[3] = {{AWT_LORA_Q, 0, d}, {AWT_LORA_K, d, d}, {AWT_LORA_V, 2 * d, d}};
-  const Slot out_slot[1] = {{AWT_LORA_OUT, 0, d}}, fc1_slot[1] = {{AWT_LORA_FC1, 0, f}}, fc2_slot[1] = {{AWT_LORA_FC2, 0, d}};
+  const Slot qkv_slots[3] = {{AWT_LORA_Q, T_Q, 0, d}, {AWT_LORA_K, T_K, d, d}, {AWT_LORA_V, T_V, 2 * d, d}};
+  const Slot out_slot[1] = {{AWT_LORA_OUT, T_OUT, 0, d}}, fc1_slot[1] = {{AWT_LORA_FC1, T_FC1, 0, f}}, fc2_slot[1] = {{AWT_LORA_FC2, T_FC2, 0, d}};
 
   // final LayerNorm
   float* dx = w.dx_a; float* dx_other = w.dx_b;
   // f16f8 images of d(x_out) (the fc2 backward GEMM's operand) and of d(pre) (the fc1 backward GEMM's) live in the same bytes as their bf16 hi / lo planes
-  const Act dxp8 = make_act(w.dxp[0], w.dxp[1], (size_t)M * d, PREC_F16F8), dpre8 = make_act(w.dpre[0], w.dpre[1], (size_t)M * f, PREC_F16F8);
-  rc = mlp8 ? launch_layernorm_bwd(e->ctx, d_hidden, w.x_final, e->lnf_g, nullptr, M, d, 1e-5f, dx, nullptr, nullptr, s, gscale, &dxp8)
-            : launch_layernorm_bwd(e->ctx, d_hidden, w.x_final, e->lnf_g, nullptr, M, d, 1e-5f, dx, w.dxp[0], w.dxp[1], s, gscale);
-  if (rc) return rc;
+  const Act dxp8 = make_act(w.dxp, (size_t)M * d, PREC_F16F8), dpre8 = make_act(w.dpre, (size_t)M * f, PREC_F16F8);
+  // (mlp8: the two LayerNorm backwards that feed an fc2 backward GEMM write those images instead of the planes)
+  rc = launch_layernorm_bwd(e->ctx, d_hidden, w.x_final, e->lnf_g, nullptr, M, d, 1e-5f, dx, mlp8 ? PlanePair{} : w.dxp, s, gscale, mlp8 ? &dxp8 : nullptr); if (rc) return rc;
   for (int li = c.n_layers - 1; li >= 0; --li) {
     Layer& L = e->layers[li];
     const LayerBufs& b = w.layer[li];
-    // gradient layout of the layer: q, k, v, out, fc1, fc2 (enabled ones); the groups are visited fc2, fc1, out, qkv
-    float* g_qkv = layer_grads + (size_t)li * per_layer;
-    float* const gl = g_qkv;   // train_base: the layer's block
-    size_t n_qkv = 0;
-    for (const Slot& sl : qkv_slots) if (c.lora_targets & sl.bit) n_qkv += (size_t)2 * r * d;
-    float* g_out = g_qkv + n_qkv;
-    float* g_fc1 = g_out + ((c.lora_targets & AWT_LORA_OUT) ? (size_t)2 * r * d : 0);
-    float* g_fc2 = g_fc1 + ((c.lora_targets & AWT_LORA_FC1) ? (size_t)r * d + (size_t)f * r : 0);
+    // the layer's block of the gradient buffer: adapters q, k, v, out, fc1, fc2 (enabled ones; lora_grad_slots), or train_base's entries (go); the
+    // groups are visited fc2, fc1, out, qkv
+    float* const gl = layer_grads + (size_t)li * per_layer;
     // ---- MLP: dpre = ([dx | du2] [W2 | lscale A2]) * gelu'(pre) ; dln = [dpre | du1] [W1 | lscale A1] ; dx_mid = dx + LN2_bwd(dln)
-    rc = group_backward(L.l2, w.dxp[0], w.dxp[1], d, d, fc2_slot, 1, b.ff, f, b.u2, g_fc2); if (rc) return rc;
+    rc = group_backward(L.l2, dxp, d, d, fc2_slot, 1, b.ff, f, b.u2, gl); if (rc) return rc;
     if (tb) {
-      rc = dW(w.dxp[0], w.dxp[1], d, 0, d, b.ff, f, 0, f, M, nullptr, gl + o_f2w, f, 1); if (rc) return rc;
-      rc = dBias(w.dxp[0], w.dxp[1], d, 0, d, M, gl + o_f2b); if (rc) return rc;
+      rc = dW(dxp.p, d, 0, d, b.ff, f, 0, f, M, nullptr, gl + go.f2w, f, 1); if (rc) return rc;
+      rc = dBias(dxp.p, d, 0, d, M, gl + go.f2b); if (rc) return rc;
     }
     if (mlp8) {   // no fc1 / fc2 adapters in this mode (encoder_create): one K segment each
       GemmSeg s8 = seg_plain(dxp8, d, L.fc2T8, 0, d, M);
-      GemmOut o{}; set_out(o, dpre8); o.ldo = f; o.n_valid = f; o.pre_hi = b.pre[0]; o.pre_lo = b.pre[1]; o.scale = 1.0f;
+      GemmOut o{}; set_out(o, dpre8); o.ldo = f; o.n_valid = f; o.pre_hi = b.pre.hi; o.pre_lo = b.pre.lo; o.scale = 1.0f;
       rc = launch_gemm(e->ctx, M, f, &s8, 1, PREC_F16F8, EPI_BF16_DGELU, o, s); if (rc) return rc;
       s8 = seg_plain(dpre8, f, L.fc1T8, 0, f, M);
       GemmOut o2{}; o2.f32 = w.dln; o2.ldo = d; o2.n_valid = d;
       rc = launch_gemm(e->ctx, M, d, &s8, 1, PREC_F16F8, EPI_F32, o2, s); if (rc) return rc;
     } else {
-    {
-      GemmSeg sg[2];
-      sg[0] = seg_plain(w.dxp[0], w.dxp[1], d, L.fc2T, 0, d, M);
-      if (L.l2.active) sg[1] = seg_plain(w.du[0], w.du[1], L.l2.kp, L.l2.aT, 0, L.l2.kp, M);
-      GemmOut o{}; o.hi = w.dpre[0]; o.lo = w.dpre[1]; o.ldo = f; o.n_valid = f; o.pre_hi = b.pre[0]; o.pre_lo = b.pre[1];
-      rc = launch_gemm(e->ctx, M, f, sg, L.l2.active ? 2 : 1, gterms, EPI_BF16_DGELU, o, s); if (rc) return rc;
+      GemmOut o{}; set_out(o, dpre.a); o.pre_hi = b.pre.hi; o.pre_lo = b.pre.lo;
+      rc = linear_backward_input(e, dxp.a, d, L.fc2T, L.l2, du.a, f, EPI_BF16_DGELU, o, M, gterms, s); if (rc) return rc;
+      rc = group_backward(L.l1, dpre, f, f, fc1_slot, 1, b.ln2, d, b.u1, gl); if (rc) return rc;
+      if (tb) {
+        rc = dW(dpre.p, f, 0, f, b.ln2, d, 0, d, M, nullptr, gl + go.f1w, d, 1); if (rc) return rc;
+        rc = dBias(dpre.p, f, 0, f, M, gl + go.f1b); if (rc) return rc;
+      }
+      GemmOut o2{}; o2.f32 = w.dln;
+      rc = linear_backward_input(e, dpre.a, f, L.fc1T, L.l1, du.a, d, EPI_F32, o2, M, gterms, s); if (rc) return rc;
     }
-    rc = group_backward(L.l1, w.dpre[0], w.dpre[1], f, f, fc1_slot, 1, b.ln2, d, b.u1, g_fc1); if (rc) return rc;
-    if (tb) {
-      rc = dW(w.dpre[0], w.dpre[1], f, 0, f, b.ln2, d, 0, d, M, nullptr, gl + o_f1w, d, 1); if (rc) return rc;
-      rc = dBias(w.dpre[0], w.dpre[1], f, 0, f, M, gl + o_f1b); if (rc) return rc;
-    }
-    {
-      GemmSeg sg[2];
-      sg[0] = seg_plain(w.dpre[0], w.dpre[1], f, L.fc1T, 0, f, M);
-      if (L.l1.active) sg[1] = seg_plain(w.du[0], w.du[1], L.l1.kp, L.l1.aT, 0, L.l1.kp, M);
-      GemmOut o{}; o.f32 = w.dln; o.ldo = d; o.n_valid = d;
-      rc = launch_gemm(e->ctx, M, d, sg, L.l1.active ? 2 : 1, gterms, EPI_F32, o, s); if (rc) return rc;
-    }
-    }
-    if (tb) { rc = dLN(w.dln, b.x_mid, inv_gscale, gl + o_ln2); if (rc) return rc; }
-    rc = launch_layernorm_bwd(e->ctx, w.dln, b.x_mid, L.ln2_g, dx, M, d, 1e-5f, dx_other, w.dxp[0], w.dxp[1], s); if (rc) return rc;
+    if (tb) { rc = dLN(w.dln, b.x_mid, inv_gscale, gl + go.ln2); if (rc) return rc; }
+    rc = launch_layernorm_bwd(e->ctx, w.dln, b.x_mid, L.ln2_g, dx, M, d, 1e-5f, dx_other, w.dxp, s); if (rc) return rc;
     std::swap(dx, dx_other);   // dx = d(loss)/d(x_mid)
     // ---- attention: datt = [dx_mid | duo] [Wo | lscale Ao] ; (dq, dk, dv) = attention_bwd
-    rc = group_backward(L.lo_, w.dxp[0], w.dxp[1], d, d, out_slot, 1, b.att, d, b.uo, g_out); if (rc) return rc;
+    rc = group_backward(L.lo_, dxp, d, d, out_slot, 1, b.att, d, b.uo, gl); if (rc) return rc;
     if (tb) {
-      rc = dW(w.dxp[0], w.dxp[1], d, 0, d, b.att, d, 0, d, M, nullptr, gl + o_ow, d, 1); if (rc) return rc;
-      rc = dBias(w.dxp[0], w.dxp[1], d, 0, d, M, gl + o_ob); if (rc) return rc;
+      rc = dW(dxp.p, d, 0, d, b.att, d, 0, d, M, nullptr, gl + go.ow, d, 1); if (rc) return rc;
+      rc = dBias(dxp.p, d, 0, d, M, gl + go.ob); if (rc) return rc;
     }
     {
-      GemmSeg sg[2];
-      sg[0] = seg_plain(w.dxp[0], w.dxp[1], d, L.outT, 0, d, M);
-      if (L.lo_.active) sg[1] = seg_plain(w.du[0], w.du[1], L.lo_.kp, L.lo_.aT, 0, L.lo_.kp, M);
-      GemmOut o{}; o.hi = w.datt[0]; o.lo = w.datt[1]; o.ldo = d; o.n_valid = d; o.scale = 1.0f;
-      rc = launch_gemm(e->ctx, M, d, sg, L.lo_.active ? 2 : 1, gterms, EPI_BF16, o, s); if (rc) return rc;
+      GemmOut o{}; set_out(o, datt.a); o.scale = 1.0f;
+      rc = linear_backward_input(e, dxp.a, d, L.outT, L.lo_, du.a, d, EPI_BF16, o, M, gterms, s); if (rc) return rc;
     }
-    rc = launch_attention_bwd(e->ctx, b.qkv[0], b.qkv[1], b.qkv[0] + plane, b.qkv[1] ? b.qkv[1] + plane : nullptr, b.qkv[0] + 2 * plane,
-                              b.qkv[1] ? b.qkv[1] + 2 * plane : nullptr, b.att[0], b.att[1], w.datt[0], w.datt[1], b.lse, w.delta,
-                              w.dqkv[0], w.dqkv[1], B, H, S, 0.125f, terms, gterms, s);
+    rc = launch_attention_bwd(e->ctx, b.qkv, b.qkv.at(plane), b.qkv.at(2 * plane), b.att, w.datt, b.lse, w.delta, w.dqkv, B, H, S, 0.125f, terms, gterms, s);
     if (rc) return rc;
-    rc = group_backward(L.lq, w.dqkv[0], w.dqkv[1], 3 * d, 3 * d, qkv_slots, 3, b.ln1, d, b.u, g_qkv); if (rc) return rc;
+    rc = group_backward(L.lq, dqkv, 3 * d, 3 * d, qkv_slots, 3, b.ln1, d, b.u, gl); if (rc) return rc;
     if (tb) {   // q | k | v weights are adjacent in the block: one [3 d, d] product; k_proj has no bias
-      rc = dW(w.dqkv[0], w.dqkv[1], 3 * d, 0, 3 * d, b.ln1, d, 0, d, M, nullptr, gl + o_qkvw, d, 1); if (rc) return rc;
-      rc = dBias(w.dqkv[0], w.dqkv[1], 3 * d, 0, d, M, gl + o_qb); if (rc) return rc;
-      rc = dBias(w.dqkv[0], w.dqkv[1], 3 * d, 2 * d, d, M, gl + o_vb); if (rc) return rc;
+      rc = dW(dqkv.p, 3 * d, 0, 3 * d, b.ln1, d, 0, d, M, nullptr, gl + go.qkvw, d, 1); if (rc) return rc;
+      rc = dBias(dqkv.p, 3 * d, 0, d, M, gl + go.qb); if (rc) return rc;
+      rc = dBias(dqkv.p, 3 * d, 2 * d, d, M, gl + go.vb); if (rc) return rc;
     }
     // ---- gradient exchange: layers [li, group_hi) are final -- average them over the ranks on the side stream while the
     //      lower layers' backward continues on `s`
@@ -1419,15 +1412,11 @@ extern "C" int awt_encoder_backward_ex(awt_encoder* e, const float* d_hidden, in
     if (li == 0 && !tb) break;   // nothing below the first adapter needs a gradient
     // ---- dln = [dqkv | du] [Wqkv | lscale A]  ; dx_in = dx_mid + LN1_bwd(dln)
     {
-      GemmSeg sg[2];
-      sg[0] = seg_plain(w.dqkv[0], w.dqkv[1], 3 * d, L.qkvT, 0, 3 * d, M);
-      if (L.lq.active) sg[1] = seg_plain(w.du[0], w.du[1], L.lq.kp, L.lq.aT, 0, L.lq.kp, M);
-      GemmOut o{}; o.f32 = w.dln; o.ldo = d; o.n_valid = d;
-      rc = launch_gemm(e->ctx, M, d, sg, L.lq.active ? 2 : 1, gterms, EPI_F32, o, s); if (rc) return rc;
+      GemmOut o{}; o.f32 = w.dln;
+      rc = linear_backward_input(e, dqkv.a, 3 * d, L.qkvT, L.lq, du.a, d, EPI_F32, o, M, gterms, s); if (rc) return rc;
     }
-    if (tb) { rc = dLN(w.dln, b.x_in, inv_gscale, gl + o_ln1); if (rc) return rc; }
-    rc = mlp8 ? launch_layernorm_bwd(e->ctx, w.dln, b.x_in, L.ln1_g, dx, M, d, 1e-5f, dx_other, nullptr, nullptr, s, 1.0f, &dxp8)     // feeds the layer below's fc2 backward GEMM
-              : launch_layernorm_bwd(e->ctx, w.dln, b.x_in, L.ln1_g, dx, M, d, 1e-5f, dx_other, w.dxp[0], w.dxp[1], s);
+    if (tb) { rc = dLN(w.dln, b.x_in, inv_gscale, gl + go.ln1); if (rc) return rc; }
+    rc = launch_layernorm_bwd(e->ctx, w.dln, b.x_in, L.ln1_g, dx, M, d, 1e-5f, dx_other, mlp8 ? PlanePair{} : w.dxp, s, 1.0f, mlp8 ? &dxp8 : nullptr);     // feeds the layer below's fc2 backward GEMM
     if (rc) return rc;
     std::swap(dx, dx_other);
   }
@@ -1436,39 +1425,39 @@ extern "C" int awt_encoder_backward_ex(awt_encoder* e, const float* d_hidden, in
     //      conv1: h1 = gelu(pre1), pre1 kept by the forward.  Tap dt of conv2 reads h1 row 2 s + dt - 1 (zero outside the clip).
     const int T = 2 * S, Mt = B * T, nm = c.n_mels, k1 = conv1_k(nm);
     {
+      const Act h1 = make_act(w.conv.h1, (size_t)Mt * d, terms);
       GemmSeg sg[3];
       for (int dt = 0; dt < 3; ++dt) {
-        sg[dt] = seg_plain(w.h1[0], w.h1[1], d, e->conv2.w, (int64_t)dt * d, d, M);
+        sg[dt] = seg_plain(h1, d, e->conv2.w, (int64_t)dt * d, d, M);
         sg[dt].rows_out = S; sg[dt].rows_in = T; sg[dt].row_mul = 2; sg[dt].row_add = dt - 1;
       }
       GemmOut o{}; o.f32 = w.dln; o.ldo = d; o.bias = e->conv2.bias; o.n_valid = d;
       rc = launch_gemm(e->ctx, M, d, sg, 3, terms, EPI_F32, o, s); if (rc) return rc;
     }
-    rc = launch_dgelu_planes(e->ctx, dx, w.dln, (int64_t)M * d, w.datt[0], w.datt[1], s); if (rc) return rc;     // d pre2
-    float* const g_c1w = lora_grads, *g_c1b = g_c1w + (size_t)d * nm * 3, *g_c2w = g_c1b + d, *g_c2b = g_c2w + 3 * dd;
+    rc = launch_dgelu_planes(e->ctx, dx, w.dln, (int64_t)M * d, datt.p, s); if (rc) return rc;     // d pre2
     for (int dt = 0; dt < 3; ++dt) {   // conv2.weight[n, c, dt]
       const WgradRowMap map{S, T, 2, dt - 1};
-      rc = dW(w.datt[0], w.datt[1], d, 0, d, w.h1, d, 0, d, M, &map, g_c2w + dt, 3 * (int64_t)d, 3); if (rc) return rc;
+      rc = dW(datt.p, d, 0, d, w.conv.h1, d, 0, d, M, &map, lora_grads + go.c2w + dt, 3 * (int64_t)d, 3); if (rc) return rc;
     }
-    rc = dBias(w.datt[0], w.datt[1], d, 0, d, M, g_c2b); if (rc) return rc;
+    rc = dBias(datt.p, d, 0, d, M, lora_grads + go.c2b); if (rc) return rc;
     // d pre1 [B T, d] viewed as [B S, 2 d]: even frames t = 2 j take tap 1 of row j; odd frames t = 2 j + 1 take tap 0 of row j + 1 and tap 2 of row j
-    bf16_t* const dh1[2] = {w.dqkv[0], w.dqkv[1]};
+    const Grad& dh1 = dqkv;
     {
-      GemmSeg sg = seg_plain(w.datt[0], w.datt[1], d, e->conv2T[1], 0, d, M);
-      GemmOut o{}; o.hi = dh1[0]; o.lo = dh1[1]; o.ldo = 2 * d; o.n_valid = d; o.pre_hi = w.pre1[0]; o.pre_lo = w.pre1[1];
+      GemmSeg sg = seg_plain(datt.a, d, e->conv2T[1], 0, d, M);
+      GemmOut o{}; set_out(o, dh1.a); o.ldo = 2 * d; o.n_valid = d; o.pre_hi = w.conv.pre1.hi; o.pre_lo = w.conv.pre1.lo;
       rc = launch_gemm(e->ctx, M, d, &sg, 1, gterms, EPI_BF16_DGELU, o, s); if (rc) return rc;
       GemmSeg so[2];
-      so[0] = seg_plain(w.datt[0], w.datt[1], d, e->conv2T[0], 0, d, M);
+      so[0] = seg_plain(datt.a, d, e->conv2T[0], 0, d, M);
       so[0].rows_out = S; so[0].rows_in = S; so[0].row_mul = 1; so[0].row_add = 1;
-      so[1] = seg_plain(w.datt[0], w.datt[1], d, e->conv2T[2], 0, d, M);
-      GemmOut oo{}; oo.hi = dh1[0] + d; oo.lo = dh1[1] ? dh1[1] + d : nullptr; oo.ldo = 2 * d; oo.n_valid = d;
-      oo.pre_hi = w.pre1[0] + d; oo.pre_lo = w.pre1[1] ? w.pre1[1] + d : nullptr;
+      so[1] = seg_plain(datt.a, d, e->conv2T[2], 0, d, M);
+      const PlanePair pre1_odd = w.conv.pre1.at(d);
+      GemmOut oo{}; set_out(oo, act_offset(dh1.a, d)); oo.ldo = 2 * d; oo.n_valid = d; oo.pre_hi = pre1_odd.hi; oo.pre_lo = pre1_odd.lo;
       rc = launch_gemm(e->ctx, M, d, so, 2, gterms, EPI_BF16_DGELU, oo, s); if (rc) return rc;
     }
     for (int dt = 0; dt < 3; ++dt) {   // conv1.weight[n, c, dt]: the im2col row holds tap dt at columns dt n_mels ..
-      rc = dW(dh1[0], dh1[1], d, 0, d, w.a1, k1, dt * nm, nm, Mt, nullptr, g_c1w + dt, 3 * (int64_t)nm, 3); if (rc) return rc;
+      rc = dW(dh1.p, d, 0, d, w.conv.a1, k1, dt * nm, nm, Mt, nullptr, lora_grads + go.c1w + dt, 3 * (int64_t)nm, 3); if (rc) return rc;
     }
-    rc = dBias(dh1[0], dh1[1], d, 0, d, Mt, g_c1b); if (rc) return rc;
+    rc = dBias(dh1.p, d, 0, d, Mt, lora_grads + go.c1b); if (rc) return rc;
     if (exchange) {   // the lowest layer group together with the non-layer parameters in front of it
       const int G = e->comm_groups, Lr = c.n_layers;
       const int hi_layer = (int)(((int64_t)Lr + G - 1) / G);

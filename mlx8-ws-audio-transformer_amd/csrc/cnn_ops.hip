@@ -324,7 +324,7 @@ extern "C" int awt_op_conv1d(awt_ctx* c, const float* x, const float* w, const f
   // are discontinuous, so the forward's last bits decide masks: this is the format the model's forward convs run in (cnn_classifier.py).
   const bool two = terms != PREC_BF16;
   int rc = terms == PREC_F16X3 ? launch_split_planes(c, x, (int64_t)M * Cin, 1.0f, terms, kF8Act, xh, xl, nullptr, nullptr, s)
-                               : launch_split_f32(c, x, (int64_t)M * Cin, 1.0f, xh, two ? xl : nullptr, s);
+                               : launch_split_f32(c, x, (int64_t)M * Cin, 1.0f, PlanePair{xh, two ? xl : nullptr}, s);
   if (rc) return rc;
   rc = launch_pack_weight(c, w, Cout, Cin, 3, K, 0, 0, 1.0f, wh, two ? wl : nullptr, nullptr, terms, s); if (rc) return rc;   // k = tap Cin + ci
   GemmSeg sg[3];

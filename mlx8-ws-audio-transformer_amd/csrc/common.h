@@ -329,8 +329,17 @@ struct Carver {
 };
 // the hi / lo planes of a matrix of `elems` 2-byte elements, the commonest pieces; and the workspace that is nothing else
 // (a layout returns its struct as a braced list: the initialisers run left to right, bytes() last)
-struct PlanePair { bf16_t *hi, *lo; };
-inline PlanePair take_planes(Carver& cv, size_t elems) { return {cv.take<bf16_t>(elems * 2), cv.take<bf16_t>(elems * 2)}; }
+// PlanePair is the one host type for "hi plane + optional lo plane" (lo null: the one-plane precisions); at() moves both by `elems`, a null plane stays null
+struct PlanePair {
+  bf16_t *hi = nullptr, *lo = nullptr;
+  PlanePair at(int64_t elems) const { return {hi ? hi + elems : nullptr, lo ? lo + elems : nullptr}; }
+};
+inline PlanePair take_planes(Carver& cv, size_t elems, int planes = 2) {
+  PlanePair p;
+  p.hi = cv.take<bf16_t>(elems * 2);
+  if (planes == 2) p.lo = cv.take<bf16_t>(elems * 2);
+  return p;
+}
 struct PlanesWs { PlanePair p; size_t bytes; };
 inline PlanesWs planes_layout(void* base, size_t elems) { Carver cv(base); return {take_planes(cv, elems), cv.bytes()}; }
 
@@ -459,17 +468,15 @@ void awt_gemm_set_mfma16(int v);                    // tuning knob "gemm_mfma16"
 int launch_layernorm(awt_ctx* c, const float* x, const float* gamma, const float* beta, int M, int d, float eps,
                      float* out_f32, const Act& out, int prec, hipStream_t s);
 // q, k, v planes: bf16 [B, H, S, 64] (lo may be null for terms == 1); o: bf16 [B*S, H*64] hi/lo
-int launch_attention(awt_ctx* c, const bf16_t* q_hi, const bf16_t* q_lo, const bf16_t* k_hi, const bf16_t* k_lo,
-                     const bf16_t* v_hi, const bf16_t* v_lo, bf16_t* o_hi, bf16_t* o_lo, float* o_f32, float* lse, int B, int H,
+int launch_attention(awt_ctx* c, const PlanePair& q, const PlanePair& k, const PlanePair& v, const PlanePair& o, float* o_f32, float* lse, int B, int H,
                      int S, int terms, hipStream_t s);
-int launch_split_f32(awt_ctx* c, const float* x, int64_t n, float scale, bf16_t* hi, bf16_t* lo, hipStream_t s);
+int launch_split_f32(awt_ctx* c, const float* x, int64_t n, float scale, const PlanePair& out, hipStream_t s);
 // precision-aware form: PREC_BF16 / PREC_BF16X3 / PREC_F16X3 write p16 (+ lo16); PREC_F16F8 writes p16 (fp16), hi8 = e4m3(x 2^f8_exp),
 // lo8 = e4m3((x - fp16(x)) 2^(f8_exp + 11))
-struct F8Planes { bf16_t* p16; uint8_t* hi8; uint8_t* lo8; };
 int launch_split_planes(awt_ctx* c, const float* x, int64_t n, float scale, int prec, int f8_exp, bf16_t* p16, bf16_t* lo16, uint8_t* hi8,
                         uint8_t* lo8, hipStream_t s, char* ilv = nullptr);   // ilv (PREC_F16F8, f8_exp == kF8Act): split lines instead of the planes
-int launch_attention_f16f8(awt_ctx* c, const F8Planes& q, const F8Planes& k, const F8Planes& v, const F8Planes& o, float* o_f32,
-                           float* lse, int B, int H, int S, hipStream_t s, char* o_ilv = nullptr);   // o_ilv: the output as split lines (Act::ilv) instead of o
+// q, k, v, o: the p16 / hi8 / lo8 planes of each; o.ilv: the output as split lines instead of o's planes
+int launch_attention_f16f8(awt_ctx* c, const Act& q, const Act& k, const Act& v, const Act& o, float* o_f32, float* lse, int B, int H, int S, hipStream_t s);
 // weights: dst(row_off + n, col_off + k) = scale * src[n, c, dt], k = dt * C + c (taps = 1: plain [N, C]); dst is a
 // fragment-major matrix with ld / 32 k-steps (ld = its K, a multiple of 32; its row count a multiple of 16)
 // prec PREC_F16F8: hi = fp16 plane (w16f8_index order), lo = the hi8 plane, lo8 = the lo8 plane (w8_index order); else hi / lo in
@@ -503,19 +510,15 @@ bool attention_f16f8_reads_v8(bool with_lse);   // whether v's e4m3 images must 
 void awt_gemm_force_tile(int t);  // 0 auto, 64 / 128 / 256: tuning / tests (awt_tuning_set)
 
 // ---- backward-pass launchers
-int launch_attention_bwd(awt_ctx* c, const bf16_t* q_hi, const bf16_t* q_lo, const bf16_t* k_hi, const bf16_t* k_lo,
-                         const bf16_t* v_hi, const bf16_t* v_lo, const bf16_t* o_hi, const bf16_t* o_lo, const bf16_t* do_hi,
-                         const bf16_t* do_lo, const float* lse2, float* delta, bf16_t* g_hi, bf16_t* g_lo, int B, int H, int S,
-                         float qscale, int terms, int grad_terms, hipStream_t s);
-// dx = dres + LayerNorm_backward(dy; x, gamma)  (fp32), plus bf16 hi/lo planes of dx for the next GEMM; dres may be null
+int launch_attention_bwd(awt_ctx* c, const PlanePair& q, const PlanePair& k, const PlanePair& v, const PlanePair& o, const PlanePair& d_o, const float* lse2,
+                         float* delta, const PlanePair& g, int B, int H, int S, float qscale, int terms, int grad_terms, hipStream_t s);
+// dx = dres + LayerNorm_backward(dy; x, gamma)  (fp32), plus bf16 hi/lo planes of dx for the next GEMM (dxp; both may be null); dres may be null
 int launch_layernorm_bwd(awt_ctx* c, const float* dy, const float* x, const float* gamma, const float* dres, int M, int d, float eps,
-                         float* dx, bf16_t* dx_hi, bf16_t* dx_lo, hipStream_t s, float gscale = 1.0f, const Act* out8 = nullptr);   // gscale multiplies dy; out8: dx as f16f8 planes too
+                         float* dx, const PlanePair& dxp, hipStream_t s, float gscale = 1.0f, const Act* out8 = nullptr);   // gscale multiplies dy; out8: dx as f16f8 planes too
 int launch_transpose_f32(awt_ctx* c, const float* src, int N, int C, float* dst, hipStream_t s);   // dst [C, N] = src [N, C]^T
 // dst(row_off + c, col_off + n) = scale * src[n, c]   (transposed copy of an [N, C] fp32 matrix into fragment-major planes)
-int launch_pack_weight_t(awt_ctx* c, const float* src, int N, int C, int64_t ld, int row_off, int col_off, float scale, bf16_t* hi,
-                         bf16_t* lo, hipStream_t s);
+int launch_pack_weight_t(awt_ctx* c, const float* src, int N, int C, int64_t ld, int row_off, int col_off, float scale, const PlanePair& dst, hipStream_t s);
 // out[j * sj + n * sn] (+)= scale * sum_m X[m, xcol + j] * Y[m, ycol + n]   for j < r, n < ny  (LoRA dA / dB; fp32 result)
-int launch_outer_reduce(awt_ctx* c, const bf16_t* x_hi, const bf16_t* x_lo, int64_t ldx, int xcol, int r, const bf16_t* y_hi,
-                        const bf16_t* y_lo, int64_t ldy, int ycol, int ny, int M, float scale, float* out, int64_t sj, int64_t sn,
-                        float* partial, size_t partial_bytes, int accumulate, hipStream_t s);
+int launch_outer_reduce(awt_ctx* c, const PlanePair& x, int64_t ldx, int xcol, int r, const PlanePair& y, int64_t ldy, int ycol, int ny, int M, float scale,
+                        float* out, int64_t sj, int64_t sn, float* partial, size_t partial_bytes, int accumulate, hipStream_t s);
 size_t outer_reduce_partial_bytes(int M, int r, int ny);

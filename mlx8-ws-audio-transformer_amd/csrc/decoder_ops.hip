@@ -49,7 +49,7 @@ extern "C" int awt_weight_create(awt_ctx* c, const float* w, const float* bias, 
   if (!rc && with_transpose) {
     rc = dmalloc0((void**)&h->t_hi, plane);
     if (!rc && precision == PREC_BF16X3) rc = dmalloc0((void**)&h->t_lo, plane);
-    if (!rc) rc = launch_pack_weight_t(c, w, N, K, h->Np, 0, 0, 1.0f, h->t_hi, h->t_lo, s);
+    if (!rc) rc = launch_pack_weight_t(c, w, N, K, h->Np, 0, 0, 1.0f, PlanePair{h->t_hi, h->t_lo}, s);
   }
   if (!rc && bias) {
     rc = dmalloc0((void**)&h->bias, (size_t)h->Np * 4);
@@ -68,7 +68,7 @@ extern "C" int awt_weight_update(awt_ctx* c, awt_weight* h, const float* w, cons
   AWT_REQUIRE((bias != nullptr) == (h->bias != nullptr), AWT_ERR_INVALID, "weight_update: the handle was created with a bias iff one must be given");
   hipStream_t s = (hipStream_t)stream;
   int rc = launch_pack_weight(c, w, h->N, h->K, 1, h->K, 0, 0, 1.0f, h->hi, h->lo, nullptr, h->prec, s);
-  if (!rc && h->t_hi) rc = launch_pack_weight_t(c, w, h->N, h->K, h->Np, 0, 0, 1.0f, h->t_hi, h->t_lo, s);
+  if (!rc && h->t_hi) rc = launch_pack_weight_t(c, w, h->N, h->K, h->Np, 0, 0, 1.0f, PlanePair{h->t_hi, h->t_lo}, s);
   if (!rc && bias && hipMemcpyAsync(h->bias, bias, (size_t)h->N * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) rc = awt_fail(AWT_ERR_HIP, "weight_update: bias copy failed");
   return rc;
 }
@@ -563,14 +563,14 @@ extern "C" int awt_op_gelu_backward(awt_ctx* c, const float* x, const float* dy,
 }
 extern "C" int awt_op_layernorm_backward(awt_ctx* c, const float* dy, const float* x, const float* gamma, const float* dres, float* dx, int M,
                                          int d, float eps, void* stream) {
-  return launch_layernorm_bwd(c, dy, x, gamma, dres, M, d, eps, dx, nullptr, nullptr, (hipStream_t)stream);
+  return launch_layernorm_bwd(c, dy, x, gamma, dres, M, d, eps, dx, PlanePair{}, (hipStream_t)stream);
 }
 size_t param_grad_partial_bytes(int M, int d) { return (size_t)((M + kSlabRows - 1) / kSlabRows) * 2 * (size_t)d * 4; }
-int launch_param_grad(awt_ctx* c, const float* dy, const bf16_t* dy_hi, const bf16_t* dy_lo, int64_t ld, const float* x, int M, int d, float eps,
+int launch_param_grad(awt_ctx* c, const float* dy, const PlanePair& dyp, int64_t ld, const float* x, int M, int d, float eps,
                       float scale, int accumulate, float* dgamma, float* dbeta, float* partial, hipStream_t s) {
-  AWT_REQUIRE(c && (dy || dy_hi) && partial && M > 0 && d > 0 && d <= 64 * kColMaxChunks, AWT_ERR_INVALID, "param_grad: bad argument (d <= 1280)");
+  AWT_REQUIRE(c && (dy || dyp.hi) && partial && M > 0 && d > 0 && d <= 64 * kColMaxChunks, AWT_ERR_INVALID, "param_grad: bad argument (d <= 1280)");
   const int nslab = (M + kSlabRows - 1) / kSlabRows;
-  hipLaunchKernelGGL(ln_param_grad_kernel, dim3(nslab), dim3(256), 0, s, dy, x, M, d, eps, partial, dy_hi, dy_lo, ld);
+  hipLaunchKernelGGL(ln_param_grad_kernel, dim3(nslab), dim3(256), 0, s, dy, x, M, d, eps, partial, dyp.hi, dyp.lo, ld);
   hipLaunchKernelGGL(slab_sum_kernel, dim3((d + 255) / 256), dim3(256), 0, s, (const float*)partial, nslab, d, dgamma, dbeta, scale, accumulate);
   AWT_HIP_CHECK(hipGetLastError());
   return AWT_OK;
@@ -581,12 +581,12 @@ extern "C" int awt_op_layernorm_param_grad(awt_ctx* c, const float* dy, const fl
   AWT_REQUIRE(c && dy && x && dgamma && dbeta && workspace && M > 0 && d > 0 && d <= 64 * kColMaxChunks, AWT_ERR_INVALID,
               "op_layernorm_param_grad: bad argument (d <= 1280)");
   AWT_REQUIRE(ws_bytes >= awt_op_param_grad_workspace_bytes(M, d), AWT_ERR_WORKSPACE, "op_layernorm_param_grad: workspace too small");
-  return launch_param_grad(c, dy, nullptr, nullptr, 0, x, M, d, eps, 1.0f, 0, dgamma, dbeta, (float*)workspace, (hipStream_t)stream);
+  return launch_param_grad(c, dy, PlanePair{}, 0, x, M, d, eps, 1.0f, 0, dgamma, dbeta, (float*)workspace, (hipStream_t)stream);
 }
 extern "C" int awt_op_column_sums(awt_ctx* c, const float* a, float* sums, int M, int d, void* workspace, size_t ws_bytes, void* stream) {
   AWT_REQUIRE(c && a && sums && workspace && M > 0 && d > 0 && d <= 64 * kColMaxChunks, AWT_ERR_INVALID, "op_column_sums: bad argument (d <= 1280)");
   AWT_REQUIRE(ws_bytes >= awt_op_param_grad_workspace_bytes(M, d), AWT_ERR_WORKSPACE, "op_column_sums: workspace too small");
-  return launch_param_grad(c, a, nullptr, nullptr, 0, nullptr, M, d, 0.f, 1.0f, 0, nullptr, sums, (float*)workspace, (hipStream_t)stream);
+  return launch_param_grad(c, a, PlanePair{}, 0, nullptr, M, d, 0.f, 1.0f, 0, nullptr, sums, (float*)workspace, (hipStream_t)stream);
 }
 extern "C" int awt_op_cross_entropy(awt_ctx* c, const float* logits, const int64_t* labels, int M, int vocab, int ld, float* loss, float* dlogits,
                                     void* scratch /* >= (M + 1) * 4 bytes */, void* stream) {

@@ -442,12 +442,12 @@ int launch_layernorm(awt_ctx* c, const float* x, const float* gamma, const float
   return AWT_OK;
 }
 
-int launch_split_f32(awt_ctx* c, const float* x, int64_t n, float scale, bf16_t* hi, bf16_t* lo, hipStream_t s) {
-  AWT_REQUIRE(x && hi && n > 0 && n % 4 == 0, AWT_ERR_INVALID, "split: n must be a positive multiple of 4");
+int launch_split_f32(awt_ctx* c, const float* x, int64_t n, float scale, const PlanePair& out, hipStream_t s) {
+  AWT_REQUIRE(x && out.hi && n > 0 && n % 4 == 0, AWT_ERR_INVALID, "split: n must be a positive multiple of 4");
   ProfScope prof(c, AWT_PROF_OTHER, s, 0.0);
   const int64_t n4 = n / 4;
   int grid = (int)((n4 + 255) / 256); if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(split_kernel, dim3(grid), dim3(256), 0, s, x, n4, scale, hi, lo);
+  hipLaunchKernelGGL(split_kernel, dim3(grid), dim3(256), 0, s, x, n4, scale, out.hi, out.lo);
   AWT_HIP_CHECK(hipGetLastError());
   return AWT_OK;
 }
@@ -517,12 +517,12 @@ int launch_expand_conv_rows(awt_ctx* c, const float* g, const float* pos, int B,
 }
 
 int launch_layernorm_bwd(awt_ctx* c, const float* dy, const float* x, const float* gamma, const float* dres, int M, int d, float eps,
-                         float* dx, bf16_t* dx_hi, bf16_t* dx_lo, hipStream_t s, float gscale, const Act* out8) {
+                         float* dx, const PlanePair& dxp, hipStream_t s, float gscale, const Act* out8) {
   AWT_REQUIRE(dy && x && gamma && dx, AWT_ERR_INVALID, "layernorm_bwd: null argument");
   AWT_REQUIRE(M > 0 && d > 0 && d % 4 == 0 && d <= 64 * 4 * kLnMaxChunks, AWT_ERR_INVALID, "layernorm_bwd: d must be a multiple of 4 and <= 1280");
   AWT_REQUIRE(!out8 || (out8->p16 && out8->hi8 && out8->lo8), AWT_ERR_INVALID, "layernorm_bwd: the f16f8 output needs all three planes");
   ProfScope prof(c, AWT_PROF_LAYERNORM, s, 0.0);
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((M + 3) / 4), dim3(256), 0, s, dy, x, gamma, dres, M, d, eps, dx, dx_hi, dx_lo, gscale, out8 ? *out8 : Act{});
+  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((M + 3) / 4), dim3(256), 0, s, dy, x, gamma, dres, M, d, eps, dx, dxp.hi, dxp.lo, gscale, out8 ? *out8 : Act{});
   AWT_HIP_CHECK(hipGetLastError());
   return AWT_OK;
 }
@@ -534,10 +534,9 @@ int launch_transpose_f32(awt_ctx* c, const float* src, int N, int C, float* dst,
   return AWT_OK;
 }
 
-int launch_pack_weight_t(awt_ctx* c, const float* src, int N, int C, int64_t ld, int row_off, int col_off, float scale, bf16_t* hi,
-                         bf16_t* lo, hipStream_t s) {
-  AWT_REQUIRE(src && hi && N > 0 && C > 0 && ld >= col_off + N && ld % 32 == 0, AWT_ERR_INVALID, "pack_weight_t: bad shape");
-  hipLaunchKernelGGL(pack_weight_t_kernel, dim3((N + 31) / 32, (C + 31) / 32), dim3(256), 0, s, src, N, C, ld, row_off, col_off, scale, hi, lo);
+int launch_pack_weight_t(awt_ctx* c, const float* src, int N, int C, int64_t ld, int row_off, int col_off, float scale, const PlanePair& dst, hipStream_t s) {
+  AWT_REQUIRE(src && dst.hi && N > 0 && C > 0 && ld >= col_off + N && ld % 32 == 0, AWT_ERR_INVALID, "pack_weight_t: bad shape");
+  hipLaunchKernelGGL(pack_weight_t_kernel, dim3((N + 31) / 32, (C + 31) / 32), dim3(256), 0, s, src, N, C, ld, row_off, col_off, scale, dst.hi, dst.lo);
   AWT_HIP_CHECK(hipGetLastError());
   return AWT_OK;
 }
@@ -549,10 +548,9 @@ size_t outer_reduce_partial_bytes(int M, int r, int ny) {
   return (size_t)(nslab < kOrMaxBlocks ? nslab : kOrMaxBlocks) * R * ny * sizeof(float);
 }
 
-static int launch_outer_reduce_1(awt_ctx* c, const bf16_t* x_hi, const bf16_t* x_lo, int64_t ldx, int xcol, int r, const bf16_t* y_hi,
-                        const bf16_t* y_lo, int64_t ldy, int ycol, int ny, int M, float scale, float* out, int64_t sj, int64_t sn,
-                        float* partial, size_t partial_bytes, int accumulate, hipStream_t s) {
-  AWT_REQUIRE(x_hi && y_hi && out && partial && r > 0 && r <= 32 && ny > 0 && ny % 4 == 0 && ny <= 1024, AWT_ERR_INVALID, "outer_reduce: bad shape");
+static int launch_outer_reduce_1(awt_ctx* c, const PlanePair& x, int64_t ldx, int xcol, int r, const PlanePair& y, int64_t ldy, int ycol, int ny, int M, float scale,
+                                 float* out, int64_t sj, int64_t sn, float* partial, size_t partial_bytes, int accumulate, hipStream_t s) {
+  AWT_REQUIRE(x.hi && y.hi && out && partial && r > 0 && r <= 32 && ny > 0 && ny % 4 == 0 && ny <= 1024, AWT_ERR_INVALID, "outer_reduce: bad shape");
   AWT_REQUIRE(ldy % 4 == 0 && ycol % 4 == 0, AWT_ERR_INVALID, "outer_reduce: Y columns must be 8-byte aligned");
   AWT_REQUIRE(partial_bytes >= outer_reduce_partial_bytes(M, r, ny), AWT_ERR_WORKSPACE, "outer_reduce: partial buffer too small");
   ProfScope prof(c, AWT_PROF_OTHER, s, 0.0);
@@ -561,9 +559,9 @@ static int launch_outer_reduce_1(awt_ctx* c, const bf16_t* x_hi, const bf16_t* x
   const int R = r <= 8 ? 8 : (r <= 16 ? 16 : 32);
   // X columns beyond r inside the R-wide register block read neighbouring (valid, in-row) columns and are discarded below
   AWT_REQUIRE(xcol + R <= ldx, AWT_ERR_INVALID, "outer_reduce: X block exceeds its row");
-  if (R == 8) hipLaunchKernelGGL(outer_reduce_kernel<8>, dim3(nslab), dim3(256), 0, s, x_hi, x_lo, ldx, xcol, y_hi, y_lo, ldy, ycol, ny, M, partial);
-  else if (R == 16) hipLaunchKernelGGL(outer_reduce_kernel<16>, dim3(nslab), dim3(256), 0, s, x_hi, x_lo, ldx, xcol, y_hi, y_lo, ldy, ycol, ny, M, partial);
-  else hipLaunchKernelGGL(outer_reduce_kernel<32>, dim3(nslab), dim3(256), 0, s, x_hi, x_lo, ldx, xcol, y_hi, y_lo, ldy, ycol, ny, M, partial);
+  if (R == 8) hipLaunchKernelGGL(outer_reduce_kernel<8>, dim3(nslab), dim3(256), 0, s, x.hi, x.lo, ldx, xcol, y.hi, y.lo, ldy, ycol, ny, M, partial);
+  else if (R == 16) hipLaunchKernelGGL(outer_reduce_kernel<16>, dim3(nslab), dim3(256), 0, s, x.hi, x.lo, ldx, xcol, y.hi, y.lo, ldy, ycol, ny, M, partial);
+  else hipLaunchKernelGGL(outer_reduce_kernel<32>, dim3(nslab), dim3(256), 0, s, x.hi, x.lo, ldx, xcol, y.hi, y.lo, ldy, ycol, ny, M, partial);
   AWT_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(outer_reduce_final_kernel, dim3((r * ny + 31) / 32), dim3(256), 0, s, partial, nslab, R, r, ny, scale, out, sj, sn, accumulate);
   AWT_HIP_CHECK(hipGetLastError());
@@ -571,12 +569,11 @@ static int launch_outer_reduce_1(awt_ctx* c, const bf16_t* x_hi, const bf16_t* x
 }
 
 // Y blocks wider than the kernel's 1024 columns (256 threads x 4) are reduced in column chunks (Whisper large: d = 1280)
-int launch_outer_reduce(awt_ctx* c, const bf16_t* x_hi, const bf16_t* x_lo, int64_t ldx, int xcol, int r, const bf16_t* y_hi,
-                        const bf16_t* y_lo, int64_t ldy, int ycol, int ny, int M, float scale, float* out, int64_t sj, int64_t sn,
-                        float* partial, size_t partial_bytes, int accumulate, hipStream_t s) {
+int launch_outer_reduce(awt_ctx* c, const PlanePair& x, int64_t ldx, int xcol, int r, const PlanePair& y, int64_t ldy, int ycol, int ny, int M, float scale,
+                        float* out, int64_t sj, int64_t sn, float* partial, size_t partial_bytes, int accumulate, hipStream_t s) {
   for (int n0 = 0; n0 < ny; n0 += 1024) {
     const int nc = ny - n0 < 1024 ? ny - n0 : 1024;
-    int rc = launch_outer_reduce_1(c, x_hi, x_lo, ldx, xcol, r, y_hi, y_lo, ldy, ycol + n0, nc, M, scale, out + (int64_t)n0 * sn, sj, sn,
+    int rc = launch_outer_reduce_1(c, x, ldx, xcol, r, y, ldy, ycol + n0, nc, M, scale, out + (int64_t)n0 * sn, sj, sn,
                                    partial, partial_bytes, accumulate, s);
     if (rc) return rc;
   }

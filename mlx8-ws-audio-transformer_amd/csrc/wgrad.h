@@ -15,14 +15,14 @@ int launch_wgrad(awt_ctx* c, const WgradOperand& y, int N, const WgradOperand& x
 int wgrad_slabs(int M, int N, int K, int* slab_rows);       // slabs M is cut into: a function of the shape only
 size_t wgrad_partial_bytes(int M, int N, int K);
 // planes of dy * gelu'(pre), n elements (a multiple of 4)
-int launch_dgelu_planes(awt_ctx* c, const float* dy, const float* pre, int64_t n, bf16_t* hi, bf16_t* lo, hipStream_t s);
+int launch_dgelu_planes(awt_ctx* c, const float* dy, const float* pre, int64_t n, const PlanePair& out, hipStream_t s);
 // dst [N, C] = src[:, :, tap] of a Conv1d weight [N, C, 3]
 int launch_conv_tap(awt_ctx* c, const float* src, int N, int C, int tap, float* dst, hipStream_t s);
 
 // Column reductions over M rows (decoder_ops.hip, the row kernels behind awt_op_column_sums / awt_op_layernorm_param_grad):
 //   dbeta[c] (+)= scale * sum_m g[m, c],   dgamma[c] (+)= scale * sum_m g[m, c] xhat[m, c]   (x null: dbeta only)
-// with g either fp32 rows `dy` [M, d] or the plane pair (dy_hi, dy_lo) of pitch ld (columns col0 .. col0 + d - 1); d <= 1280.
+// with g either fp32 rows `dy` [M, d] or the plane pair dyp of pitch ld (its first d columns); d <= 1280.
 // partial: >= param_grad_partial_bytes(M, d) bytes.
 size_t param_grad_partial_bytes(int M, int d);
-int launch_param_grad(awt_ctx* c, const float* dy, const bf16_t* dy_hi, const bf16_t* dy_lo, int64_t ld, const float* x, int M, int d, float eps,
+int launch_param_grad(awt_ctx* c, const float* dy, const PlanePair& dyp, int64_t ld, const float* x, int M, int d, float eps,
                       float scale, int accumulate, float* dgamma, float* dbeta, float* partial, hipStream_t s);

@@ -228,9 +228,9 @@ int launch_wgrad(awt_ctx* c, const WgradOperand& y, int N, const WgradOperand& x
   return AWT_OK;
 }
 
-int launch_dgelu_planes(awt_ctx* c, const float* dy, const float* pre, int64_t n, bf16_t* hi, bf16_t* lo, hipStream_t s) {
-  AWT_REQUIRE(c && dy && pre && hi && n > 0 && n % 4 == 0, AWT_ERR_INVALID, "dgelu_planes: bad argument");
-  hipLaunchKernelGGL(dgelu_planes_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, dy, pre, n / 4, hi, lo);
+int launch_dgelu_planes(awt_ctx* c, const float* dy, const float* pre, int64_t n, const PlanePair& out, hipStream_t s) {
+  AWT_REQUIRE(c && dy && pre && out.hi && n > 0 && n % 4 == 0, AWT_ERR_INVALID, "dgelu_planes: bad argument");
+  hipLaunchKernelGGL(dgelu_planes_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, dy, pre, n / 4, out.hi, out.lo);
   AWT_HIP_CHECK(hipGetLastError());
   return AWT_OK;
 }
@@ -271,8 +271,8 @@ extern "C" int awt_op_weight_grad(awt_ctx* c, const float* dy, int ldy, int ycol
   AWT_REQUIRE(ws_bytes >= awt_op_weight_grad_workspace_bytes(M, rows_x, ldy, ldx, N, K), AWT_ERR_WORKSPACE, "op_weight_grad: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const OpWgradWs w = op_wgrad_layout(workspace, M, rows_x, ldy, ldx, N, K);
-  int rc = launch_split_f32(c, dy, (int64_t)M * ldy, 1.0f, w.y.hi, w.y.lo, s); if (rc) return rc;
-  rc = launch_split_f32(c, x, (int64_t)rows_x * ldx, 1.0f, w.x.hi, w.x.lo, s); if (rc) return rc;
+  int rc = launch_split_f32(c, dy, (int64_t)M * ldy, 1.0f, w.y, s); if (rc) return rc;
+  rc = launch_split_f32(c, x, (int64_t)rows_x * ldx, 1.0f, w.x, s); if (rc) return rc;
   const WgradOperand yo{w.y.hi, w.y.lo, ldy, ycol}, xo{w.x.hi, w.x.lo, ldx, xcol};
   const WgradRowMap map{rows_out, rows_in, row_mul, row_add};
   return launch_wgrad(c, yo, N, xo, K, M, mapped ? &map : nullptr, terms, scale, out, sn, sk, accumulate, w.partial, w.partial_bytes, s);
