@@ -13,7 +13,11 @@
  *    allocated in *_create / *_set_weight / awt_*_prepare; only a front-end configuration that was never prepared is
  *    built at its first use);
  *  - all work is enqueued on the caller's hipStream_t (passed as void*; NULL = default stream);
- *    no hidden synchronisation except where a function says so (awt_prof_collect);
+ *    no hidden synchronisation except where a function says so (awt_prof_collect; the creation and upload calls awt_weight_create and
+ *    awt_encoder_set_weight; awt_op_linear / awt_op_linear_fused with terms 4 and 5 outside a stream capture).  Every other function with a
+ *    stream parameter can be recorded into a HIP graph (hipStreamBeginCapture on that stream) and replayed on new contents of the same buffers
+ *    bit-identically, once the tables and weights it uses exist, i.e. after one ordinary call; the communicator's calls, which use a second
+ *    stream, are the exception.  tests/graph_capture.py lists both groups and tests/test_gpu_graph_capture.py holds every operator to it;
  *  - a handle is not thread-safe; distinct handles are independent; one awt_ctx per (process, device).
  */
 #ifndef AWT_H_
@@ -263,7 +267,11 @@ int awt_conv_stem_positions(int n_ctx, int max_valid);
 
 /* ------------------------------------------------------------------------------------------------------
  * Single-operator entry points (what the encoder is made of; used by the per-kernel parity tests).
- * Row-major float32 in / out; bf16 splitting happens inside.  `terms` = 1 or 3 as in awt_encoder_cfg. */
+ * Row-major float32 in / out; bf16 splitting happens inside.  `terms` = 1 or 3 as in awt_encoder_cfg.
+ * awt_op_linear (and awt_op_linear_fused) pack w on every call.  With terms 4 and 5 that pack also looks for fp16-exact weights as awt_encoder_set_weight
+ * does and, to read the one flag back, synchronises `stream` -- except while `stream` is recording into a HIP graph, where a host read is not possible:
+ * there the probe is left out and the GEMM keeps every cross term, which is the form any weight that is not fp16-exact takes anyway (for one that is,
+ * the extra product is with an all-zero plane).  Terms 1 to 3 never synchronise. */
 int awt_op_linear(awt_ctx* c, const float* x /*[M,K]*/, const float* w /*[N,K]*/, const float* bias /*[N] or NULL*/,
                   float* y /*[M,N]*/, int M, int N, int K, int terms, void* workspace, size_t ws_bytes, void* stream);
 size_t awt_op_linear_workspace_bytes(int M, int N, int K);
@@ -348,7 +356,8 @@ size_t awt_op_linear_fused_workspace_bytes(int x_rows, int ldx, int N, int ldw);
 typedef struct awt_weight awt_weight;
 /* Packs a frozen nn.Linear weight [N, K] (+ bias [N] or NULL) once: N is zero-padded to a multiple of 128 (awt_weight_padded_rows),
  * K must be a multiple of 64; precision 1 (bf16) or 3 (bf16x3); with_transpose keeps the transposed copy that
- * awt_linear_backward_input needs (then K must be a multiple of 128). */
+ * awt_linear_backward_input needs (then K must be a multiple of 128).  Creation time: the planes are hipMalloc'd and cleared with a blocking
+ * hipMemset, so this call synchronises the device and cannot be part of a stream capture; the pack itself runs on `stream`. */
 int awt_weight_create(awt_ctx* c, const float* w, const float* bias, int N, int K, int precision, int with_transpose, void* stream,
                       awt_weight** out);
 void awt_weight_destroy(awt_weight* w);

@@ -972,8 +972,12 @@ int op_linear_pack_weight(awt_ctx* c, const float* w, int N, int K, int terms, c
       if (hipMemsetAsync(ws.s16, 0, ws.s_bytes, s) != hipSuccess) return awt_fail(AWT_ERR_HIP, "op_linear: weight copy reset failed");
     }
   }
-  // as awt_encoder_set_weight does: fp16-exact weights take the GEMM without the x_hi w_lo product
-  if (terms == PREC_F16F8 || terms == PREC_F16X3) return probe_exact16(c, "op_linear", w, pw, N, K, 0, terms, ws.flag, 0, 1, s);
+  // as awt_encoder_set_weight does: fp16-exact weights take the GEMM without the x_hi w_lo product.  The probe reads one flag back on the host and
+  // synchronises `s`, which a stream that is recording into a HIP graph cannot do: there the weight is packed without the probe and the GEMM keeps
+  // every cross term -- the form of any weight that is not fp16-exact, and for one that is, a product with an all-zero plane more
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  const bool probe = (terms == PREC_F16F8 || terms == PREC_F16X3) && !(hipStreamIsCapturing(s, &capturing) == hipSuccess && capturing == hipStreamCaptureStatusActive);
+  if (probe) return probe_exact16(c, "op_linear", w, pw, N, K, 0, terms, ws.flag, 0, 1, s);
   return pack(c, w, pw, N, K, 1, 0, 0, terms, s);     // fragment-major
 }
 // awt_op_attention's workspace: the two 2-byte planes of q, of k and of v
