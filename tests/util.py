@@ -34,7 +34,8 @@ GUARD = 4096
 
 
 def guarded(shape, dtype, device="cuda"):
-    """(buffer, tensor): a tensor of 0xFF bytes (NaN in every floating-point format) between two 4 KiB guards of 0xA5 bytes."""
+    """(buffer, tensor): a tensor of 0xFF bytes (NaN in every floating-point format) between two 4 KiB guards of 0xA5 bytes.
+    For a whole operator call -- inputs, outputs and the workspaces its wrapper allocates -- see tests/hostile_alloc.py (`run_fenced`)."""
     import torch
 
     n = torch.empty(shape, dtype=dtype).numel() * torch.empty((), dtype=dtype).element_size()
