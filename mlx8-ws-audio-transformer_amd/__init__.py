@@ -10,3 +10,6 @@ from .weights import (CONFIGS, EncoderConfig, LoraSpec, config, init_encoder_wei
 from .cnn_classifier import CNNUrbanSound8KClassifier, eval_or_test_cnn, train_cnn  # noqa: F401,E402
 from .waveform_classifier import CNNWaveformClassifier, UrbanSoundRawDataset, train_waveform_classifier  # noqa: F401,E402
 from .music2midi import CrossAttentionAdapter, MusicTranscriptionModel, Qwen3Cache, Qwen3Config, Qwen3Decoder  # noqa: F401,E402
+from .optim import FusedAdamW  # noqa: F401,E402
+from .music2midi_train import (collate_fn, load_checkpoint, save_checkpoint, setup_optimizers, train_music2midi,  # noqa: F401,E402
+                               validate_model)

@@ -13,6 +13,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AWT_LIB") or os.path.join(HERE, "libawt.so")   # AWT_LIB: kernel-variant A/B builds (tools/)
 HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "awt.h")
+OPTIM_HEADER_PATH = os.path.join(os.path.dirname(HERE), "include", "awt_optim.h")   # the optimizer phase: a header of its own (its top comment says why)
 
 AWT_OK = 0
 AWT_ERR_VALUE = -5
@@ -168,6 +169,10 @@ _SIGNATURES = {
     "awt_op_bn_relu_pool_backward_workspace_bytes": (_sz, [_i, _i, _i]),
     "awt_op_bn_relu_pool_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "awt_op_conv1d_framed": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    # include/awt_optim.h
+    "awt_optim_chunk_elems": (_i, []),
+    "awt_op_adamw_workspace_bytes": (_sz, [_i64]),
+    "awt_op_adamw_step": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _i, _vp, _f, _vp, _vp, _sz, _vp]),
     "awt_tuning_set": (_i, [C.c_char_p, _i]),
     "awt_prof_enable": (_i, [_vp, _i]),
     "awt_prof_collect": (_i, [_vp, _i, C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(C.c_double)]),
@@ -178,9 +183,9 @@ _lock = threading.Lock()
 _ctx = {}
 
 
-def declared_symbols() -> list:
-    """Function names declared in include/awt.h (used by the CPU-side export test)."""
-    text = open(HEADER_PATH).read()
+def declared_symbols(header: str = HEADER_PATH) -> list:
+    """Function names declared in include/awt.h, or in another header of include/ (used by the CPU-side export tests)."""
+    text = open(header).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(awt_[a-z0-9_]+)\s*\(", text)))
 

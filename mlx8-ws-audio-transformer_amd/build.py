@@ -1,4 +1,4 @@
-"""Builds libawt.so (the C-ABI HIP library, include/awt.h) in-tree for gfx950.
+"""Builds libawt.so (the C-ABI HIP library, include/awt.h and include/awt_optim.h) in-tree for gfx950.
 
     python -m mlx8_ws_audio_transformer_amd.build [--force]
 
@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libawt.so")
-SOURCES = ["awt_api.hip", "logmel.hip", "gemm.hip", "attention.hip", "attention_f8.hip", "attention_bwd.hip", "elementwise.hip", "comm.hip", "decoder_ops.hip", "decoder_grad.hip", "bmm.hip", "decode_select.hip", "alignment.hip", "wgrad.hip", "cnn_ops.hip", "cross_attention.hip", "qwen_ops.hip", "gemv.hip"]
+SOURCES = ["awt_api.hip", "logmel.hip", "gemm.hip", "attention.hip", "attention_f8.hip", "attention_bwd.hip", "elementwise.hip", "comm.hip", "decoder_ops.hip", "decoder_grad.hip", "bmm.hip", "decode_select.hip", "alignment.hip", "wgrad.hip", "cnn_ops.hip", "cross_attention.hip", "qwen_ops.hip", "gemv.hip", "optim.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 
@@ -30,7 +30,7 @@ def _stale(target: str, deps) -> bool:
 
 def _compile(src: str, force: bool) -> str:
     obj = os.path.join(OBJ, src.replace(".hip", ".o"))
-    deps = [os.path.join(CSRC, src), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "comm.h"), os.path.join(CSRC, "gemm_pp.h"), os.path.join(CSRC, "wgrad.h"), os.path.join(HERE, "..", "include", "awt.h")]
+    deps = [os.path.join(CSRC, src), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "comm.h"), os.path.join(CSRC, "gemm_pp.h"), os.path.join(CSRC, "wgrad.h"), os.path.join(HERE, "..", "include", "awt.h"), os.path.join(HERE, "..", "include", "awt_optim.h")]
     if force or _stale(obj, deps):
         cmd = [HIPCC, *FLAGS, "-c", os.path.join(CSRC, src), "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -4,7 +4,14 @@
 positions of a stub audio tower -- forward + backward + AdamW step of `MusicTranscriptionModel`, beside a torch fp32 eager restatement of the same step
 (same parameters, same trainable set, torch's own scaled_dot_product_attention with the causal mask) on the same GPU.  GPU box only.
 
-    python tools/music2midi_train_bench.py [--steps 3] [--rounds 5] [--precision bf16x3] [--layers 28] [--out profiles/music2midi_train_bench.json]
+    python tools/music2midi_train_bench.py [--steps 3] [--rounds 5] [--precision bf16x3] [--layers 28] [--optimizer torch] [--out profiles/music2midi_train_bench.json]
+    python tools/music2midi_train_bench.py --optim-split [--out profiles/music2midi_optim_bench.json]          
+
+--optimizer picks what steps the native model: torch (torch.optim.AdamW, the default and section 4.13's measurement), torch_fused (torch.optim.AdamW(fused=True))
+or fused (optim.FusedAdamW).  --optim-split times the native step alone, in three phases between HIP events -- re-pack of the stepped weights (what the next
+forward's `_pack()` does), forward + backward, optimizer phase (global-norm clip at 1.0 + AdamW step, the reference loop's two calls) -- once per optimizer kind
+on the same model in the same run: the kinds' windows alternate, medians over the rounds, max / min of the windows as the spread.  The fused phase's bytes/s
+count 32 B per stepped element (4 read for the norm, 16 read and 12 written by the update) against the 6.29 TB/s a float4 copy reaches on this part.
 
 Step times are medians over `rounds` windows of `steps` steps each, by HIP events, after a warm-up; native and torch windows alternate; max / min of the
 windows is the spread.  The shader clock and package power are read from sysfs while the native step loops.  The per-kernel-class shares come from the
@@ -19,6 +26,7 @@ import argparse
 import dataclasses
 import json
 import os
+import statistics
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -28,6 +36,7 @@ import torch.nn.functional as F
 import bench
 from mlx8_ws_audio_transformer_amd import CrossAttentionAdapter, _lib, ops
 from mlx8_ws_audio_transformer_amd.music2midi import MusicTranscriptionModel, Qwen3Config, Qwen3Decoder
+from mlx8_ws_audio_transformer_amd.optim import FusedAdamW
 from music2midi_adapter_bench import TorchAdapter, medians
 
 B, L, SA, AUDIO_DIM, K_TRAINED = 4, 512, 1500, 512, 4
@@ -66,12 +75,80 @@ def visited_share(Lq, T):
     return staged, multiplied, dkv
 
 
+def make_optimizer(kind, params):
+    if kind == "fused":
+        return FusedAdamW(params, lr=1e-4, weight_decay=1e-4)
+    return torch.optim.AdamW(params, lr=1e-4, weight_decay=1e-4, fused=True if kind == "torch_fused" else None)
+
+
+COPY_BYTES_PER_S = 6.29e12          # float4 copy on this part
+FUSED_BYTES_PER_ELEMENT = 32        # 4 read by the norm pass, 16 read and 12 written by the update
+
+
+def optimizer_split(model, params, ids, mask, a):
+    """The native step in three phases per optimizer kind (the module docstring); prints and writes one JSON line."""
+    kinds = ("torch", "torch_fused", "fused")
+    opts = {k: make_optimizer(k, params) for k in kinds}
+    phases = ("repack_ms", "forward_backward_ms", "optimizer_ms")
+
+    def window(kind, steps):
+        opt, marks = opts[kind], []
+        for _ in range(steps):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            ev[0].record()
+            model.text_decoder._pack()
+            ev[1].record()
+            opt.zero_grad(set_to_none=True)
+            model([None] * B, 16000, ids, mask).backward()
+            ev[2].record()
+            if kind == "fused":
+                opt.step(max_norm=1.0)
+            else:
+                torch.nn.utils.clip_grad_norm_(params, 1.0)
+                opt.step()
+            ev[3].record()
+            marks.append(ev)
+        torch.cuda.synchronize()
+        return [sum(ev[i].elapsed_time(ev[i + 1]) for ev in marks) / steps for i in range(3)]
+
+    for k in kinds:
+        window(k, 2)                                                       # warm-up: state, tables and the first re-pack come into being
+    times = {k: [] for k in kinds}
+    for _ in range(a.rounds):
+        for k in kinds:
+            times[k].append(window(k, a.steps))
+    res, spread = {}, {}
+    for k in kinds:
+        cols = list(zip(*times[k]))
+        res[k] = {ph: round(statistics.median(c), 4) for ph, c in zip(phases, cols)}
+        res[k]["step_ms"] = round(statistics.median(sum(w) for w in times[k]), 4)
+        spread[k] = {ph: round(max(c) / min(c), 3) for ph, c in zip(phases, cols)}
+    elements = sum(p.numel() for p in params)
+    fused_bps = FUSED_BYTES_PER_ELEMENT * elements / (res["fused"]["optimizer_ms"] * 1e-3)
+    line = json.dumps({"metric": f"music2midi training step at Qwen3-0.6B's shape ({a.layers} layers, top {min(K_TRAINED, a.layers)} trained, tied head; adapter audio_dim "
+                                 f"{AUDIO_DIM} over {SA} positions), B {B}, L {L}, precision {a.precision}, split by HIP events into re-pack of the stepped weights, forward + "
+                                 "backward, and optimizer phase (global-norm clip at 1.0 + AdamW step), per optimizer kind on the same model in the same run (median ms over "
+                                 "alternating windows)",
+                       "results": res, "max_over_min_of_windows": spread, "steps": a.steps, "rounds": a.rounds,
+                       "stepped_elements": elements, "stepped_tensors": len(params),
+                       "fused_over_torch_optimizer_phase": round(res["fused"]["optimizer_ms"] / res["torch"]["optimizer_ms"], 4),
+                       "fused_over_torch_fused_optimizer_phase": round(res["fused"]["optimizer_ms"] / res["torch_fused"]["optimizer_ms"], 4),
+                       "fused_bytes_per_s_at_32B_per_element": round(fused_bps, -9), "fraction_of_float4_copy_6p29TBps": round(fused_bps / COPY_BYTES_PER_S, 4),
+                       "device": torch.cuda.get_device_name(0)})
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--precision", default="bf16x3", choices=["bf16x3", "bf16"])
     ap.add_argument("--layers", type=int, default=28)
+    ap.add_argument("--optimizer", default="torch", choices=["torch", "fused", "torch_fused"])
+    ap.add_argument("--optim-split", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.manual_seed(0)
@@ -83,7 +160,10 @@ def main():
     model = MusicTranscriptionModel(lambda w, sr: audio, adapter, dec)
     ids = torch.randint(0, cfg.vocab_size, (B, L), device=dev)
     mask = torch.ones(B, L, dtype=torch.long, device=dev)
-    opt = torch.optim.AdamW([p for p in model.parameters() if p.requires_grad], lr=1e-4, weight_decay=1e-4)
+    trainable = [p for p in model.parameters() if p.requires_grad]
+    if a.optim_split:
+        return optimizer_split(model, trainable, ids, mask, a)
+    opt = make_optimizer(a.optimizer, trainable)
 
     # the torch restatement: its own copies of every parameter, the same trainable set
     t_adapter = TorchAdapter().to(dev)
@@ -162,7 +242,7 @@ def main():
                                  f"layers, final norm and head trained; adapter audio_dim {AUDIO_DIM} over {SA} encoder positions), B {B}, L {L}, seeded weights, precision "
                                  f"{a.precision}: forward + backward + AdamW step, native beside a torch fp32 eager restatement on the same GPU (median ms over alternating "
                                  "windows, HIP events)",
-                       "results": res, "max_over_min_of_windows": spread, "steps": a.steps, "rounds": a.rounds,
+                       "results": res, "max_over_min_of_windows": spread, "steps": a.steps, "rounds": a.rounds, "native_optimizer": a.optimizer,
                        "loss_first_step_native_torch": first, "loss_last_step_native_torch": last,
                        "kernel_classes_native_step": classes,
                        "attention_backward_Lq512_T512_B4_H16": att, "attention_backward_max_over_min": att_spread,
