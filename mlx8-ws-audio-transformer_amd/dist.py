@@ -98,6 +98,9 @@ class AwtComm:
             _lib.lib().awt_comm_destroy(self.handle)
             self.handle = None
 
+    def __reduce_ex__(self, protocol):
+        raise TypeError("AwtComm owns a library handle (awt_comm) that close() / __del__ free: it cannot be copied or pickled; construct it on every rank")
+
     def __del__(self):
         try:
             self.close()

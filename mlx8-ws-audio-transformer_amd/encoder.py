@@ -169,7 +169,6 @@ class NativeWhisperEncoder(nn.Module):
         self.lora = lora
         self.trainable = trainable
         self.train_base = train_base
-        self._base_layout = None
         self.config = SimpleNamespace(d_model=cfg.d_model, encoder_layers=cfg.layers, encoder_attention_heads=cfg.heads,
                                       encoder_ffn_dim=cfg.ffn, num_mel_bins=cfg.n_mels,
                                       max_source_positions=cfg.max_source_positions)
@@ -185,21 +184,24 @@ class NativeWhisperEncoder(nn.Module):
             for name, shape in lora_param_shapes(cfg, lora):
                 t = torch.from_numpy(lw[name]) if lw is not None else torch.zeros(shape)
                 _attach(self, name, nn.Parameter(t.to(dev), requires_grad=True), self._epoch)
-        self._handle = None
         self._chunk = chunk_clips
-        self._synced: Dict[str, int] = {}
-        self._param_cache = None
-        self._param_ids = None
-        self._ws: Optional[torch.Tensor] = None
-        # bound gradient buffer (bind_grad_buffer) and the communicator its exchange runs on (set_comm)
-        self._grad_flat: Optional[torch.Tensor] = None
-        self._grad_params: list = []
-        self._grad_views: list = []
-        self._grad_fresh = True
-        self._comm = None
+        self.__dict__.update(self._no_library_state())
         self.grad_sync = True       # False: this backward only accumulates (all but the last micro-batch of a step)
 
     # ------------------------------------------------------------------------------------------------ plumbing
+    @staticmethod
+    def _no_library_state() -> dict:
+        """Everything the module holds of the library, before any of it exists: the handle and the versions pushed to it (`_synced`: name -> version),
+        the cached parameter list, the workspace, the gradient layout, the bound gradient buffer (bind_grad_buffer) and the communicator its
+        exchange runs on (set_comm)."""
+        return dict(_handle=None, _synced={}, _param_cache=None, _param_ids=None, _ws=None, _base_layout=None,
+                    _grad_flat=None, _grad_params=[], _grad_views=[], _grad_fresh=True, _comm=None)
+
+    def __getstate__(self):
+        """A copy (copy.copy, copy.deepcopy, pickle) starts without library state and builds its own handle at first use: the handle is freed by
+        __del__, so two modules must never hold the same one.  Parameters, configuration and `precision` are copied."""
+        return {**self.__dict__, **self._no_library_state()}
+
     @property
     def device(self) -> torch.device:
         return next(self.parameters()).device

@@ -26,11 +26,11 @@ autograd_ops.py, shared with the classifiers; `_CrossAttention` here):
 The two residual adds, the dtype casts and the row slices of `in_proj_weight` are element-wise / view ops of torch under autograd.  There is no
 torch fallback for any operator above: without libawt or without a GPU the first call raises.
 
-`Qwen3Decoder` and `MusicTranscriptionModel` (further down; DESIGN.md sections 4.12 and 4.13) are the stock Qwen decoder and the model around all three
-pieces: teacher-forced loss and logits, and `generate` with a KV cache, on awt_op_rmsnorm / awt_op_qk_norm_rope / awt_op_causal_attention / awt_op_silu_mul
-and the packed-weight GEMMs.  Built with `trainable_layers=K` the decoder also trains, under the reference's rule (the top K layers, the final norm, the
-output head), and passes the gradient of `inputs_embeds` down through every layer to the adapter: `_Qwen3Graph` is one autograd node whose backward is
-libawt calls (awt_op_causal_attention_backward, awt_op_qk_norm_rope_backward, awt_op_rmsnorm_backward / _param_grad, awt_op_silu_mul_backward,
+`Qwen3Decoder` and `MusicTranscriptionModel` (further down; DESIGN.md sections 4.12 and 4.13) are the stock Qwen decoder and the model around all three pieces:
+teacher-forced loss and logits, and `generate` with a KV cache, on awt_op_rmsnorm / awt_op_qk_norm_rope / awt_op_causal_attention / awt_op_silu_mul and the packed-weight
+GEMMs (operands kept by native_decoder.PackedSet; a copy of the decoder packs its own).  Built with `trainable_layers=K` the decoder also trains, under the reference's rule
+(the top K layers, the final norm, the output head), and passes the gradient of `inputs_embeds` down through every layer to the adapter: `_Qwen3Graph` is one autograd node
+whose backward is libawt calls (awt_op_causal_attention_backward, awt_op_qk_norm_rope_backward, awt_op_rmsnorm_backward / _param_grad, awt_op_silu_mul_backward,
 awt_linear_backward_input, awt_op_weight_grad, awt_op_embed_backward).
 
 `encode_audio(audio_features)` returns the projected key / value buffer `audio_kv` [B, Sa, 2 text_dim]; `forward(text, audio_kv=audio_kv)` reuses it.
@@ -46,6 +46,7 @@ import torch.nn as nn
 
 from . import _lib, ops
 from .autograd_ops import AlignedLinear, Gelu, LayerNorm
+from .native_decoder import PackedLinear, PackedSet, cross_entropy, embed_backward
 
 HEAD_DIM = 128            # csrc/cross_attention.hip
 MAX_TEXT_DIM = 1280       # the LayerNorm kernels' row limit
@@ -234,8 +235,7 @@ class Qwen3Decoder(nn.Module):
         self.model.norm = _Weight(d, ones=True)
         if not c.tie_word_embeddings:
             self.lm_head = _Weight(c.vocab_size, d)
-        self._packed = None
-        self._versions = None
+        self._packed = PackedSet()
         self._rope = None
         if trainable_layers is not None:
             for p in self._reference_trainable():
@@ -270,7 +270,7 @@ class Qwen3Decoder(nn.Module):
         if not self.config.tie_word_embeddings:
             self.lm_head.weight = resized(self.lm_head.weight)
         self.config = dataclasses.replace(self.config, vocab_size=n)
-        self._packed = None
+        self._packed.invalidate()
         return emb
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
@@ -278,41 +278,30 @@ class Qwen3Decoder(nn.Module):
         if self.config.tie_word_embeddings:
             sd.pop("lm_head.weight", None)                                 # HF lists the tied head as a second name of the embedding
         out = super().load_state_dict(sd, strict=strict, **kw)
-        self._packed = None
+        self._packed.invalidate()
         return out
 
     def _apply(self, fn, *a, **kw):
-        self._packed, self._rope = None, None
+        self._packed.invalidate()
+        self._rope = None
         return super()._apply(fn, *a, **kw)
 
     def _pack(self) -> dict:
-        """The fused q | k | v, o, gate | up and down projections of every layer and the output head as `awt_weight` handles.  Inference only: packed once.
-        Trainable: with the transpose planes of `backward_input`, and brought up to date when a parameter changed -- the same Parameter objects at new versions
-        (an optimizer step) re-pack only the handles made of a changed parameter, in place; anything else builds every handle."""
+        """The fused q | k | v, o, gate | up and down projections of every layer and the output head as `awt_weight` handles (native_decoder.PackedSet).
+        Inference only: packed once.  Trainable: with the transpose planes of `backward_input`, and following every parameter."""
         train = self.trainable_layers is not None
-        vers = tuple((id(p), p._version) for p in self.parameters()) if train else None      # identity too: a replaced Parameter starts at version 0 again
-        if self._packed is not None and self._versions == vers:
-            return self._packed
-        from .native_decoder import PackedLinear
-        plan = []                                                          # (slot, key, the parameters it is made of, what to pack)
-        fresh = self._packed is None or tuple(i for i, _ in self._versions) != tuple(i for i, _ in vers)
-        pk = {"layers": [{} for _ in self.model.layers]} if fresh else self._packed
-        for layer, slot in zip(self.model.layers, pk["layers"]):
-            att, mlp = layer.self_attn, layer.mlp
-            plan += [(slot, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), lambda att=att: torch.cat([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight])),
-                     (slot, "o", (att.o_proj.weight,), lambda att=att: att.o_proj.weight),
-                     (slot, "gu", (mlp.gate_proj.weight, mlp.up_proj.weight), lambda mlp=mlp: torch.cat([mlp.gate_proj.weight, mlp.up_proj.weight])),
-                     (slot, "down", (mlp.down_proj.weight,), lambda mlp=mlp: mlp.down_proj.weight)]
-        plan.append((pk, "lm_head", (self._head_weight(),), self._head_weight))
-        changed = set() if fresh else {i for (i, v), (_, v0) in zip(vers, self._versions) if v != v0}
-        with torch.no_grad():
-            for slot, key, sources, make in plan:
-                if fresh:
-                    slot[key] = PackedLinear(make(), None, self.precision, backward=train)
-                elif any(id(p) in changed for p in sources):
-                    slot[key].update(make(), None)
-        self._packed, self._versions = pk, vers
-        return pk
+
+        def plan():
+            plan = []
+            for i, layer in enumerate(self.model.layers):
+                att, mlp, where = layer.self_attn, layer.mlp, ("layers", i)
+                plan += [(where, "qkv", (att.q_proj.weight, att.k_proj.weight, att.v_proj.weight), lambda att=att: (torch.cat([att.q_proj.weight, att.k_proj.weight, att.v_proj.weight]), None)),
+                         (where, "o", (att.o_proj.weight,), lambda att=att: (att.o_proj.weight, None)),
+                         (where, "gu", (mlp.gate_proj.weight, mlp.up_proj.weight), lambda mlp=mlp: (torch.cat([mlp.gate_proj.weight, mlp.up_proj.weight]), None)),
+                         (where, "down", (mlp.down_proj.weight,), lambda mlp=mlp: (mlp.down_proj.weight, None))]
+            return {"layers": [{} for _ in self.model.layers]}, plan + [((), "lm_head", (self._head_weight(),), lambda: (self._head_weight(), None))]
+
+        return self._packed.refresh(list(self.parameters()) if train else None, plan, lambda w, b: PackedLinear(w, b, self.precision, backward=train))
 
     def _rope_tables(self, device):
         """cos / sin [max_position_embeddings, 64] fp32 as HF's Qwen3RotaryEmbedding forms them: fp32 inv_freq, fp32 outer product, then cos / sin."""
@@ -413,7 +402,6 @@ class Qwen3Decoder(nn.Module):
         logits = padded.view(B, L, -1)[:, :, : self.config.vocab_size]
         if labels is None:
             return logits
-        from .native_decoder import cross_entropy
         return logits, cross_entropy(padded, self._shifted(labels, padded.device).reshape(-1), self.config.vocab_size)[0]
 
     @staticmethod
@@ -450,7 +438,6 @@ class _Qwen3Graph(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, inputs_embeds, dec: "Qwen3Decoder", shifted, holder, *trained):
-        from .native_decoder import cross_entropy
         c, dev = dec.config, inputs_embeds.device
         B, L, d = inputs_embeds.shape
         Hq, Hkv, I, eps = c.num_attention_heads, c.num_key_value_heads, c.intermediate_size, c.rms_norm_eps
@@ -565,7 +552,6 @@ class _EmbedLookup(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .native_decoder import embed_backward
         B, L = ctx.ids.shape
         d = g.shape[-1]
         dtok = torch.zeros((ctx.rows, d), dtype=torch.float32, device=g.device)

@@ -31,7 +31,8 @@ of d(loss) / d(encoder states) from one more.
 
 Full-parameter fine-tuning (`train_base=True`): every base parameter requires grad, the backward also forms their gradients
 (weight-gradient GEMM, pitched column sums, LayerNorm parameter gradients, `awt_op_embed_backward` for the tied table and the positions), and
-`packed()` re-packs the stepped weights into the handles it already has (`awt_weight_update`).
+`packed()` re-packs the stepped weights into the handles it already has (`awt_weight_update`): its plan runs on `PackedSet`, the one tracker of
+parameter versions (music2midi's decoder uses it too).  A `PackedLinear` owns its handle and refuses copy / pickle; a copied `PackedSet` is empty.
 """
 from __future__ import annotations
 
@@ -105,6 +106,9 @@ class PackedLinear:
             raise ValueError(f"PackedLinear.update: the handle lives on {self.device}, the weight on {w.device}")
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().awt_weight_update(_lib.ctx(self.device), self.handle, _lib.ptr(w), _lib.ptr(b), _lib.stream_handle()))
+
+    def __reduce_ex__(self, protocol):
+        raise TypeError("PackedLinear owns a library handle (awt_weight) that its __del__ frees: it cannot be copied or pickled; pack the weight again")
 
     def __del__(self):
         try:
@@ -302,6 +306,40 @@ class PackedBatch:
         with torch.cuda.device(b.device):
             _lib.check(_lib.lib().awt_bmm_pack(_lib.ctx(b.device), _lib.ptr(b), self.K, self.N * self.K, self.batch, self.N, self.K, _lib.ptr(self.buf),
                                                self.buf.numel(), _lib.stream_handle()))
+
+
+class PackedSet:
+    """The packed objects of one module (`objects`: a dict of PackedLinear / PackedBatch, or None) and the parameter versions they were packed from.
+    A copy or a pickle of it is EMPTY: the copy of a model packs its own weights at first use and never shares or frees the original's handles."""
+    objects = _versions = None
+
+    def __reduce_ex__(self, protocol):
+        return PackedSet, ()
+
+    def invalidate(self) -> None:
+        self.objects = None               # the next `refresh` builds every object: after load_state_dict, _apply (.to(), .float()), a resized table
+
+    def refresh(self, params, plan, new) -> dict:
+        """`objects`, brought up to date with `params`: the parameters to watch (walked once per call), or None to pack once and follow nothing.
+        plan() -> (the empty result, [(where, key, sources, make)]): result[key], or result[name][i][key] with where = (name, i), is made of the
+        parameters `sources` out of the operand tuple make() returns.  The same Parameter objects at new versions (an optimizer step) pack only the
+        entries with a changed source again, in place (`update(*operands)`); anything else builds every object (`new(*operands)`)."""
+        vers = None if params is None else [(id(p), p._version) for p in params]           # identity too: a replaced Parameter starts at version 0 again
+        if self.objects is not None and self._versions == vers:
+            return self.objects
+        fresh = self.objects is None or None in (vers, self._versions) or [i for i, _ in self._versions] != [i for i, _ in vers]
+        changed = set() if fresh else {i for (i, v), (_, v0) in zip(vers, self._versions) if v != v0}
+        pk, entries = plan()
+        pk = pk if fresh else self.objects
+        with torch.no_grad():
+            for where, key, sources, make in entries:
+                slot = pk[where[0]][where[1]] if where else pk
+                if fresh:
+                    slot[key] = new(*make())
+                elif any(id(p) in changed for p in sources):
+                    slot[key].update(*make())
+        self.objects, self._versions = pk, vers
+        return pk
 
 
 def bmm(a, pb: PackedBatch, M: int, out, resid=None, a_kmajor=None) -> None:
@@ -560,9 +598,7 @@ class NativeWhisperDecoder(nn.Module):
                         a = unit_variates(f"decoder.layers.{i}.{att}.{proj}.lora_A", lora.r * d, lora_seed) / math.sqrt(d)
                         leaf.lora_A = nn.Parameter(torch.from_numpy(a.astype("float32").reshape(lora.r, d)), requires_grad=True)
                         leaf.lora_B = nn.Parameter(torch.zeros(d, lora.r), requires_grad=True)          # B = 0: the adapter starts inert
-        self._packed: Optional[Dict[str, object]] = None
-        self._versions: Optional[Tuple[int, ...]] = None
-        import os
+        self._packed = PackedSet()
         self.cross_mode = os.environ.get("AWT_DECODER_CROSS", "auto")          # "auto" | "kv" | "absorbed" (A/B runs: tools, bench)
         if self.cross_mode not in ("auto", "kv", "absorbed"):
             raise ValueError("AWT_DECODER_CROSS must be auto, kv or absorbed")
@@ -619,61 +655,44 @@ class NativeWhisperDecoder(nn.Module):
     # ------------------------------------------------------------------------------------------------ packing
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         res = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._packed = None
+        self._packed.invalidate()
         return res
 
     def _apply(self, fn, *a, **kw):
-        self._packed = None
+        self._packed.invalidate()
         return super()._apply(fn, *a, **kw)
 
     def packed(self) -> Dict[str, object]:
-        """The weights as `awt_weight` handles, brought up to date when a parameter changed: per layer the fused self-attention q|k|v
-        projection, the two output projections, the cross-attention query projection, fc1, fc2; the fused cross-attention k|v
-        projection of ALL layers (one GEMM over the encoder output) and the tied vocabulary projection."""
-        vers = tuple((id(p), p._version) for n, p in self.named_parameters() if "lora_" not in n)     # identity too: a replaced Parameter object starts at version 0 again
-        if self._packed is not None and self._versions == vers:
-            return self._packed
-        prec = self.precision
-        H, d = self.heads, self.d
-        zeros = torch.zeros(d, device=self.embed_tokens.weight.device)
-        # every packed object as (where it lives in the result, the parameters it is made of, what to pack): a (weight, bias) pair becomes a
-        # PackedLinear, a [H, N, K] tensor the per-head B operands of _AbsorbedCross (a PackedBatch)
-        plan = []
-        for i, lay in enumerate(self.layers):
-            sa, ca = lay.self_attn, lay.encoder_attn
-            where = ("layers", i)
-            plan += [(where, "qkv", (sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight, sa.q_proj.bias, sa.v_proj.bias),
-                      lambda sa=sa: (torch.cat([sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight]), torch.cat([sa.q_proj.bias, zeros, sa.v_proj.bias]))),
-                     (where, "so", (sa.out_proj.weight, sa.out_proj.bias), lambda sa=sa: (sa.out_proj.weight, sa.out_proj.bias)),
-                     (where, "cq", (ca.q_proj.weight, ca.q_proj.bias), lambda ca=ca: (ca.q_proj.weight, ca.q_proj.bias)),
-                     (where, "co", (ca.out_proj.weight, ca.out_proj.bias), lambda ca=ca: (ca.out_proj.weight, ca.out_proj.bias)),
-                     (where, "fc1", (lay.fc1.weight, lay.fc1.bias), lambda lay=lay: (lay.fc1.weight, lay.fc1.bias)),
-                     (where, "fc2", (lay.fc2.weight, lay.fc2.bias), lambda lay=lay: (lay.fc2.weight, lay.fc2.bias))]
-            where = ("cross_heads", i)                                             # per-head blocks of W_k / W_v as batched B operands
-            plan += [(where, "k", (ca.k_proj.weight,), lambda ca=ca: ca.k_proj.weight.detach().view(H, 64, d)),
-                     (where, "kT", (ca.k_proj.weight,), lambda ca=ca: ca.k_proj.weight.detach().view(H, 64, d).transpose(1, 2)),
-                     (where, "v", (ca.v_proj.weight,), lambda ca=ca: ca.v_proj.weight.detach().view(H, 64, d)),
-                     (where, "vT", (ca.v_proj.weight,), lambda ca=ca: ca.v_proj.weight.detach().view(H, 64, d).transpose(1, 2))]
-        att = [l.encoder_attn for l in self.layers]
-        plan += [((), "ckv", tuple(t for a in att for t in (a.k_proj.weight, a.v_proj.weight, a.v_proj.bias)),
-                  lambda: (torch.cat([w for a in att for w in (a.k_proj.weight, a.v_proj.weight)]), torch.cat([b for a in att for b in (zeros, a.v_proj.bias)]))),
-                 ((), "vocab", (self.embed_tokens.weight,), lambda: (self.embed_tokens.weight, None))]
-        # the same Parameter objects at new versions (an optimizer step of the train_base mode): only what changed is packed again, into the
-        # handles that exist; anything else (first use, load_state_dict, .to(), a replaced Parameter) builds every handle
-        fresh = self._packed is None or tuple(i for i, _ in self._versions) != tuple(i for i, _ in vers)
-        changed = set() if fresh else {i for (i, v), (_, v0) in zip(vers, self._versions) if v != v0}
-        pk: Dict[str, object] = {"layers": [{} for _ in self.layers], "cross_heads": [{} for _ in self.layers]} if fresh else self._packed
-        with torch.no_grad():
-            for where, key, sources, make in plan:
-                slot = pk[where[0]][where[1]] if where else pk
-                if fresh:
-                    what = make()
-                    slot[key] = PackedLinear(what[0], what[1], prec) if isinstance(what, tuple) else PackedBatch(what)
-                elif any(id(p) in changed for p in sources):
-                    what = make()
-                    slot[key].update(*what) if isinstance(what, tuple) else slot[key].update(what)
-        self._packed, self._versions = pk, vers
-        return pk
+        """The weights as `awt_weight` handles, brought up to date when a parameter changed (`PackedSet`; what an optimizer step of the train_base
+        mode needs): per layer the fused self-attention q|k|v projection, the two output projections, the cross-attention query projection, fc1,
+        fc2; the fused cross-attention k|v projection of ALL layers (one GEMM over the encoder output) and the tied vocabulary projection."""
+        def plan():
+            # the operands: a (weight, bias) pair becomes a PackedLinear, one [H, N, K] tensor the per-head B operands of _AbsorbedCross (a PackedBatch)
+            H, d = self.heads, self.d
+            zeros = torch.zeros(d, device=self.embed_tokens.weight.device)
+            plan = []
+            for i, lay in enumerate(self.layers):
+                sa, ca = lay.self_attn, lay.encoder_attn
+                where = ("layers", i)
+                plan += [(where, "qkv", (sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight, sa.q_proj.bias, sa.v_proj.bias),
+                          lambda sa=sa: (torch.cat([sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight]), torch.cat([sa.q_proj.bias, zeros, sa.v_proj.bias]))),
+                         (where, "so", (sa.out_proj.weight, sa.out_proj.bias), lambda sa=sa: (sa.out_proj.weight, sa.out_proj.bias)),
+                         (where, "cq", (ca.q_proj.weight, ca.q_proj.bias), lambda ca=ca: (ca.q_proj.weight, ca.q_proj.bias)),
+                         (where, "co", (ca.out_proj.weight, ca.out_proj.bias), lambda ca=ca: (ca.out_proj.weight, ca.out_proj.bias)),
+                         (where, "fc1", (lay.fc1.weight, lay.fc1.bias), lambda lay=lay: (lay.fc1.weight, lay.fc1.bias)),
+                         (where, "fc2", (lay.fc2.weight, lay.fc2.bias), lambda lay=lay: (lay.fc2.weight, lay.fc2.bias))]
+                where = ("cross_heads", i)                                             # per-head blocks of W_k / W_v as batched B operands
+                plan += [(where, "k", (ca.k_proj.weight,), lambda ca=ca: (ca.k_proj.weight.detach().view(H, 64, d),)),
+                         (where, "kT", (ca.k_proj.weight,), lambda ca=ca: (ca.k_proj.weight.detach().view(H, 64, d).transpose(1, 2),)),
+                         (where, "v", (ca.v_proj.weight,), lambda ca=ca: (ca.v_proj.weight.detach().view(H, 64, d),)),
+                         (where, "vT", (ca.v_proj.weight,), lambda ca=ca: (ca.v_proj.weight.detach().view(H, 64, d).transpose(1, 2),))]
+            att = [l.encoder_attn for l in self.layers]
+            plan += [((), "ckv", tuple(t for a in att for t in (a.k_proj.weight, a.v_proj.weight, a.v_proj.bias)),
+                      lambda: (torch.cat([w for a in att for w in (a.k_proj.weight, a.v_proj.weight)]), torch.cat([b for a in att for b in (zeros, a.v_proj.bias)]))),
+                     ((), "vocab", (self.embed_tokens.weight,), lambda: (self.embed_tokens.weight, None))]
+            return {"layers": [{} for _ in self.layers], "cross_heads": [{} for _ in self.layers]}, plan
+
+        return self._packed.refresh([p for n, p in self.named_parameters() if "lora_" not in n], plan, lambda w, *b: PackedLinear(w, *b, self.precision) if b else PackedBatch(w))
 
     # ------------------------------------------------------------------------------------------------ forward pieces
     def cross_kv(self, enc: torch.Tensor, precision: Optional[str] = None) -> torch.Tensor:
