@@ -97,7 +97,9 @@ __device__ __forceinline__ float4 bn_xhat(const BnCoef& k, const float4 x) { ret
 __device__ __forceinline__ float4 bn_act(const BnCoef& k, const float4 xh) {      // pre-ReLU BatchNorm output
   return make_float4(fmaf(xh.x, k.gamma.x, k.beta.x), fmaf(xh.y, k.gamma.y, k.beta.y), fmaf(xh.z, k.gamma.z, k.beta.z), fmaf(xh.w, k.gamma.w, k.beta.w));
 }
-__device__ __forceinline__ float4 relu4(const float4 z) { return max4(z, f4(0.f)); }
+// relu(NaN) = NaN as in torch (fmaxf(NaN, 0) would be 0: a channel whose statistics are NaN would come out as clean zeros)
+__device__ __forceinline__ float relu1(float z) { return z <= 0.f ? 0.f : z; }
+__device__ __forceinline__ float4 relu4(const float4 z) { return make_float4(relu1(z.x), relu1(z.y), relu1(z.z), relu1(z.w)); }
 __device__ __forceinline__ float4 gate(const float4 z, const float4 g) {           // g where z > 0: ReLU's derivative
   return make_float4(z.x > 0.f ? g.x : 0.f, z.y > 0.f ? g.y : 0.f, z.z > 0.f ? g.z : 0.f, z.w > 0.f ? g.w : 0.f);
 }

@@ -183,7 +183,9 @@ __device__ __forceinline__ float gelu_erf(float x) {
   q = fmaf(q, tc, 1.6279137134552002f);
   const float e = __builtin_amdgcn_exp2f(fmaf(tc - t, 12.5f, -tc * q));
   const float h = 0.5f * x;
-  return fmaf(-fabsf(h), e, h + fabsf(h));
+  // |h|'s partner e is exactly 0 far out in the tail, so |h| is clamped to the largest finite value: x = +inf gives -FLT_MAX 0 + inf = +inf (as torch) where
+  // inf 0 would be NaN; no finite x changes.  x = -inf stays NaN through h + |h| (torch: -inf 0), and NaN stays NaN the same way.
+  return fmaf(-fminf(fabsf(h), 3.402823466e+38f), e, h + fabsf(h));
 }
 
 // Fragment-major weight layout.  Every "W-side" GEMM operand is library-owned and static within a step, so it is stored

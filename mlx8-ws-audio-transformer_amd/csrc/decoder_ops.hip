@@ -132,8 +132,10 @@ __global__ __launch_bounds__(256) void gelu_fwd_kernel(const float* __restrict__
     reinterpret_cast<float4*>(y)[i] = make_float4(gelu_erf(v.x), gelu_erf(v.y), gelu_erf(v.z), gelu_erf(v.w));
   }
 }
+// x = +inf: gelu is the identity out there (gelu_erf(+inf) = +inf), so the slope is 1, not 1 + inf 0.  x = -inf and NaN give NaN, as the forward does.
 __device__ __forceinline__ float dgelu(float x) {   // d/dx gelu(x) = Phi(x) + x phi(x)
-  return 0.5f * (1.0f + erf_fast(x * 0.70710678118654752440f)) + x * 0.39894228040143267794f * __expf(-0.5f * x * x);
+  const float tail = x == __builtin_inff() ? 0.f : x * 0.39894228040143267794f * __expf(-0.5f * x * x);
+  return 0.5f * (1.0f + erf_fast(x * 0.70710678118654752440f)) + tail;
 }
 __global__ __launch_bounds__(256) void gelu_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, int64_t n4, float* dx) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
@@ -175,7 +177,7 @@ __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logit
   const float inv = 1.0f / sum;
   for (int i = tid; i < ld; i += 256) {
     float v = 0.f;
-    if (i < vocab) v = (__expf(z[i] - mx) * inv - (i == lab ? 1.0f : 0.0f)) * scale;
+    if (i < vocab && scale != 0.f) v = (__expf(z[i] - mx) * inv - (i == lab ? 1.0f : 0.0f)) * scale;   // an ignored row's gradient is 0 whatever it holds (NaN 0 is not)
     g[i] = v;
   }
 }
@@ -267,7 +269,7 @@ __global__ __launch_bounds__(256) void ln_param_grad_kernel(const float* __restr
 #pragma unroll
     for (int j = 0; j < kColMaxChunks; ++j) {
       const int c = lane + 64 * j;
-      if (j < nch && c < d) { const float g = gh ? bf16_to_f32(gh[c]) + (gl ? bf16_to_f32(gl[c]) : 0.f) : gr[c]; db[j] += g; if (xr) dg[j] += g * (xv[j] - mean) * rstd; }
+      if (j < nch && c < d) { const float g = gh ? bf16_to_f32(gh[c]) + (gl ? bf16_to_f32(gl[c]) : 0.f) : gr[c]; db[j] += g; if (xr) dg[j] += g * ((xv[j] - mean) * rstd); }   // xhat first: g (x - mean) may overflow where rstd = 0 makes xhat 0 (inf 0 = NaN)
     }
   }
   // waves -> one partial row per slab
